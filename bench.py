@@ -7,13 +7,16 @@ gfx950 kernels, fp32 master weights + fused AdamW, bucketed gradient all-reduce 
 overlapped with backward.  Synthetic token data, random-init weights.
 
 Timed region: exactly K full training steps (forward, backward + all-reduce, optimizer
-step), bracketed by barrier + device synchronize, max over ranks.  After it, the checkpoint
-phase measures a DCP-format sharded save of the full train state (model + AdamW state +
-step): time until training can resume (HBM snapshot enqueued), time until every shard is
-durable and `.metadata` committed, training throughput while the write is in flight, and
-the restore wall-clock (sharded read + RCCL broadcast into the live model/optimizer).
+step), bracketed by barrier + device synchronize, max over ranks.  A plain run stops there: it
+prints the result line (and, with --dump-outputs DIR, writes the last step's loss and updated
+parameters as .npy files).  With --full, the checkpoint phase then measures a DCP-format
+sharded save of the full train state (model + AdamW state + step): time until training can
+resume (HBM snapshot enqueued), time until every shard is durable and `.metadata` committed,
+training throughput while the write is in flight, and the restore wall-clock (sharded read +
+RCCL broadcast into the live model/optimizer).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model gpt2-small] [--batch 16]
+    python bench.py --full ...      (+ checkpoint phase; at N > 1 preflight, in-sync check, bucket sweep)
     python bench.py --model resnet18 [--batch 256] [--image-size 224]      (BASELINE config 2)
     python bench.py --model llama3-8b [--batch 1] [--seq-len 2048]         (BASELINE config 4)
     torchrun --nproc-per-node N bench.py --gpus N ...
@@ -52,6 +55,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: the checkpoint "
+                         "phase, the multi-rank preflight (all-reduce check + bus bandwidth), the cross-rank "
+                         "in-sync check and the bucket sweep.  A plain run only sets up, warms up, times the "
+                         "steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32): the loss and the updated parameters (a fixed seeded sample "
+                         "of a large model's)")
     ap.add_argument("--model", default="gpt2-small")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU per step (model default if unset)")
     ap.add_argument("--seq-len", type=int, default=None)
@@ -68,7 +80,7 @@ def main():
                     help="1: each bucket's fused optimizer update runs on a side stream as soon as its gradients "
                          "are final (optim/overlap.py; bitwise the plain step's result).  Off by default: measured "
                          "+0.1 ms on GPT-2 and ResNet-18 on one GPU (profiles/optim_overlap_ab.txt)")
-    ap.add_argument("--no-ckpt", action="store_true")
+    ap.add_argument("--no-ckpt", action="store_true", help="--full without the checkpoint phase")
     ap.add_argument("--ckpt-dir", default=None)
     ap.add_argument("--ckpt-scope", default="full", choices=["full", "model"],
                     help="full = model + optimizer train state (default); model = weights only")
@@ -91,7 +103,7 @@ def main():
                          "one process.  Off by default: ResNet-18 measured 8.14 vs 8.08 ms/step eager "
                          "(profiles/resnet_hipgraph_ab_r5.txt)")
     ap.add_argument("--sweep", type=int, default=1, choices=[0, 1],
-                    help="N > 1: after the timed run, a short bucket_cap_mb x grad-comm-dtype sweep (comm.sweep)")
+                    help="--full at N > 1: after the timed run, a short bucket_cap_mb x grad-comm-dtype sweep (comm.sweep)")
     ap.add_argument("--ckpt-budget-s", type=float, default=float(os.environ.get("RTDC_BENCH_CKPT_BUDGET_S", 300)),
                     help="wall-clock budget of the checkpoint phase; on overrun the measured headline is printed "
                          "with phase_timed_out and the run exits")
@@ -154,7 +166,7 @@ def main():
         _ext.gpu_ext()  # native kernels are mandatory on the GPU path
     sync = (lambda: None) if args.cpu else torch.cuda.synchronize
     _progress(rank, "process group up" if dist_on else "start")
-    pre = preflight(world, rank, dev, args) if dist_on else None
+    pre = preflight(world, rank, dev, args) if dist_on and args.full else None
     torch.manual_seed(1234)
     wl = build_workload(args, dev, rank)
     model, opt = wl["model"], wl["opt"]
@@ -232,7 +244,9 @@ def main():
     final_loss = loss.item()
     comm_plan = net.comm_plan() if dist_on else None
     # every rank must hold bitwise the same parameters (and, without ZeRO, optimizer state)
-    in_sync = ranks_in_sync(model, opt, world, dev) if dist_on else None
+    in_sync = ranks_in_sync(model, opt, world, dev) if dist_on and args.full else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
 
     out = headline(args, wl, model, world, B, T, ms_per_step, samples_per_s, final_loss, overlap, dist_on,
                    comm_plan, pre, in_sync, dev)
@@ -242,7 +256,7 @@ def main():
     wd = PhaseWatchdog(out, rank)
     _progress(rank, f"headline measured: {ms_per_step:.3f} ms/step")
 
-    if not args.no_ckpt:
+    if args.full and not args.no_ckpt:
         # the throughput above is measured and must be reported even if the checkpoint phase
         # fails (e.g. a filesystem that refuses the shard writes): the failure is reported too
         with wd.phase("checkpoint", args.ckpt_budget_s):
@@ -253,7 +267,7 @@ def main():
                 print(f"[bench] rank {rank}: {ck['ckpt_unmeasured']}", file=sys.stderr, flush=True)
         out.update(ck)
 
-    if dist_on and args.sweep and args.zero == 0 and not args.overlap_opt:
+    if args.full and dist_on and args.sweep and args.zero == 0 and not args.overlap_opt:
         with wd.phase("sweep", args.sweep_budget_s):
             try:
                 sweep = comm_sweep(args, model, opt, net, cur, step, world, sync)
@@ -380,6 +394,33 @@ def headline(args, wl, model, world, B, T, ms_per_step, samples_per_s, final_los
         out["ranks_in_sync"] = in_sync
     out["comm"] = comm
     return out
+
+
+DUMP_SAMPLE_ELEMS = 1 << 22  # 16 MB of float32 per dumped array at most
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, model) -> None:
+    """--dump-outputs: what the last timed step handed back, as float32 .npy files - `loss.npy`
+    and `params.npy`, the updated parameters in `named_parameters()` order, flattened and
+    concatenated.  A model with more than DUMP_SAMPLE_ELEMS parameter elements contributes a
+    sample instead: from each parameter a share proportional to its size, at indices drawn from
+    a fixed-seed generator, so two builds given the same arguments dump the same elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    params = [p for _n, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    g = torch.Generator().manual_seed(20240607)
+    parts = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if total > DUMP_SAMPLE_ELEMS:
+            k = min(flat.numel(), max(1, flat.numel() * DUMP_SAMPLE_ELEMS // total))
+            idx = torch.randint(flat.numel(), (k,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(parts).numpy())
 
 
 def preflight(world, rank, dev, args) -> dict:

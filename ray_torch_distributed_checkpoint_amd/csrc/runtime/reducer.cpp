@@ -340,6 +340,10 @@ class GradBucketEngine {
     return {lo + zero_rank_ * sh, lo + (zero_rank_ + 1) * sh};
   }
 
+  // Enqueue note: a collective is handed to the process group with the GIL released, as torch's
+  // own Python bindings do.  gloo's worker threads retire a finished Work under the queue mutex
+  // that enqueue takes, and retiring it can need the GIL: with the GIL held here, a worker that
+  // is late (fewer cores than ranks) and this thread wait for each other forever.
   void launch(size_t b) {
     const int64_t lo = bounds_[b], hi = bounds_[b + 1];
     at::Tensor src = flat_.slice(0, lo, hi);
@@ -385,10 +389,12 @@ class GradBucketEngine {
       at::Tensor out = t[0].slice(0, olo - lo, ohi - lo);
       c10d::ReduceScatterOptions ro;
       ro.reduceOp = use_avg_ ? c10d::ReduceOp(c10d::ReduceOp::AVG) : c10d::ReduceOp(c10d::ReduceOp::SUM);
+      pybind11::gil_scoped_release nogil;  // see enqueue note above launch()
       works_[b] = pg_->_reduce_scatter_base(out, t[0], ro);
     } else {
       c10d::AllreduceOptions opts;
       opts.reduceOp = use_avg_ ? c10d::ReduceOp(c10d::ReduceOp::AVG) : c10d::ReduceOp(c10d::ReduceOp::SUM);
+      pybind11::gil_scoped_release nogil;
       works_[b] = pg_->allreduce(t, opts);
     }
     launched_[b] = true;
@@ -432,6 +438,7 @@ class GradBucketEngine {
         t = dst;
       }
       std::vector<at::Tensor> tv{t};
+      pybind11::gil_scoped_release nogil;
       piece_works_.push_back(pg_->allreduce(tv, opts));
     }
     if (side_) {

@@ -42,16 +42,19 @@ int rtdc_xent(const void* logits, void* dlogits, const int64_t* target, float* l
               hipStream_t st);
 int rtdc_adamw(const void* chunks, int nchunks, float* p, const float* g, float* m, float* v, void* shadow,
                float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-               float grad_scale, const int* skip, hipStream_t st);
+               float grad_scale, const int* skip, const float* clip, hipStream_t st);
 int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow, float lr,
              float momentum, float dampening, float wd, int nesterov, int first, float grad_scale,
-             const int* skip, hipStream_t st);
+             const int* skip, const float* clip, hipStream_t st);
 int rtdc_f32_to_bf16(const float* x, void* y, long long n, hipStream_t st);
 int rtdc_f32_to_bf16_t(const float* x, void* y, int R, int C, hipStream_t st);
 int rtdc_bf16_transpose_multi(const void* const* src, void* const* dst, const int* R, const int* C, int n,
                               void* jobs_dev, hipStream_t st);
 int rtdc_bf16_transpose_jobs_bytes();
-int rtdc_sumsq(const void* chunks, int nchunks, const float* g, float* partial, hipStream_t st);
+int rtdc_gradnorm_partial(const void* chunks, int nchunks, const float* g, double* partial, hipStream_t st);
+int rtdc_gradnorm_finalize(const double* partial, int n, float grad_scale, float max_norm, float* out, double* local,
+                           hipStream_t st);
+int rtdc_gradnorm_combine(const double* sums, int world, float grad_scale, float max_norm, float* out, hipStream_t st);
 int rtdc_softmax_fwd(const void* S, void* P, float* lse, long long rows, int T, int causal, hipStream_t st);
 int rtdc_softmax_bwd(const void* P, const void* dP, void* dS, long long rows, int T, int causal,
                      hipStream_t st);
@@ -374,21 +377,22 @@ static void check_chunks(const Tensor& chunks, int64_t nchunks, const char* op) 
 }
 static void adamw(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, Tensor m, Tensor v,
                   c10::optional<Tensor> shadow, double lr, double b1, double b2, double eps, double wd, double bc1,
-                  double bc2_sqrt, double grad_scale, int64_t skip_ptr) {
+                  double bc2_sqrt, double grad_scale, int64_t skip_ptr, int64_t clip_ptr) {
   check_chunks(chunks, nchunks, "adamw");
   check_rc(rtdc_adamw(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                       v.data_ptr<float>(), ptr_or_null(shadow), (float)lr, (float)b1, (float)b2, (float)eps,
                       (float)wd, (float)bc1, (float)bc2_sqrt, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
-                      cur_stream()),
+                      (const float*)(uintptr_t)clip_ptr, cur_stream()),
            "adamw");
 }
 static void sgd(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, c10::optional<Tensor> buf,
                 c10::optional<Tensor> shadow, double lr, double momentum, double dampening, double wd,
-                bool nesterov, bool first, double grad_scale, int64_t skip_ptr) {
+                bool nesterov, bool first, double grad_scale, int64_t skip_ptr, int64_t clip_ptr) {
   check_chunks(chunks, nchunks, "sgd");
   check_rc(rtdc_sgd(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(),
                     (float*)ptr_or_null(buf), ptr_or_null(shadow), (float)lr, (float)momentum, (float)dampening,
-                    (float)wd, nesterov, first, (float)grad_scale, (const int*)(uintptr_t)skip_ptr, cur_stream()),
+                    (float)wd, nesterov, first, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
+                    (const float*)(uintptr_t)clip_ptr, cur_stream()),
            "sgd");
 }
 static void f32_to_bf16(Tensor x, Tensor y) {
@@ -430,10 +434,42 @@ static void f32_to_bf16_t(Tensor x, Tensor y) {
   check_rc(rtdc_f32_to_bf16_t(x.data_ptr<float>(), y.data_ptr(), (int)x.size(0), (int)x.size(1), cur_stream()),
            "f32_to_bf16_t");
 }
-static void sumsq(Tensor chunks, int64_t nchunks, Tensor g, Tensor partial) {
-  check_chunks(chunks, nchunks, "sumsq");
-  check_rc(rtdc_sumsq(chunks.data_ptr(), (int)nchunks, g.data_ptr<float>(), partial.data_ptr<float>(), cur_stream()),
-           "sumsq");
+// global gradient-norm clipping (kernels/optim.hip): partial[offset + ci] = sum of squares of
+// chunk ci; finalize sums partial[0:n] -> out = {total_norm, coef}, or (ZeRO-1) local[0] = sum;
+// combine adds the all-gathered local sums in rank order -> out.  The sums (partial, local,
+// sums) are fp64 buffers, g and out fp32.
+static void check_buf(const Tensor& t, at::ScalarType dt, int64_t n, const char* op, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous() && t.numel() >= n, op, ": ", what,
+              " must be a contiguous ", dt, " GPU tensor of >= ", n, " elements");
+}
+static void check_f32(const Tensor& t, int64_t n, const char* op, const char* what) { check_buf(t, at::kFloat, n, op, what); }
+static void check_f64(const Tensor& t, int64_t n, const char* op, const char* what) { check_buf(t, at::kDouble, n, op, what); }
+static void gradnorm_partial(Tensor chunks, int64_t nchunks, Tensor g, Tensor partial, int64_t offset) {
+  check_chunks(chunks, nchunks, "gradnorm_partial");
+  TORCH_CHECK(offset >= 0 && nchunks >= 0, "gradnorm_partial: offset / nchunks");
+  check_f32(g, 0, "gradnorm_partial", "g");
+  check_f64(partial, offset + nchunks, "gradnorm_partial", "partial");
+  check_rc(rtdc_gradnorm_partial(chunks.data_ptr(), (int)nchunks, g.data_ptr<float>(),
+                                 partial.data_ptr<double>() + offset, cur_stream()),
+           "gradnorm_partial");
+}
+static void gradnorm_finalize(Tensor partial, int64_t n, double grad_scale, double max_norm, Tensor out,
+                              c10::optional<Tensor> local) {
+  TORCH_CHECK(n >= 0, "gradnorm_finalize: n");
+  check_f64(partial, n, "gradnorm_finalize", "partial");
+  check_f32(out, 2, "gradnorm_finalize", "out");
+  if (local.has_value()) check_f64(*local, 1, "gradnorm_finalize", "local");
+  check_rc(rtdc_gradnorm_finalize(partial.data_ptr<double>(), (int)n, (float)grad_scale, (float)max_norm,
+                                  out.data_ptr<float>(), (double*)ptr_or_null(local), cur_stream()),
+           "gradnorm_finalize");
+}
+static void gradnorm_combine(Tensor sums, int64_t world, double grad_scale, double max_norm, Tensor out) {
+  TORCH_CHECK(world >= 1, "gradnorm_combine: world");
+  check_f64(sums, world, "gradnorm_combine", "sums");
+  check_f32(out, 2, "gradnorm_combine", "out");
+  check_rc(rtdc_gradnorm_combine(sums.data_ptr<double>(), (int)world, (float)grad_scale, (float)max_norm,
+                                 out.data_ptr<float>(), cur_stream()),
+           "gradnorm_combine");
 }
 
 // ---------------------------------------------------------------------------------- attention softmax
@@ -1013,15 +1049,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent", &xent);
   m.def("adamw", &adamw, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("m"),
         py::arg("v"), py::arg("shadow"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
-        py::arg("bc1"), py::arg("bc2_sqrt"), py::arg("grad_scale"), py::arg("skip_ptr") = 0);
+        py::arg("bc1"), py::arg("bc2_sqrt"), py::arg("grad_scale"), py::arg("skip_ptr") = 0,
+        py::arg("clip_ptr") = 0);
   m.def("sgd", &sgd, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("buf"),
         py::arg("shadow"), py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("wd"),
-        py::arg("nesterov"), py::arg("first"), py::arg("grad_scale"), py::arg("skip_ptr") = 0);
+        py::arg("nesterov"), py::arg("first"), py::arg("grad_scale"), py::arg("skip_ptr") = 0,
+        py::arg("clip_ptr") = 0);
   m.def("f32_to_bf16", &f32_to_bf16);
   m.def("f32_to_bf16_t", &f32_to_bf16_t);
   m.def("bf16_transpose_multi", &bf16_transpose_multi);
   m.def("bf16_transpose_jobs_bytes", &rtdc_bf16_transpose_jobs_bytes);
-  m.def("sumsq", &sumsq);
+  m.def("gradnorm_partial", &gradnorm_partial, py::arg("chunks"), py::arg("nchunks"), py::arg("g"),
+        py::arg("partial"), py::arg("offset") = 0);
+  m.def("gradnorm_finalize", &gradnorm_finalize, py::arg("partial"), py::arg("n"), py::arg("grad_scale"),
+        py::arg("max_norm"), py::arg("out"), py::arg("local") = py::none());
+  m.def("gradnorm_combine", &gradnorm_combine);
   m.def("softmax_fwd", &softmax_fwd);
   m.def("softmax_bwd", &softmax_bwd);
   m.def("embed_fwd", &embed_fwd);

@@ -41,8 +41,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ ch
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    bf16_t* __restrict__ shadow, float lr, float b1,
                                                    float b2, float eps, float wd, float bc1,
-                                                   float bc2_sqrt, float grad_scale, const int* skip) {
+                                                   float bc2_sqrt, float grad_scale, const int* skip,
+                                                   const float* __restrict__ clip) {
   if (comm_poisoned(skip)) return;
+  // clip (optional): {total_norm, coef} of gradnorm_finalize_kernel - the clip coefficient folds
+  // into the gradient multiply
+  const float gs = clip ? grad_scale * clip[1] : grad_scale;
   const float step_size = lr / bc1;
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const Chunk c = chunks[ci];
@@ -54,7 +58,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ ch
         f32x4 mm = *(f32x4*)(m + so), vv = *(f32x4*)(v + so);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float gr = gg[e] * grad_scale;
+          const float gr = gg[e] * gs;
           float pe = pp[e] * decay;
           mm[e] = b1 * mm[e] + (1.f - b1) * gr;
           vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ ch
       } else {
         for (int e = 0; e < 4 && i + e < c.len; ++e) {
           const long long oe = o + e, se = so + e;
-          const float gr = g[oe] * grad_scale;
+          const float gr = g[oe] * gs;
           float pe = p[oe] * decay;
           m[se] = b1 * m[se] + (1.f - b1) * gr;
           v[se] = b2 * v[se] + (1.f - b2) * gr * gr;
@@ -89,13 +93,15 @@ __global__ __launch_bounds__(256) void sgd_kernel(const Chunk* __restrict__ chun
                                                  float* __restrict__ p, const float* __restrict__ g,
                                                  float* __restrict__ buf, bf16_t* __restrict__ shadow,
                                                  float lr, float momentum, float dampening, float wd,
-                                                 int nesterov, int first, float grad_scale, const int* skip) {
+                                                 int nesterov, int first, float grad_scale, const int* skip,
+                                                 const float* __restrict__ clip) {
   if (comm_poisoned(skip)) return;
+  const float gs = clip ? grad_scale * clip[1] : grad_scale;
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const Chunk c = chunks[ci];
     const float w = c.decay ? wd : 0.f;
     auto upd = [&](float gv, float& pe, float& b) {
-      float d = gv * grad_scale;
+      float d = gv * gs;
       d += w * pe;
       if (momentum != 0.f) {
         b = first ? d : momentum * b + (1.f - dampening) * d;
@@ -204,20 +210,117 @@ __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const bf16_t* __restri
   }
 }
 
-// sum of squares per chunk -> partial[ci] (for grad-norm clipping); deterministic
-__global__ __launch_bounds__(256) void sumsq_kernel(const Chunk* __restrict__ chunks, int nchunks,
-                                                   const float* __restrict__ g, float* __restrict__ partial) {
-  __shared__ float red[4];
+// ---- global gradient-norm clipping (optim/fused.py max_grad_norm) -------------------------
+// Three small kernels produce clip[0] = total_norm, clip[1] = coef on the device; the update
+// kernels above fold clip[1] into their gradient multiply, so clipping costs one extra read of
+// the gradients, no write and no host sync.  No atomics: every sum has a fixed order, so the
+// norm is bitwise reproducible for a fixed chunk table.
+//
+// All sums of squares are carried in fp64 (the square of an fp32 value is exact in fp64; the
+// kernel stays memory-bound, CDNA's fp64 FMA is full rate) and rounded to fp32 once, at the
+// norm.  With fp32 sums the norm depended on where the chunks are cut in its last bit, so a
+// ZeRO-1 run (chunks cut at shard boundaries) and a replicated run got clip coefficients one
+// ulp apart - which bf16 compute amplifies to visibly different parameters within a few
+// steps.  fp64 sums of two different cuts agree to ~1e-15, so the fp32 norm is the same
+// unless the exact value lies that close to an fp32 rounding boundary.
+//
+// partial[ci] = sum of squares of chunk ci.  One chunk per block iteration; the value depends
+// only on the chunk's (start, len) and the data (the block is always 256 lanes), not on the
+// grid.  16-B loads when `start` is 4-aligned (always, except chunks cut at an odd offset),
+// four independent loads in flight per lane, each into its own accumulator.
+__device__ __forceinline__ double sqd(float x) { return (double)x * (double)x; }
+__device__ __forceinline__ double sq4(const f32x4 x) { return (sqd(x[0]) + sqd(x[1])) + (sqd(x[2]) + sqd(x[3])); }
+
+// block_sum (common.h) for fp64: a fixed-order butterfly inside each wave, then the waves' sums
+// in wave order.  `red` must hold NT/64 doubles.
+template <int NT>
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  if (l == 0) red[w] = v;
+  __syncthreads();
+  double r = 0.0;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) r += red[i];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(256) void gradnorm_partial_kernel(const Chunk* __restrict__ chunks, int nchunks,
+                                                              const float* __restrict__ g,
+                                                              double* __restrict__ partial) {
+  __shared__ double red[4];
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const Chunk c = chunks[ci];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < c.len; i += 256) {
-      const float x = g[c.start + i];
-      s += x * x;
+    const float* gc = g + c.start;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if ((c.start & 3) == 0) {
+      const f32x4* gv = (const f32x4*)gc;
+      const int nv = c.len >> 2;
+      int j = threadIdx.x;
+      for (; j + 768 < nv; j += 1024) {
+        const f32x4 x0 = gv[j], x1 = gv[j + 256], x2 = gv[j + 512], x3 = gv[j + 768];
+        a0 += sq4(x0);
+        a1 += sq4(x1);
+        a2 += sq4(x2);
+        a3 += sq4(x3);
+      }
+      for (; j < nv; j += 256) a0 += sq4(gv[j]);
+      // scalar tail: the last len % 4 elements
+      const int i = (nv << 2) + threadIdx.x;
+      if (i < c.len) a1 += sqd(gc[i]);
+    } else {
+      int i = threadIdx.x;
+      for (; i + 768 < c.len; i += 1024) {
+        const float x0 = gc[i], x1 = gc[i + 256], x2 = gc[i + 512], x3 = gc[i + 768];
+        a0 += sqd(x0);
+        a1 += sqd(x1);
+        a2 += sqd(x2);
+        a3 += sqd(x3);
+      }
+      for (; i < c.len; i += 256) a0 += sqd(gc[i]);
     }
-    s = block_sum<256>(s, red);
+    const double s = block_sum_f64<256>((a0 + a1) + (a2 + a3), red);
     if (threadIdx.x == 0) partial[ci] = s;
   }
+}
+
+// out[0] = total_norm = grad_scale * sqrt(sum), out[1] = coef = min(1, max_norm / (total_norm + 1e-6))
+// (torch.nn.utils.clip_grad_norm_; a NaN norm gives a NaN coefficient, as torch's clamp does)
+__device__ __forceinline__ void write_clip(double sum, float grad_scale, float max_norm, float* out) {
+  const float total = grad_scale * (float)sqrt(sum);
+  const float c = max_norm / (total + 1e-6f);
+  out[0] = total;
+  out[1] = c < 1.f ? c : (c != c ? c : 1.f);
+}
+
+// One block: lane t sums partial[t], partial[t + 1024], ... serially, then a fixed-order block
+// reduction.  local != nullptr (ZeRO-1): only the local sum is written - the ranks' sums are
+// all-gathered and combined by gradnorm_combine_kernel.
+__global__ __launch_bounds__(1024) void gradnorm_finalize_kernel(const double* __restrict__ partial, int n,
+                                                                float grad_scale, float max_norm,
+                                                                float* __restrict__ out, double* __restrict__ local) {
+  __shared__ double red[16];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 1024) s += partial[i];
+  s = block_sum_f64<1024>(s, red);
+  if (threadIdx.x == 0) {
+    if (local != nullptr)
+      local[0] = s;
+    else
+      write_clip(s, grad_scale, max_norm, out);
+  }
+}
+
+// ZeRO-1: the ranks' local sums (all-gathered: every rank holds the same `world` doubles) are
+// added in rank order, so every rank computes the same bits.
+__global__ void gradnorm_combine_kernel(const double* __restrict__ sums, int world, float grad_scale, float max_norm,
+                                        float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double s = 0.0;
+  for (int r = 0; r < world; ++r) s += sums[r];
+  write_clip(s, grad_scale, max_norm, out);
 }
 
 }  // namespace rtdc
@@ -228,20 +331,22 @@ static inline int grid_for(int nchunks) { return nchunks < 4096 ? nchunks : 4096
 
 extern "C" int rtdc_adamw(const void* chunks, int nchunks, float* p, const float* g, float* m,
                           float* v, void* shadow, float lr, float b1, float b2, float eps, float wd,
-                          float bc1, float bc2_sqrt, float grad_scale, const int* skip, hipStream_t st) {
+                          float bc1, float bc2_sqrt, float grad_scale, const int* skip, const float* clip,
+                          hipStream_t st) {
   if (nchunks <= 0) return 0;
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
-                     nchunks, p, g, m, v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, skip);
+                     nchunks, p, g, m, v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, skip, clip);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 extern "C" int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* g, float* buf,
                         void* shadow, float lr, float momentum, float dampening, float wd,
-                        int nesterov, int first, float grad_scale, const int* skip, hipStream_t st) {
+                        int nesterov, int first, float grad_scale, const int* skip, const float* clip,
+                        hipStream_t st) {
   if (nchunks <= 0) return 0;
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
                      nchunks, p, g, buf, (bf16_t*)shadow, lr, momentum, dampening, wd, nesterov, first,
-                     grad_scale, skip);
+                     grad_scale, skip, clip);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -338,10 +443,27 @@ extern "C" int rtdc_bf16_transpose_multi(const void* const* src, void* const* ds
 
 extern "C" int rtdc_bf16_transpose_jobs_bytes() { return (int)sizeof(TJobs); }
 
-extern "C" int rtdc_sumsq(const void* chunks, int nchunks, const float* g, float* partial, hipStream_t st) {
+// memory-bound read pass: at most 256 CUs x 8 blocks, the rest by the grid-stride loop
+static inline int grid_for_read(int nchunks) { return nchunks < 2048 ? nchunks : 2048; }
+
+extern "C" int rtdc_gradnorm_partial(const void* chunks, int nchunks, const float* g, double* partial,
+                                     hipStream_t st) {
   if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
+  hipLaunchKernelGGL(gradnorm_partial_kernel, dim3(grid_for_read(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
                      nchunks, g, partial);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_gradnorm_finalize(const double* partial, int n, float grad_scale, float max_norm, float* out,
+                                      double* local, hipStream_t st) {
+  hipLaunchKernelGGL(gradnorm_finalize_kernel, dim3(1), dim3(1024), 0, st, partial, n, grad_scale, max_norm, out,
+                     local);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_gradnorm_combine(const double* sums, int world, float grad_scale, float max_norm, float* out,
+                                     hipStream_t st) {
+  hipLaunchKernelGGL(gradnorm_combine_kernel, dim3(1), dim3(64), 0, st, sums, world, grad_scale, max_norm, out);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

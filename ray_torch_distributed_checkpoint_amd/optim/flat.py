@@ -293,6 +293,15 @@ class FlatParamSpace:
             for st in range(a, b, CHUNK):
                 yield st, min(CHUNK, b - st) | (int(bool(d)) << 32), so + (st - a)
 
+    def max_chunks(self) -> int:
+        """Upper bound of the rows of all chunk tables of one step (what a per-chunk workspace
+        holds): every segment's chunks, plus one more per ZeRO shard boundary and some slack for
+        the cuts of `chunk_table_splits` (each boundary or split cuts at most one chunk)."""
+        n = sum((s.numel + CHUNK - 1) // CHUNK for s in self.segments)
+        if self.zero is not None:
+            n += 2 * len(self.zero.owned)
+        return n + 64
+
     def owned_ranges(self, s: Segment) -> list:
         """[(flat start, flat end, state start)] of segment s this rank owns (all of it without
         ZeRO).  The fused optimizers' per-parameter state is these slices of the state buffers."""

@@ -13,6 +13,23 @@ optimizer launch); the per-parameter `step` tensors are materialised only by
 `state_dict()` and parsed back by `load_state_dict()`, so checkpoints stay torch-compatible.
 Like torch.optim, parameters without a gradient this step are skipped entirely (no weight
 decay, no momentum), and the chunk table is built only from parameters that have one.
+
+Global gradient-norm clipping (`max_grad_norm`, off by default) is fused into the step: a
+read-only pass over the same chunk tables writes one sum of squares per chunk, a single-block
+kernel turns them into `{total_norm, coef}` on the device, and the update kernels fold `coef`
+into the gradient multiply they already do - one extra read of the gradients, no write, no
+host sync, no atomics.  The norm is over every parameter of every param group that has a
+gradient this step (`clip_grad_norm_(model.parameters())`); under ZeRO-1 each rank sums its
+owned shards and the ranks' sums are all-gathered and added in rank order, so every rank gets
+the same bits.  Determinism: for a fixed configuration (world size, ZeRO stage, bucket plan,
+tail split) the chunk tables and every summation order are fixed, so the norm is bitwise
+reproducible from run to run and across a restart.  Across configurations the chunk cuts
+differ, and only agreement to fp32 rounding is promised.  The GPU kernels carry the sums of
+squares in fp64 and round once, at the norm, so in practice two cuts of the same gradient give
+the same fp32 norm (their fp64 sums agree to ~1e-15; the norms differ only if the exact value
+lies that close to an fp32 rounding boundary) - with fp32 sums a ZeRO-1 and a replicated run
+got coefficients one ulp apart, which bf16 compute amplifies to visibly different parameters
+within a few steps.  The CPU reference paths sum in fp32.
 """
 from __future__ import annotations
 
@@ -28,8 +45,18 @@ from .flat import FlatParamSpace, space_of
 class _FlatOptimizer(torch.optim.Optimizer):
     _state_keys: tuple = ()
 
-    def __init__(self, params, defaults):
+    def __init__(self, params, defaults, max_grad_norm=None):
         super().__init__(params, defaults)
+        # clip the global gradient norm to this value inside the step (None / 0: off).  An
+        # attribute, not a param-group option: state_dict() and checkpoints do not change.
+        # Unlike torch.nn.utils.clip_grad_norm_, `p.grad` is left UNSCALED - the coefficient is
+        # applied inside the update.
+        self.max_grad_norm = max_grad_norm
+        # pre-clip global norm of the last clipped step: a 0-dim fp32 tensor on the parameters'
+        # device (a view of the clip workspace: reading it is the caller's sync, the step has
+        # none); None before the first clipped step
+        self.grad_norm = None
+        self._clip_ws = None
         self._space: FlatParamSpace | None = None
         self._bufs: dict[str, torch.Tensor] = {}
         self._steps: dict = {}  # param -> number of optimizer steps taken (host int)
@@ -286,6 +313,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         have = sp.ensure_grad_views()
         self._have = None if len(have) == len(sp.params) else set(have)
         ov = self._overlap
+        clip = self._clip_on()
+        if clip and ov is not None:
+            raise ValueError("max_grad_norm with BackwardOverlap: the updates that ran during backward cannot be "
+                             "clipped (the global norm is known only after the whole backward)")
         done = ov.updated if ov is not None else ()
         native = self._use_native()
         launches = []
@@ -293,7 +324,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
             ps = [p for p in self._with_grad(group) if p not in done]
             if ps:
                 launches += self._native_launches(group, ps) if native else self._cpu_launches(group, ps)
-        self._launch_split(sp, launches)
+        if clip:
+            self._launch_clipped(sp, launches, native)
+        else:
+            self._launch_split(sp, launches)
         if ov is not None:
             ov.end_step()  # the compute stream waits for the updates that ran during backward
         sp.after_step()  # ZeRO-1: gather the updated shards
@@ -310,7 +344,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _launch_split(self, sp, launches) -> None:
         """launches: [(params, decay_flags, fn(chunks, n))].  With a pending last-bucket
         all-reduce (DDP defer_tail_to_optimizer), update everything below its slice first,
-        stream-wait for the collective, then the slice itself."""
+        stream-wait for the collective, then the slice itself.
+
+        Gradient clipping (`_launch_clipped`) gives up this tail/update overlap: every update
+        needs the clip coefficient, which needs the whole gradient, so only the norm pass of the
+        early part overlaps the tail's transfer."""
         tail = sp.pending_tail
         if tail is None:
             for ps, flags, fn in launches:
@@ -327,6 +365,115 @@ class _FlatOptimizer(torch.optim.Optimizer):
             for tables, fn in parts:
                 if tables[i + 1][1]:
                     fn(*tables[i + 1])
+
+    # -- global gradient-norm clipping ---------------------------------------------------------
+    def _clip_on(self) -> bool:
+        m = self.max_grad_norm
+        return m is not None and m > 0
+
+    def _clip_buffers(self, device, need: int = 0, floor: int = 0, world: int = 1) -> dict:
+        """The clip workspace, allocated once (never inside a launch, so a step stays
+        capturable): `out` = {total_norm, coef}, `local` = this rank's sum of squares (ZeRO-1;
+        the CPU paths' accumulator), `gather` = every rank's sum, `partial` = one sum per chunk
+        (`floor`: the largest chunk count of the space; `need`: this step's).  `out` is fp32; the
+        sums are fp64 on the GPU (what the kernels carry them in), fp32 on the CPU paths."""
+        ws = self._clip_ws
+        sums = torch.float64 if torch.device(device).type == "cuda" else torch.float32
+        if ws is None:
+            ws = self._clip_ws = {k: torch.zeros(n, dtype=dt, device=device)
+                                  for k, n, dt in (("out", 2, torch.float32), ("local", 1, sums),
+                                                   ("gather", world, sums), ("partial", 0, sums))}
+        if ws["gather"].numel() != world:
+            ws["gather"] = torch.zeros(world, dtype=sums, device=device)
+        if ws["partial"].numel() < need:
+            ws["partial"] = torch.zeros(max(need, floor), dtype=sums, device=device)
+        if self.grad_norm is None:
+            self.grad_norm = ws["out"][0]
+        return ws
+
+    @staticmethod
+    def _write_clip(out, sumsq, scale: float, max_norm: float) -> float:
+        """torch twin of the finalize kernel: out = {scale * sqrt(sumsq), min(1, max_norm / (norm + 1e-6))}
+        in fp32 (torch.clamp keeps a NaN, like clip_grad_norm_); returns the coefficient."""
+        total = sumsq.reshape(()).sqrt() * scale
+        out[0] = total
+        out[1] = torch.clamp(max_norm / (total + 1e-6), max=1.0)
+        return float(out[1])
+
+    def _launch_clipped(self, sp, launches, native: bool) -> None:
+        """`_launch_split` with clipping: the per-chunk sums of squares of every launch's chunk
+        table (each its own slice of the partials buffer, in launch order), finalize, then the
+        updates with the clip coefficient.  With a pending DDP tail: the sums of everything
+        below the first in-flight piece, then per piece wait + its sums, finalize, all updates."""
+        tail = sp.pending_tail
+        sp.pending_tail = None
+        if tail is None:
+            parts = [((sp.chunk_table(ps, flags),), fn) for ps, flags, fn in launches]
+            waits = []
+        else:
+            starts = [off for off, _ in tail]
+            parts = [(sp.chunk_table_splits(ps, flags, starts), fn) for ps, flags, fn in launches]
+            waits = [wait for _, wait in tail]
+        z = sp.zero
+        ws = self._clip_buffers(sp.device, sum(n for tables, _ in parts for _, n in tables), sp.max_chunks(),
+                                1 if z is None else z.world)
+        ext = gpu_ext() if native else None
+        max_norm = float(self.max_grad_norm)
+        if not native:
+            ws["local"].zero_()
+        total = 0
+        for i in range(len(waits) + 1):
+            if i:
+                waits[i - 1]()
+            for tables, _ in parts:
+                chunks, n = tables[i]
+                if not n:
+                    continue
+                if native:
+                    ext.gradnorm_partial(chunks, n, sp.grad, ws["partial"], total)
+                else:  # CPU reference: per-chunk sum(g * g) in fp32, added in table order
+                    for start, ln, _, _ in self._rows(chunks, n):
+                        g = sp.grad[start:start + ln]
+                        ws["local"] += (g * g).sum()
+                total += n
+        if native:
+            ext.gradnorm_finalize(ws["partial"], total, sp.grad_scale, max_norm, ws["out"],
+                                  None if z is None else ws["local"])
+        if z is not None:
+            import torch.distributed as dist
+
+            # all-gather (not all-reduce) + a rank-order sum: the same bits on every rank
+            dist.all_gather_into_tensor(ws["gather"], ws["local"], group=z.group)
+            if native:
+                ext.gradnorm_combine(ws["gather"], z.world, sp.grad_scale, max_norm, ws["out"])
+        if native:
+            clip = ws["out"].data_ptr()
+        else:
+            s = ws["local"][0]
+            if z is not None:
+                s = ws["gather"][0]
+                for r in range(1, z.world):
+                    s = s + ws["gather"][r]
+            clip = self._write_clip(ws["out"], s, sp.grad_scale, max_norm)
+        for i in range(len(waits) + 1):
+            for tables, fn in parts:
+                chunks, n = tables[i]
+                if n:
+                    fn(chunks, n, clip)
+
+    def _plain_clip(self):
+        """Clip coefficient of the per-tensor CPU step (None: clipping off): the same
+        semantics with torch ops - per-tensor sum(g * g) in fp32, added in parameter order."""
+        if not self._clip_on():
+            return None
+        ps = [p for group in self.param_groups for p in self._with_grad(group)]
+        dev = ps[0].device if ps else self._all_params()[0].device
+        ws = self._clip_buffers(dev)
+        ws["local"].zero_()
+        for p in ps:
+            g = p.grad.float()
+            ws["local"] += (g * g).sum()
+        return self._write_clip(ws["out"], ws["local"][0], 1.0, float(self.max_grad_norm))
 
     def _use_native(self):
         ps = self._all_params()
@@ -350,12 +497,16 @@ class FusedAdamW(_FlatOptimizer):
         self._steps.setdefault(p, 0)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 maximize=False):
+                 maximize=False, max_grad_norm=None):
+        """`max_grad_norm`: clip the global gradient norm inside the step (None / 0: off; settable
+        later as `opt.max_grad_norm`).  `opt.grad_norm` then holds the pre-clip norm of the last
+        step.  `p.grad` is left unscaled - the one visible difference from
+        `torch.nn.utils.clip_grad_norm_`, which rewrites the gradients."""
         if amsgrad or maximize:
             raise NotImplementedError("amsgrad/maximize are not supported by the fused kernel")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
-                                      fused=None))
+                                      fused=None), max_grad_norm)
 
     def _native_launches(self, group, ps) -> list:
         """[(params, decay_flags, fn(chunks, n))] of one param group's native update of `ps`
@@ -367,10 +518,10 @@ class FusedAdamW(_FlatOptimizer):
         wd = group["weight_decay"]
         out = []
         for step, sub in self._count(ps).items():
-            def fn(chunks, n, group=group, b1=b1, b2=b2, wd=wd, step=step):
+            def fn(chunks, n, clip=0, group=group, b1=b1, b2=b2, wd=wd, step=step):
                 ext.adamw(chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"],
                           sp.shadow, group["lr"], b1, b2, group["eps"], wd, 1 - b1 ** step,
-                          math.sqrt(1 - b2 ** step), sp.grad_scale, sp.skip_ptr)
+                          math.sqrt(1 - b2 ** step), sp.grad_scale, sp.skip_ptr, clip)
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out
@@ -386,12 +537,13 @@ class FusedAdamW(_FlatOptimizer):
         m_all, v_all = self._bufs["exp_avg"], self._bufs["exp_avg_sq"]
         out = []
         for step, sub in self._count(ps).items():
-            def fn(chunks, n, step=step):
+            def fn(chunks, n, clip=None, step=step):
+                gs = sp.grad_scale if clip is None else sp.grad_scale * clip
                 for start, ln, decay, so in self._rows(chunks, n):
                     p = sp.data[start:start + ln]
                     g = sp.grad[start:start + ln]
-                    if sp.grad_scale != 1.0:
-                        g = g * sp.grad_scale
+                    if gs != 1.0:
+                        g = g * gs
                     m, v = m_all[so:so + ln], v_all[so:so + ln]
                     if decay:
                         p.mul_(1 - lr * wd)
@@ -431,6 +583,7 @@ class FusedAdamW(_FlatOptimizer):
         sp = space_of(self._all_params())
         if sp is not None:
             sp.wait_pending_tail()
+        coef = self._plain_clip()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             ps = self._with_grad(group)
@@ -440,7 +593,7 @@ class FusedAdamW(_FlatOptimizer):
                     if "exp_avg" not in st:
                         st["exp_avg"] = torch.zeros_like(p)
                         st["exp_avg_sq"] = torch.zeros_like(p)
-                    g = p.grad
+                    g = p.grad if coef is None else p.grad * coef
                     p.mul_(1 - group["lr"] * group["weight_decay"])
                     st["exp_avg"].lerp_(g, 1 - b1)
                     st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
@@ -457,12 +610,14 @@ class FusedSGD(_FlatOptimizer):
             super().init_state()
 
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 maximize=False):
+                 maximize=False, max_grad_norm=None):
+        """`max_grad_norm`: as in `FusedAdamW` (clipping inside the step, `p.grad` left unscaled);
+        a clipped FusedSGD step stays capturable in `utils.graphs.CapturedStep`."""
         if maximize:
             raise NotImplementedError("maximize is not supported by the fused kernel")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, maximize=False, foreach=None, differentiable=False,
-                                      fused=None))
+                                      fused=None), max_grad_norm)
 
     def _native_launches(self, group, ps) -> list:
         sp, ext = self._space, gpu_ext()
@@ -480,10 +635,10 @@ class FusedSGD(_FlatOptimizer):
                 self._bind_state(p)
         out = []
         for sub, first in parts:
-            def fn(chunks, n, group=group, mom=mom, wd=wd, first=first):
+            def fn(chunks, n, clip=0, group=group, mom=mom, wd=wd, first=first):
                 ext.sgd(chunks, n, sp.data, sp.grad, self._bufs["momentum_buffer"] if mom != 0.0 else None,
                         sp.shadow, group["lr"], mom, group["dampening"], wd, group["nesterov"], first,
-                        sp.grad_scale, sp.skip_ptr)
+                        sp.grad_scale, sp.skip_ptr, clip)
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out
@@ -504,12 +659,13 @@ class FusedSGD(_FlatOptimizer):
         buf_all = self._bufs.get("momentum_buffer")
         out = []
         for sub, first in parts:
-            def fn(chunks, n, first=first):
+            def fn(chunks, n, clip=None, first=first):
+                gs = sp.grad_scale if clip is None else sp.grad_scale * clip
                 for start, ln, decay, so in self._rows(chunks, n):
                     p = sp.data[start:start + ln]
                     d = sp.grad[start:start + ln]
-                    if sp.grad_scale != 1.0:
-                        d = d * sp.grad_scale
+                    if gs != 1.0:
+                        d = d * gs
                     if wd != 0 and decay:
                         d = d.add(p, alpha=wd)
                     if mom != 0:
@@ -539,10 +695,11 @@ class FusedSGD(_FlatOptimizer):
         sp = space_of(self._all_params())
         if sp is not None:
             sp.wait_pending_tail()
+        coef = self._plain_clip()
         for group in self.param_groups:
             mom = group["momentum"]
             for p in self._with_grad(group):
-                d = p.grad
+                d = p.grad if coef is None else p.grad * coef
                 if group["weight_decay"] != 0:
                     d = d.add(p, alpha=group["weight_decay"])
                 if mom != 0:

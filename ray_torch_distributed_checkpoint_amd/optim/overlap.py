@@ -22,7 +22,8 @@ sees every update.  Per element the math is exactly `opt.step()`'s - results are
 identical to the non-overlapped step (tests/test_optim_overlap_gpu.py).
 
 Contract (why it is opt-in): one backward per optimizer step and no gradient edits between
-backward and `step()` (clipping, unscaling) - the update has already run by then.  A second
+backward and `step()` (clipping, unscaling) - the update has already run by then; the fused
+optimizers' own `max_grad_norm` is refused here for the same reason (ValueError).  A second
 gradient for an already-updated parameter in the same step raises.  Not with ZeRO-1 (the
 shards are reduce-scattered and gathered around the step).
 """
@@ -37,6 +38,9 @@ class BackwardOverlap:
     def __init__(self, opt, ddp=None, bucket_mb: float = 32.0):
         if not opt._use_native():
             raise ValueError("BackwardOverlap needs the native (GPU) fused optimizer")
+        if opt._clip_on():
+            raise ValueError("BackwardOverlap cannot be combined with max_grad_norm: the updates run during "
+                             "backward, before the global gradient norm is known")
         sp = opt._ensure_space()
         self.opt, self.sp = opt, sp
         self.engine = None

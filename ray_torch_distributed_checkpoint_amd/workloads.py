@@ -67,6 +67,7 @@ class WorkloadConfig:
     checkpoint: object = None             # upstream Checkpoint (--from-run / --from-task)
     async_checkpoint: Optional[bool] = None  # None -> CheckpointConfig.async_checkpoint
     num_classes: int = 10
+    max_grad_norm: Optional[float] = None  # clip the global gradient norm inside the fused step (None / 0: off)
 
     @classmethod
     def from_dict(cls, d: dict) -> "WorkloadConfig":
@@ -193,6 +194,7 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     B = cfg.batch_size_per_worker or B0
     S = cfg.seq_len or S0
     lr = cfg.lr or lr0
+    clip = cfg.max_grad_norm or None
     torch.manual_seed(cfg.seed)
     name = cfg.model
     if name.startswith("resnet18"):
@@ -200,7 +202,7 @@ def build(cfg: WorkloadConfig, device) -> Workload:
 
         # "-tiny" = the full network on 32x32 images (the GEMM tiles need >= 64 channels)
         model = ResNet18(num_classes=cfg.num_classes).to(device)
-        opt = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=5e-5)
+        opt = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=5e-5, max_grad_norm=clip)
         data = SyntheticImages(cfg.dataset_size, S, cfg.num_classes, device, seed=cfg.seed)
         return Workload(model, opt, data, B, S, 0, model.flops_per_sample(S),
                         lambda net, x, y: ops.cross_entropy(net(x), y))
@@ -218,7 +220,7 @@ def build(cfg: WorkloadConfig, device) -> Workload:
         model = GPT2(mc).to(device)
     else:
         raise ValueError(f"unknown workload model {name!r}")
-    opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1)
+    opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=clip)
     data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed)
     return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S, lambda net, x, y: net(x, y))
 
@@ -375,6 +377,8 @@ def train_loop_per_worker(config: dict):
 
     pending = None  # this rank's in-flight async save (at most one: bounded snapshot memory)
     losses = []
+    clipping = bool(cfg.max_grad_norm)
+    norms = []  # per-step pre-clip gradient norms (device scalars, read with the losses)
     t_last, n_last = time.perf_counter(), 0
     for step in range(start, cfg.steps):
         train.report_progress(step)
@@ -387,18 +391,26 @@ def train_loop_per_worker(config: dict):
             opt.step()
             opt.zero_grad(set_to_none=True)
         losses.append(loss.detach())
+        if clipping:
+            norms.append(opt.grad_norm.clone())
         n_last += 1
         done = step + 1
         do_ckpt = bool(every) and (done % every == 0 or done == cfg.steps)
         if not (do_ckpt or done % report_every == 0 or done == cfg.steps):
             continue
-        vals = torch.stack(losses).float().tolist()  # the one host sync per report
+        vals = torch.stack(losses).float()
+        if clipping:
+            vals = torch.cat([vals, torch.stack(norms)])
+        vals = vals.tolist()  # the one host sync per report
+        vals, gnorms = vals[:len(losses)], vals[len(losses):]
         dt = time.perf_counter() - t_last
         metrics = {"step": done, "loss": vals[-1], "losses": vals, "epoch": stream.epoch,
                    "samples_per_s": round(n_last * wl.batch * world / max(dt, 1e-9), 3)}
         if wl.tokens_per_sample:
             metrics["tokens_per_s"] = round(metrics["samples_per_s"] * wl.tokens_per_sample, 1)
-        losses, n_last = [], 0
+        if clipping:
+            metrics["grad_norm"], metrics["grad_norms"] = gnorms[-1], gnorms
+        losses, norms, n_last = [], [], 0
         ck = None
         if do_ckpt:
             with phase("ckpt"):
@@ -437,14 +449,17 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    max_failures: int = 0, seed: int = 1234, grad_comm_dtype: str = "fp32",
                    bucket_cap_mb: float = 32.0, zero_stage: int = -1, progress_timeout_s: float | None = 300.0,
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
-                   report_every_n_steps: int | None = None):
+                   report_every_n_steps: int | None = None, max_grad_norm: float | None = None):
     """`train_fashion_mnist`'s counterpart for the bf16 workloads (R/my_ray_module.py:216-251).
-    zero_stage -1: `default_zero_stage(model, num_workers)`."""
+    zero_stage -1: `default_zero_stage(model, num_workers)`.  max_grad_norm: clip the global
+    gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
+    `grad_norm` / `grad_norms` (pre-clip)."""
     if zero_stage < 0:
         zero_stage = default_zero_stage(model, num_workers)
     cfg = WorkloadConfig(model=model, steps=steps, batch_size_per_worker=batch_size_per_worker, seq_len=seq_len,
                          lr=lr, ckpt_every_n_steps=ckpt_every_n_steps, seed=seed, resume_mode=resume_mode,
-                         checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps)
+                         checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
+                         max_grad_norm=max_grad_norm or None)
     run_config = train.RunConfig(
         name=name, storage_path=checkpoint_storage_path, verbose=verbose,
         checkpoint_config=train.CheckpointConfig(num_to_keep=num_checkpoints_to_keep,
@@ -474,12 +489,14 @@ def main(argv=None):
     ap.add_argument("--grad-comm-dtype", default="fp32")
     ap.add_argument("--zero-stage", type=int, default=-1, choices=[-1, 0, 1],
                     help="-1: ZeRO-1 for llama* at more than one worker, else replicated")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the global gradient norm inside the fused optimizer step (default: off)")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
     use_gpu = torch.cuda.is_available() and not a.cpu
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
-                         zero_stage=a.zero_stage)
+                         zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm)
     print(res)
 
 

@@ -51,6 +51,9 @@ class RayTorchTrain(FlowSpec):
     zero_stage = Parameter("zero_stage", default=-1,
                            help="1: ZeRO-1 sharded optimizer step, 0: replicated; -1 (default): ZeRO-1 for llama* "
                                 "at more than one worker (bf16 workloads)")
+    max_grad_norm = Parameter("max_grad_norm", default=0.0,
+                              help="bf16 workloads: clip the global gradient norm inside the fused optimizer step "
+                                   "(0: off)")
     batch_size_per_worker = Parameter("batch_size_per_worker", default=0,
                                       help="bf16 workloads: samples per worker per step (0: the model's default). "
                                            "--batch_size is the reference MLP's global batch")
@@ -106,7 +109,8 @@ class RayTorchTrain(FlowSpec):
                 checkpoint_storage_path=current.ray_storage_path, checkpoint=args.get("checkpoint"),
                 resume_mode=mode, max_failures=int(self.max_failures), grad_comm_dtype=self.grad_comm_dtype,
                 zero_stage=int(self.zero_stage),
-                report_every_n_steps=int(self.report_every_n_steps) or None)
+                report_every_n_steps=int(self.report_every_n_steps) or None,
+                max_grad_norm=float(self.max_grad_norm) or None)
         self.next(self.join)
 
     @step

@@ -21,7 +21,7 @@
 //             P here instead of accumulating dQ with float atomics keeps the backward
 //             bitwise reproducible (MI355X_MICROARCH.md §Global float atomics).
 //   delta   : D[b,h,t] = sum_d dO * O (the softmax-backward row term), computed by bwd_dq
-//             in its prologue (bwd_dq runs first); delta_kernel is the standalone form.
+//             in its prologue (bwd_dq runs first).
 // Requires T % 64 == 0 and Dh in {64, 128}.
 //
 // Pipelining (all three loops): the streamed tiles (K/V for fwd and dQ; Q, dO and the 64
@@ -35,8 +35,8 @@
 // drain the DMA queue).  The tile of step j+NS-1 is issued at the top of step j into the slot
 // that step j-1 read, which every wave has left: its reads completed (lgkmcnt(0)) before the
 // barrier that closed step j-1.  All LDS is one __shared__ array.
-// NS (ring slots) is chosen at launch (fa_ns below): LDS per block grows with NS and sets how
-// many blocks share a CU, so deeper rings trade occupancy for DMA depth.
+// NS (ring slots) is 2 at every launch (see the note above rtdc_flash_fwd): LDS per block grows
+// with NS and sets how many blocks share a CU, so deeper rings trade occupancy for DMA depth.
 #include "common.h"
 
 #include <cstdlib>
@@ -58,7 +58,6 @@ struct Args {
   float scale;
   int xcd_remap;  // 1: the blocks of one head share an XCD (and its L2); 2: + heavy blocks first
                   // across all the XCD's heads
-  int diag;       // timing-only builds (wrong results): bit 1 skips the loop's DMA waits
   // optional [B*T/16][W] fp32: per 16-row group, the column sums of the bf16 dQ / dK / dV rows
   // the backward kernels store (the qkv projection's bias gradient, reduced later without
   // re-reading dqkv: ops/gemm.py offer_colsum_partials)
@@ -68,9 +67,6 @@ struct Args {
   // part [qs][B*T][Hkv][2*Dh]; dkdv_reduce_kernel sums them in qsub order (deterministic)
   float* part;
   int qs;
-  // delta already in `delta` (delta_kernel ran first): the dQ kernels compute their own copy for
-  // their rows but do not store it - dK/dV may be reading it concurrently (rtdc_flash_bwd `which`)
-  int delta_ready;
 };
 
 // column sums over a wave's 16 rows of its stored fragment values v (lane = row (lane & 15) x
@@ -227,11 +223,9 @@ __device__ __forceinline__ f32x4 mfma(const bf16x8& a, const bf16x8& b, const f3
 }
 
 // ------------------------------------------------------------------------------ forward
-// DBV: output column blocks of 16 whose V fragments are read per batch (registers vs LDS
-// latency per batch)
-template <int DH, int NS, int DBV = 4>
+template <int DH, int NS>
 __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
-  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < DBV ? DT : DBV, TILE = 64 * DH * 2, PER = DH / 16;
+  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -349,146 +343,8 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
         o[d0 + d] = mfma(tr_use(vq[d][1]), p1, o[d0 + d]);
       }
     }
-    if (kb + 1 < nkb && !(a.diag & 1)) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
+    if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
     step_barrier();
-  }
-#undef KT
-#undef VT
-  const float l = lacc[0];
-  const float inv = 1.f / l;
-  bf16_t* orow = a.out + ((long long)b * a.T + myq) * C + h * DH;
-#pragma unroll
-  for (int d = 0; d < DT; ++d) {
-    const uint2 v = make_uint2(pack_bf2(o[d][0] * inv, o[d][1] * inv), pack_bf2(o[d][2] * inv, o[d][3] * inv));
-    *(uint2*)(orow + 16 * d + 4 * g) = v;
-  }
-  if (g == 0) a.lse[(long long)bh * a.T + myq] = m + log2f(l);
-}
-
-// Forward, software-pipelined across key tiles inside each wave: the S = K.Q MFMAs of tile kb+1
-// are issued before the softmax of tile kb, so one wave's matrix work runs under its own
-// exp/max/pack VALU instead of waiting for a co-resident wave to fill the gap (the serial
-// S -> max -> exp -> P.V chain of fwd_kernel).  K therefore streams one tile further ahead than
-// V: a 3-slot K ring and a 2-slot V ring (40 KiB, the same 4 blocks per CU as fwd_kernel's
-// 2+2 slots would allow at this register count).  Step kb issues K(kb+2) and V(kb+1) - into the
-// slots of K(kb-1) (read in step kb-2) and V(kb-1) (read in step kb-1) - and retires both
-// before its closing barrier, so each DMA has one step to land, as in fwd_kernel.  Same math in
-// the same order as fwd_kernel: bitwise equal output.
-template <int DH>
-__global__ __launch_bounds__(256, 2) void fwd3_kernel(Args a) {
-  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2;
-  __shared__ __attribute__((aligned(16))) char smem[5 * TILE];  // K[3], V[2]
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = lane >> 4;
-  const int nqb = a.T / BQ;
-  int bx, bh;
-  grid_pos(a, bx, bh);
-  const int qb = nqb - 1 - bx;
-  const int b = bh / a.H, h = bh % a.H;
-  const int grp = a.H / a.Hkv, kvh = h / grp;
-  const int C = a.H * DH, W = C + 2 * a.Hkv * DH;
-  const bf16_t* base = a.qkv + (long long)b * a.T * W;
-  const int qcol = h * DH, kcol = C + kvh * DH, vcol = C + a.Hkv * DH + kvh * DH;
-  const int q0w = qb * BQ + wave * 16;
-  const int myq = q0w + (lane & 15);
-  const float c = a.scale * LOG2E;
-  uint32_t troff[DH / 16];
-  tr_lane_offsets<DH>(troff, lane);
-  const int nkb = qb + 1;
-
-#define KT(s) (smem + (s) * TILE)
-#define VT(s) (smem + (3 + (s)) * TILE)
-  stage<DH>(base, W, 0, kcol, KT(0), wave, lane);
-  stage<DH>(base, W, 0, vcol, VT(0), wave, lane);
-  if (nkb > 1) stage<DH>(base, W, BKV, kcol, KT(1), wave, lane);
-  bf16x8 qf[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = gload8(base + (long long)myq * W + qcol + ks * 32 + g * 8);
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) settle(qf[ks]);  // (retires the DMA above with it)
-  step_barrier();
-
-  auto scores = [&](const char* kt, f32x4 (&s)[4]) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) s[t] = mfma(frag_rows<DH>(kt, 16 * t, ks, lane), qf[ks], s[t]);
-    }
-  };
-  f32x4 o[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 lacc = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (short)0x3F80;
-  float m = -INFINITY;
-  f32x4 s[4];
-  scores(KT(0), s);
-
-  for (int kb = 0; kb < nkb; ++kb) {
-    if (kb + 2 < nkb) stage<DH>(base, W, (kb + 2) * BKV, kcol, KT((kb + 2) % 3), wave, lane);
-    if (kb + 1 < nkb) stage<DH>(base, W, (kb + 1) * BKV, vcol, VT((kb + 1) & 1), wave, lane);
-    // next tile's scores first: independent of this tile's softmax
-    f32x4 sn[4];
-    if (kb + 1 < nkb) scores(KT((kb + 1) % 3), sn);
-    const uint32_t vbase = lds_addr(VT(kb & 1));
-    float mx = -INFINITY;
-    const bool diag = (kb == qb);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = s[t][r];
-        if (diag) {
-          const int key = kb * BKV + 16 * t + 4 * g + r;
-          if (key > myq) v = -INFINITY;
-        }
-        s[t][r] = v;
-        mx = fmaxf(mx, v);
-      }
-    mx = max_rows4(mx);
-    if (__any(mx * c > m + 8.f)) {
-      const float mn = fmaxf(m, mx * c);
-      const float alpha = fexp2(m - mn);
-      m = mn;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lacc[r] *= alpha;
-#pragma unroll
-      for (int d = 0; d < DT; ++d)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[d][r] *= alpha;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s[t][r] = fexp2(fmaf(s[t][r], c, -m));
-    const bf16x8 p0 = pack_pair(s[0], s[1]), p1 = pack_pair(s[2], s[3]);
-    lacc = mfma(ones, p0, lacc);
-    lacc = mfma(ones, p1, lacc);
-#pragma unroll
-    for (int d0 = 0; d0 < DT; d0 += DB) {
-      TrPair vq[DB][2];
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        const uint32_t la = vbase + troff[d0 + d];
-        vq[d][0] = frag_cols_at<DH, 0>(la);
-        vq[d][1] = frag_cols_at<DH, 32>(la);
-      }
-      lgkm_wait0();
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        o[d0 + d] = mfma(tr_use(vq[d][0]), p0, o[d0 + d]);
-        o[d0 + d] = mfma(tr_use(vq[d][1]), p1, o[d0 + d]);
-      }
-    }
-    // step kb+1 reads K(kb+2) and V(kb+1), both issued at the top of this step
-    if (kb + 1 < nkb && !(a.diag & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    step_barrier();
-#pragma unroll
-    for (int t = 0; t < 4; ++t) s[t] = sn[t];
   }
 #undef KT
 #undef VT
@@ -649,7 +505,7 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
         }
       }
     }
-    if (kb + 1 < nkb && !(a.diag & 1)) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
+    if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
     step_barrier();
   }
 #undef KT
@@ -666,38 +522,6 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
       *(uint2*)(orow + 16 * d + 4 * g) = v;
     }
     if (g == 0) a.lse[(long long)bh * a.T + myq[qg]] = m[qg] + log2f(lt);
-  }
-}
-
-// ------------------------------------------------------------------------------ delta
-// delta[b][h][t] = sum_d O * dO over one head row; G = DH/8 lanes per row (16-B loads,
-// consecutive lanes read consecutive 16 B), reduced with xor shuffles inside the lane group.
-template <int DH>
-__global__ __launch_bounds__(256) void delta_kernel(const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
-                                                   float* __restrict__ delta, int B, int T, int H) {
-  constexpr int G = DH / 8;
-  const long long gid = blockIdx.x * 256LL + threadIdx.x;
-  const long long idx = gid / G;  // (b, t, h) row
-  const int part = (int)(gid % G);
-  float s = 0.f;
-  if (idx < (long long)B * T * H) {
-    const bf16_t* o = out + idx * DH + part * 8;
-    const bf16_t* d = dout + idx * DH + part * 8;
-    const uint4 x = *(const uint4*)o, y = *(const uint4*)d;
-    const uint32_t xa[4] = {x.x, x.y, x.z, x.w}, ya[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      s += __uint_as_float(xa[i] << 16) * __uint_as_float(ya[i] << 16);
-      s += __uint_as_float(xa[i] & 0xffff0000u) * __uint_as_float(ya[i] & 0xffff0000u);
-    }
-  }
-#pragma unroll
-  for (int off = 1; off < G; off <<= 1) s += __shfl_xor(s, off, 64);
-  if (part == 0 && idx < (long long)B * T * H) {
-    const int h = (int)(idx % H);
-    const long long bt = idx / H;
-    const int t = (int)(bt % T), b = (int)(bt / T);
-    delta[((long long)b * H + h) * T + t] = s;
   }
 }
 
@@ -825,7 +649,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
         dk[e0 + d] = mfma(tr_use(fq[d][1]), d1, dk[e0 + d]);
       }
     }
-    if (it + 1 < total && !(a.diag & 1)) wait_vm_upto(PER * (min(it + NS - 1, total - 1) - it - 1));
+    if (it + 1 < total) wait_vm_upto(PER * (min(it + NS - 1, total - 1) - it - 1));
     step_barrier();
   }
   if (qs > 1) {  // fp32 partial of this q-head subset; dkdv_reduce_kernel finishes the rows
@@ -1013,7 +837,7 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
         }
       }
     }
-    if (it + 1 < total && !(a.diag & 1)) wait_vm_upto(PER * (min(it + NS - 1, total - 1) - it - 1));
+    if (it + 1 < total) wait_vm_upto(PER * (min(it + NS - 1, total - 1) - it - 1));
     step_barrier();
   }
 #pragma unroll
@@ -1135,7 +959,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
     for (int e = 0; e < 8; ++e)
       dsum = fmaf(bf2f((bf16_t)of[ks][e]), bf2f((bf16_t)ofw[ks][e]), dsum);
   const float del = sum_rows4(dsum);
-  if (g == 0 && !a.delta_ready) a.delta[r] = del;
+  if (g == 0) a.delta[r] = del;
   step_barrier();
 
   f32x4 dq[DT];
@@ -1192,7 +1016,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
         dq[e0 + d] = mfma(tr_use(fk[d][1]), d1, dq[e0 + d]);
       }
     }
-    if (kb + 1 < nkb && !(a.diag & 1)) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
+    if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
     step_barrier();
   }
 #undef KT
@@ -1276,7 +1100,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) dsum = fmaf(bf2f((bf16_t)of[qg][ks][e]), bf2f((bf16_t)ofw[qg][ks][e]), dsum);
     del[qg] = sum_rows4(dsum);
-    if (g == 0 && !a.delta_ready) a.delta[(long long)bh * a.T + myq[qg]] = del[qg];
+    if (g == 0) a.delta[(long long)bh * a.T + myq[qg]] = del[qg];
   }
   step_barrier();
 
@@ -1358,7 +1182,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
         }
       }
     }
-    if (kb + 1 < nkb && !(a.diag & 1)) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
+    if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
     step_barrier();
   }
 #undef KT
@@ -1380,16 +1204,6 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
 
 using namespace rtdc;
 
-// ring depth: RTDC_FA_NS = 2 | 3 | 4 at Dh = 64.  Measured on GPT-2 shapes (B16 T1024 H12,
-// benchmarks/attn_bench.py): NS 2 / 3 / 4 = fwd 108 / 113 / 135 us, bwd 285 / 335 / 357 us -
-// every extra slot costs a co-resident block per CU (32 / 48 / 64 KiB of LDS per block), and
-// at these 8-16-step loops occupancy hides more HBM latency than a deeper ring.  Dh = 128
-// stays at 2 (a third slot leaves one block per CU).
-static int fa_diag() {
-  static const int v = getenv("RTDC_FA_DIAG") ? atoi(getenv("RTDC_FA_DIAG")) : 0;
-  return v;
-}
-
 static int fa_xcd() {
   // 2 (default): one head's blocks share an XCD and each XCD runs the long blocks of all its
   // heads first (GPT-2 fwd 84 -> 48 us vs the plain grid order 0); 1: XCD grouping only
@@ -1397,70 +1211,41 @@ static int fa_xcd() {
   return v;
 }
 
-static int fa_ns(int Dh) {
-  static const int forced = getenv("RTDC_FA_NS") ? atoi(getenv("RTDC_FA_NS")) : 0;
-  if (Dh == 128) return 2;
-  return forced >= 2 && forced <= 4 ? forced : 2;
-}
-
-#define FA_DISPATCH(KERNEL, DH, NSV, GRID, ARGS)                                                        \
-  do {                                                                                                   \
-    if ((NSV) == 4) hipLaunchKernelGGL((KERNEL<DH, (DH == 64 ? 4 : 2)>), GRID, dim3(256), 0, st, ARGS); \
-    else if ((NSV) == 3) hipLaunchKernelGGL((KERNEL<DH, (DH == 64 ? 3 : 2)>), GRID, dim3(256), 0, st, ARGS); \
-    else hipLaunchKernelGGL((KERNEL<DH, 2>), GRID, dim3(256), 0, st, ARGS);                              \
-  } while (0)
+// Ring depth: every kernel is launched with NS = 2.  Measured at Dh = 64 on GPT-2 shapes (B16
+// T1024 H12, benchmarks/attn_bench.py): NS 2 / 3 / 4 = fwd 108 / 113 / 135 us, bwd 285 / 335 /
+// 357 us - every extra slot costs a co-resident block per CU (32 / 48 / 64 KiB of LDS per
+// block), and at these 8-16-step loops occupancy hides more HBM latency than a deeper ring.
+// At Dh = 128 a third slot leaves one block per CU.
+#define FA_LAUNCH(KERNEL, DH, GRID, ARGS) hipLaunchKernelGGL((KERNEL<DH, 2>), GRID, dim3(256), 0, st, ARGS)
 
 extern "C" int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh,
                               float scale, hipStream_t st) {
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
   fa::Args a{};
   a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)out; a.lse = lse;
-  a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd(); a.diag = fa_diag();
+  a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
   // measured (benchmarks/attn_bench.py, before the DMA ring): 32 rows/wave wins at Dh = 128
   // (Llama: 101 vs 108 us), 16 rows/wave at Dh = 64 (GPT-2: 100 vs 109 us); RTDC_FA_FWD=1|2
   // forces one
   const char* fwd_env = getenv("RTDC_FA_FWD");  // (read per call: tests A/B it in one process)
   const int forced = fwd_env ? atoi(fwd_env) : 0;
   const int variant = forced ? forced : (Dh == 128 ? 2 : 1);
-  const int ns = fa_ns(Dh);
-  if (variant == 3 && Dh == 64) {  // software-pipelined 16 rows per wave
-    dim3 grid(T / 64, B * H);
-    hipLaunchKernelGGL((fa::fwd3_kernel<64>), grid, dim3(256), 0, st, a);
-  } else if (variant == 2 && T % 128 == 0) {  // 32 rows per wave
+  if (variant == 2 && T % 128 == 0) {  // 32 rows per wave
     dim3 grid(T / 128, B * H);
-    if (Dh == 64) FA_DISPATCH(fa::fwd2_kernel, 64, ns, grid, a);
-    else FA_DISPATCH(fa::fwd2_kernel, 128, ns, grid, a);
+    if (Dh == 64) FA_LAUNCH(fa::fwd2_kernel, 64, grid, a);
+    else FA_LAUNCH(fa::fwd2_kernel, 128, grid, a);
   } else {
     dim3 grid(T / 64, B * H);
-    static const int db = getenv("RTDC_FA_DB") ? atoi(getenv("RTDC_FA_DB")) : 4;
-    if (Dh == 64 && ns == 2 && db == 2) hipLaunchKernelGGL((fa::fwd_kernel<64, 2, 2>), grid, dim3(256), 0, st, a);
-    else if (Dh == 64) FA_DISPATCH(fa::fwd_kernel, 64, ns, grid, a);
-    else FA_DISPATCH(fa::fwd_kernel, 128, ns, grid, a);
+    if (Dh == 64) FA_LAUNCH(fa::fwd_kernel, 64, grid, a);
+    else FA_LAUNCH(fa::fwd_kernel, 128, grid, a);
   }
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// delta[b][h][t] = rowsum(dO * O) alone (before dQ and dK/dV run concurrently on two streams)
-extern "C" int rtdc_flash_delta(const void* out, const void* dout, float* delta, int B, int T, int H, int Dh,
-                                hipStream_t st) {
-  if (Dh != 64 && Dh != 128) return 1;
-  const long long threads = (long long)B * T * H * (Dh / 8);
-  dim3 grid((unsigned)((threads + 255) / 256));
-  if (Dh == 64)
-    hipLaunchKernelGGL(fa::delta_kernel<64>, grid, dim3(256), 0, st, (const bf16_t*)out, (const bf16_t*)dout, delta, B,
-                       T, H);
-  else
-    hipLaunchKernelGGL(fa::delta_kernel<128>, grid, dim3(256), 0, st, (const bf16_t*)out, (const bf16_t*)dout, delta,
-                       B, T, H);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-// which: bit 0 the dQ pass (it also stores delta unless delta_ready), bit 1 the dK/dV pass (+ the
-// GQA head-split reduction).  Both bits: dQ then dK/dV on `st`.  One bit with delta_ready lets the
-// caller run the two passes on two streams (ops/attention.py).
+// dQ (it also stores delta), then dK/dV (+ the GQA head-split reduction), all on `st`
 extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                               void* dqkv, int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws,
-                              float* part, int qs, int which, int delta_ready, hipStream_t st) {
+                              float* part, int qs, hipStream_t st) {
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
   if (qs < 1 || (H / Hkv) % qs != 0 || (qs > 1 && part == nullptr) || ((Hkv * 2 * Dh) % 4) != 0) return 1;
   // dQ first: it also computes the row terms delta = rowsum(dO * O) that dK/dV read
@@ -1469,12 +1254,9 @@ extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout
   a.delta = delta;
   a.dqkv = (bf16_t*)dqkv;
   a.cs_ws = cs_ws;
-  a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd(); a.diag = fa_diag();
-  a.part = part; a.qs = qs; a.delta_ready = delta_ready;
-  if (which < 1 || which > 3 || (which != 3 && !delta_ready)) return 1;
-  const bool run_dq = which & 1, run_dkdv = which & 2;
+  a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
+  a.part = part; a.qs = qs;
   dim3 g1(T / 64, B * Hkv * qs), g2(T / 64, B * H);
-  const int ns = fa_ns(Dh);
   // dK/dV at Dh = 64: 32 keys per wave (bwd_dkdv2_kernel) unless RTDC_FA_DKDV=1 (16 keys per wave)
   const char* dkdv_env = getenv("RTDC_FA_DKDV");  // (read per call: tests A/B it in one process)
   const int dkdv_v = dkdv_env ? atoi(dkdv_env) : 2;
@@ -1484,33 +1266,25 @@ extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout
   const bool dq2 = (dq_env ? atoi(dq_env) : 2) == 2 && T % 128 == 0;
   const dim3 g2b(T / 128, B * H);
   if (Dh == 64) {
-    if (run_dq) {
-      if (dq2) FA_DISPATCH(fa::bwd_dq2_kernel, 64, ns, g2b, a);
-      else FA_DISPATCH(fa::bwd_dq_kernel, 64, ns, g2, a);
-    }
-    if (run_dkdv) {
-      if (dkdv_v == 2 && T % 128 == 0) {
-        dim3 g3(T / 128, B * Hkv * qs);
-        FA_DISPATCH(fa::bwd_dkdv2_kernel, 64, ns, g3, a);
-      } else {
-        FA_DISPATCH(fa::bwd_dkdv_kernel, 64, ns, g1, a);
-      }
+    if (dq2) FA_LAUNCH(fa::bwd_dq2_kernel, 64, g2b, a);
+    else FA_LAUNCH(fa::bwd_dq_kernel, 64, g2, a);
+    if (dkdv_v == 2 && T % 128 == 0) {
+      dim3 g3(T / 128, B * Hkv * qs);
+      FA_LAUNCH(fa::bwd_dkdv2_kernel, 64, g3, a);
+    } else {
+      FA_LAUNCH(fa::bwd_dkdv_kernel, 64, g1, a);
     }
   } else {
-    if (run_dq) {
-      if (dq2) FA_DISPATCH(fa::bwd_dq2_kernel, 128, ns, g2b, a);
-      else FA_DISPATCH(fa::bwd_dq_kernel, 128, ns, g2, a);
-    }
-    if (run_dkdv) {
-      if (dkdv_env && dkdv_v == 2 && T % 128 == 0) {  // opt-in at Dh = 128 (occupancy 1)
-        dim3 g3(T / 128, B * Hkv * qs);
-        FA_DISPATCH(fa::bwd_dkdv2_kernel, 128, ns, g3, a);
-      } else {
-        FA_DISPATCH(fa::bwd_dkdv_kernel, 128, ns, g1, a);
-      }
+    if (dq2) FA_LAUNCH(fa::bwd_dq2_kernel, 128, g2b, a);
+    else FA_LAUNCH(fa::bwd_dq_kernel, 128, g2, a);
+    if (dkdv_env && dkdv_v == 2 && T % 128 == 0) {  // opt-in at Dh = 128 (occupancy 1)
+      dim3 g3(T / 128, B * Hkv * qs);
+      FA_LAUNCH(fa::bwd_dkdv2_kernel, 128, g3, a);
+    } else {
+      FA_LAUNCH(fa::bwd_dkdv_kernel, 128, g1, a);
     }
   }
-  if (qs > 1 && run_dkdv) {
+  if (qs > 1) {
     const int KV = Hkv * 2 * Dh;
     dim3 gr((unsigned)((long long)B * T / 16), (unsigned)((KV / 4 + 255) / 256));
     if (Dh == 64) hipLaunchKernelGGL(fa::dkdv_reduce_kernel<64>, gr, dim3(256), 0, st, a);

@@ -110,11 +110,9 @@ __device__ __forceinline__ typename Frag<KMAJOR>::T load_frag96(const char* tile
 // behind stores waits for them too (vmcnt counts both), which would serialise the store
 // stream behind each load.  One specialisation per
 // activation keeps the per-element code branch-free.
-// residual / activation-input pairs loaded ahead of their use in the bf16 epilogue (A/B builds:
-// -DRTDC_EPI_W=N)
-#ifndef RTDC_EPI_W
-#define RTDC_EPI_W 2
-#endif
+// residual / activation-input pairs loaded ahead of their use in the bf16 epilogue (distance 4
+// measured no better: profiles/r6/gemm_epi_w4_and_gelu_save_grad_ab_r6.txt)
+constexpr int EPI_W = 2;
 
 // s_waitcnt vmcnt(0) lgkmcnt(0) as the builtin, which the compiler's wait insertion reads (asm
 // waits it cannot).  hipcc treats a global_load_lds (a FLAT instruction, counted in vmcnt AND
@@ -150,7 +148,7 @@ __device__ __forceinline__ void tile_epilogue_bf16(const GemmArgs& a, f32x4 (&ac
   // fragment pairs in order P = (qa * TMQ + i) * TNQ + c: consecutive stores complete a row's
   // run of SB columns (a column-run-outer order left each 128-B line half written for half
   // the epilogue; with outputs that miss the caches, c_fc forward took 159 instead of 124 us)
-  constexpr int NP = 2 * TMQ * TNQ, W = RTDC_EPI_W < NP ? RTDC_EPI_W : NP;
+  constexpr int NP = 2 * TMQ * TNQ, W = EPI_W < NP ? EPI_W : NP;
   // (the lane part of the offset is one register; the per-pair parts are wave-uniform, so
   // nothing per pair is loop-invariant across the persistent kernel's tiles)
   const int lbase = rrow * a.ldc + nrun, rows_left = a.M - m0;
@@ -300,12 +298,6 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& a, f32x4 (&acc)[2]
   }
 }
 
-// Timing-only builds (results are wrong; never shipped): bit 1 drops the main loop's vmcnt
-// waits, bit 2 reads LDS fragments in the first K-tile only, bit 4 drops the loop barriers.
-#ifndef RTDC_G8_DIAG
-#define RTDC_G8_DIAG 0
-#endif
-
 // outstanding glds instructions allowed (wave-uniform): counted waits are immediates
 __device__ __forceinline__ void wait_vm(int allowed) {
   if (allowed >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -418,15 +410,14 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& a, const int bid, con
       // after the lgkmcnt wait below)
       typename Frag<AK>::T ra[TMQ][2];
       typename Frag<BKM>::T rb[TNQ][2];
-      const bool rd = !(RTDC_G8_DIAG & 2) || t == 0;
-      if ((p == 1 || p == 3) && rd) {
+      if (p == 1 || p == 3) {
         const char* ah = buf + (p == 1 ? 0 : HALF);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int i = 0; i < TMQ; ++i) ra[i][ks] = load_fragx<AK, 128>(ah, SA * wa + 16 * i, ks, lane);
       }
-      if ((p == 1 || p == 2) && rd) {
+      if (p == 1 || p == 2) {
         const char* bh = buf + 2 * HALF + (p == 1 ? 0 : BHALF);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -440,20 +431,20 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& a, const int bid, con
       const int e = p < 4 ? 4 * t + 4 + p : 4 * t + 8;
       issue(e);
       // 3. retire what the next phase reads (p3 -> p4 reads nothing new)
-      if (p != 3 && (p != 4 || t + 1 < nt) && !(RTDC_G8_DIAG & 1)) {
+      if (p != 3 && (p != 4 || t + 1 < nt)) {
         const int need = p == 1 ? 4 * t + 2 : (p == 2 ? 4 * t + 3 : 4 * t + 5);
         wait_vm(ev_loads<CB>(need + 1, min(e, total_ev - 1)));
       }
       asm volatile("" ::: "memory");
-      if (!(RTDC_G8_DIAG & 4)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if ((p == 1 || p == 3) && rd) {
+      if (p == 1 || p == 3) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int i = 0; i < TMQ; ++i) fa[i][ks] = fval(ra[i][ks]);
       }
-      if ((p == 1 || p == 2) && rd) {
+      if (p == 1 || p == 2) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -480,7 +471,6 @@ __device__ __forceinline__ void gemm8_body(const GemmArgs& a, const int bid, con
     }
   }
 
-  if (RTDC_G8_DIAG) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
   // ---- epilogue: lane holds C[m][n..n+3] of every (quadrant, i, j) fragment ----
   const float alpha = a.alpha_dev ? a.alpha * *a.alpha_dev : a.alpha;
   if (a.splitk > 1) {

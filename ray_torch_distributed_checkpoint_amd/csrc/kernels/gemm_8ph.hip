@@ -7,7 +7,6 @@ using namespace rtdc;
 
 static int g_num_cus = 0;
 
-#ifndef RTDC_G4_ONLY  // (-DRTDC_G4_ONLY: a quick build of the 4-wave kernel alone for ISA inspection)
 // Launch the 8-phase kernel (batch 1, no causal modes).  a->splitk is honoured as set.
 // bn: 256, 192 or 128 (output tile columns; 128: bf16 output, K-major A only - else returns 1)
 extern "C" int rtdc_gemm8_launch(const GemmArgs* args, int a_kmajor, int b_kmajor, int out_fp32, int bn,
@@ -78,8 +77,6 @@ extern "C" int rtdc_gemm8p_launch(const GemmArgs* args, int a_kmajor, int b_kmaj
 #undef G8P
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
-
-#endif  // RTDC_G4_ONLY
 
 // Grouped 8-wave launch (gemm8g_kernel): n <= 8 products, every one K % 64 == 0, splitk 1,
 // 256x256 tiles; layouts and output dtype shared.  Returns 1 for an unsupported group.

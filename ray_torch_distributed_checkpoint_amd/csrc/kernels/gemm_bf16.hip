@@ -194,7 +194,9 @@ __device__ __forceinline__ void wait_stages(int ahead) {
 // the last steps), a raw s_barrier publishes it, then tile t+NS-1 is issued into the stage that
 // step t-1 read (every wave passed the barrier after consuming its fragments: WAR-safe).  With
 // 9-18 k-tiles per tile and 128-256 x 64 outputs the 2-stage loop exposed one global-load
-// latency per k-step (the N = 64 convolutions ran at 300-430 TF).
+// latency per k-step (the N = 64 convolutions ran at 300-430 TF).  Every launch now uses
+// NS = 2: in the ResNet-18 step NS = 3 / 4 measured 30 % slower (the second co-resident block
+// hides more latency than two more k-tiles of prefetch, profiles/conv_lds_stages_ab_r3.txt).
 template <class CFG, bool AK, bool BKM, typename OutT, int GM = 0, int NS = 2>
 __global__ __launch_bounds__(CFG::NT, NS == 2 ? 2 : 1) void gemm_bf16_kernel(GemmArgs a) {
   using namespace gemm;
@@ -489,8 +491,6 @@ static void launch_cfg(const GemmArgs& a, int batch, hipStream_t st) {
   hipLaunchKernelGGL((gemm_bf16_kernel<CFG, AK, BKM, OutT, GM, NS>), grid, block, 0, st, a);
 }
 
-// LDS stages of the implicit-GEMM convolution kernels (RTDC_CONV_NS=2|3|4; see the NS note at
-// gemm_bf16_kernel)
 // The N <= 64 implicit-GEMM convolutions (ResNet stem / layer1) on 256x64 tiles of 8 waves
 // (32x64 each: 97-102 VGPRs, four waves per SIMD with two blocks per CU) instead of 4 waves of
 // 64x64 (169 registers, two waves per SIMD): ResNet-18 8.74 vs 8.88 ms/step
@@ -524,21 +524,11 @@ static bool conv64wg_w8() {
   return v == 1;
 }
 
-static int conv_stages() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("RTDC_CONV_NS");
-    v = (e && e[0] >= '2' && e[0] <= '4') ? e[0] - '0' : 2;
-  }
-  return v;
-}
+// The implicit-GEMM convolutions run the 2-stage loop: NS = 3 / 4 measured 30 % slower (see the
+// NS note at gemm_bf16_kernel)
 template <class CFG, bool AK, bool BKM, typename OutT, int GM>
 static void launch_conv(const GemmArgs& a, hipStream_t st) {
-  switch (conv_stages()) {
-    case 3: launch_cfg<CFG, AK, BKM, OutT, GM, 3>(a, 1, st); break;
-    case 4: launch_cfg<CFG, AK, BKM, OutT, GM, 4>(a, 1, st); break;
-    default: launch_cfg<CFG, AK, BKM, OutT, GM, 2>(a, 1, st); break;
-  }
+  launch_cfg<CFG, AK, BKM, OutT, GM>(a, 1, st);
 }
 
 template <bool AK, bool BKM, typename OutT>
@@ -645,27 +635,6 @@ extern "C" int rtdc_gemm4b_set(int v) {
   const int old = gemm4b_enabled() ? 1 : 0;
   if (v >= 0) g_gemm4b = v ? 1 : 0;
   return old;
-}
-
-// cfg 10: the 4-wave 256x256 kernel (gemm_8ph.hip gemm4_kernel, 128x128 per wave).
-// RTDC_GEMM4W=1 routes the 8-wave 256x256 choices (cfg 6 / 8) to it.
-static bool gemm4w_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("RTDC_GEMM4W");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-// RTDC_GEMM_FEW_ROWS=0 keeps pick_cfg's choice for M <= 4096 products (A/B of pick_cfg_few_rows).
-static bool few_rows_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("RTDC_GEMM_FEW_ROWS");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
 }
 
 // Persistent 8-wave kernel (gemm_8ph.hip gemm8p_kernel) for plain-K (no split-K) products with
@@ -778,12 +747,11 @@ extern "C" int rtdc_gemm_bf16(const GemmArgs* args, int a_kmajor, int b_kmajor, 
   GemmArgs a = *args;
   if (a.K % gemm::BK != 0 || a.M % 8 != 0 || a.N % 8 != 0) return 1;
   int cfg = pick_cfg(a, batch, a_kmajor, b_kmajor);
-  if (a.tile_cfg < 0 && few_rows_enabled() && batch == 1 && a.causal == 0 && a_kmajor && !out_fp32 &&
+  if (a.tile_cfg < 0 && batch == 1 && a.causal == 0 && a_kmajor && !out_fp32 &&
       a.M >= 256 && a.M <= 4096 && a.N >= 128 && a.K >= 8 * gemm::BK) {
     const bool plain = a.act == 0 && a.bias_type == 0 && !a.cs_out && !a.cs_ws;
     cfg = pick_cfg_few_rows(a, b_kmajor, plain && a.ws != nullptr);
   }
-  if ((cfg == 6 || cfg == 8) && a.tile_cfg < 0 && gemm4w_enabled()) cfg = 10;
   if ((cfg == 6 || cfg == 8) && a.tile_cfg < 0 && gemm4b_enabled()) cfg = 12;
   // RTDC_GEMM4B_AUTO=1: the one-barrier 8-wave kernel for the forward layout up to 8 rounds of
   // 256x256 tiles (beyond that - the LM head's 12608 tiles - the persistent 8-wave kernel hides
@@ -852,7 +820,7 @@ extern "C" int rtdc_gemm_bf16(const GemmArgs* args, int a_kmajor, int b_kmajor, 
   if (plain && (cfg <= 7 || (cfg >= 10 && cfg <= 13)))
     a.splitk = cfg >= 6 ? pick_splitk(a, tiles, 256, cfg == 7 ? 1.35 : cfg == 11 ? 1.0 : cfg == 12 ? 1.52 : cfg == 13 ? 1.45 : 1.8)
                         : pick_splitk(a, tiles);
-  if (cfg == 10) {
+  if (cfg == 10) {  // the 4-wave 256x256 kernel (gemm_8ph.hip gemm4_kernel): by tile_cfg only
     const int rc = rtdc_gemm4_launch(&a, a_kmajor, b_kmajor, out_fp32, stream);
     if (rc) return rc;
   } else if (cfg == 12) {
@@ -1177,7 +1145,7 @@ extern "C" int rtdc_conv_gemm(const GemmArgs* args, int mode, hipStream_t stream
         a.cv_Ho == a.cv_H && a.cv_Wo == a.cv_W && launch_conv3x3_wgrad(a, stream) == 0)
       return hipGetLastError() == hipSuccess ? 0 : 2;
     const bool narrow = a.M <= 64;
-    a.splitk = pick_splitk(a, narrow ? ntiles<Cfg64x256>(a) : ntiles<Cfg128x128>(a), conv_stages() > 2 ? 256 : 512);
+    a.splitk = pick_splitk(a, narrow ? ntiles<Cfg64x256>(a) : ntiles<Cfg128x128>(a));
     if (narrow && conv64wg_w8()) launch_cfg<Cfg64x256w8, false, false, float, 2>(a, 1, stream);
     else if (narrow) launch_conv<Cfg64x256, false, false, float, 2>(a, stream);
     else if (conv128_w8()) launch_cfg<Cfg128x128w8, false, false, float, 2>(a, 1, stream);

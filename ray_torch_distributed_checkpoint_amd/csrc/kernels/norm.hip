@@ -94,83 +94,6 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const bf16_t* __restrict_
   }
 }
 
-// Two rows per wave with full 16-B lanes where one row's D / 8 chunks are 64k + 32 (GPT-2's
-// D = 768: 96 chunks, so the one-row form leaves half the lanes idle on its second load): the
-// 2 (64k + 32) chunks of a row pair are NPL = 2k + 1 per lane, chunk q = lane + 64 i of the pair
-// belongs to row q / nch.  Same per-row math as norm_fwd_kernel; the second row's chunks sit
-// on other lanes, so its wave reductions add the partials in another order (last-bit
-// differences in mean / rstd).
-template <int NPL, bool RMS>
-__global__ __launch_bounds__(256) void norm_fwd2r_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
-                                                         const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
-                                                         float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                         int M, int D, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;  // rows r0, r0 + 1
-  if (r0 >= M) return;
-  const int nch = D >> 3;
-  const bool two = r0 + 1 < M;
-  const bf16_t* xr = x + (long long)r0 * D;  // the pair is contiguous: chunk q at xr + 8 q
-  float v[NPL][8];
-  float s[2] = {0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int q = lane + 64 * i;
-    const int rr = q >= nch ? 1 : 0;
-    if (rr == 0 || two) {
-      ld8(xr + q * 8, v[i]);
-      float t = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) t += v[i][e];
-      s[rr] += t;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
-    }
-  }
-  float mean[2] = {0.f, 0.f};
-  if (!RMS) {
-    mean[0] = wave_sum(s[0]) / D;
-    mean[1] = wave_sum(s[1]) / D;
-  }
-  float ss[2] = {0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int q = lane + 64 * i;
-    const int rr = q >= nch ? 1 : 0;
-    float t = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float d = v[i][e] - mean[rr];
-      t += d * d;
-    }
-    ss[rr] += t;
-  }
-  const float rstd[2] = {rsqrtf(wave_sum(ss[0]) / D + eps), rsqrtf(wave_sum(ss[1]) / D + eps)};
-  if (lane == 0) {
-    if (mean_out) mean_out[r0] = mean[0];
-    rstd_out[r0] = rstd[0];
-    if (two) {
-      if (mean_out) mean_out[r0 + 1] = mean[1];
-      rstd_out[r0 + 1] = rstd[1];
-    }
-  }
-  bf16_t* yr = y + (long long)r0 * D;
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int q = lane + 64 * i;
-    const int rr = q >= nch ? 1 : 0;
-    if (rr == 1 && !two) continue;
-    const int c = q - rr * nch;
-    float gg[8], bb[8], o[8];
-    ld8(g + c * 8, gg);
-    if (!RMS) ld8(b + c * 8, bb);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (v[i][e] - mean[rr]) * rstd[rr] * gg[e] + (RMS ? 0.f : bb[e]);
-    st8(yr + q * 8, o);
-  }
-}
-
 // dxhat = dy*g ; dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat*xhat))   (LayerNorm)
 // dx = rstd * (dxhat - xhat * mean(dxhat*xhat))                                  (RMSNorm)
 // CS: also the column sums of dx itself (the residual-stream gradient this kernel produces is
@@ -325,90 +248,6 @@ __device__ __forceinline__ void unpack4(uint2 q, float* v) {
   v[1] = __uint_as_float(q.x & 0xffff0000u);
   v[2] = __uint_as_float(q.y << 16);
   v[3] = __uint_as_float(q.y & 0xffff0000u);
-}
-
-// Forward with 8-B lane chunks for widths whose 16-B chunk count is not a multiple of 64
-// (GPT-2: D = 768 -> 192 chunks of 4 = 3 per lane, every lane busy; the 16-B form idles half
-// the lanes in its second chunk).  A wave owns rows gw, gw + nw, ...: gamma / beta are loaded
-// into registers once per wave instead of once per row, and the next row's x is in flight
-// while this row is reduced and written (the rows are a pure HBM stream: 1 read + 1 write).
-template <int CPL, bool RMS>
-__global__ __launch_bounds__(256) void norm_fwd4_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
-                                                       const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
-                                                       float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                       int M, int D, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int nw = gridDim.x * 4;
-  const int nch = D >> 2;
-  float gg[CPL][4], bb[CPL][4];
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      ld4b(g + c * 4, gg[i]);
-      if (!RMS) ld4b(b + c * 4, bb[i]);
-    }
-  }
-  uint2 px[CPL];
-  auto fetch = [&](int r) {
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        const unsigned long long q =
-            __builtin_nontemporal_load((const unsigned long long*)(x + (long long)r * D + c * 4));
-        px[i] = make_uint2((uint32_t)q, (uint32_t)(q >> 32));
-      }
-    }
-  };
-  if (gw < M) fetch(gw);
-  for (int row = gw; row < M; row += nw) {
-    float v[CPL][4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        unpack4(px[i], v[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s += v[i][e];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[i][e] = 0.f;
-      }
-    }
-    if (row + nw < M) fetch(row + nw);
-    const float mean = RMS ? 0.f : wave_sum(s) / D;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = v[i][e] - mean;
-          ss += d * d;
-        }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(ss) / D + eps);
-    if (lane == 0) {
-      if (mean_out) mean_out[row] = mean;
-      rstd_out[row] = rstd;
-    }
-    bf16_t* yr = y + (long long)row * D;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        float o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * gg[i][e] + (RMS ? 0.f : bb[i][e]);
-        *(uint2*)(yr + c * 4) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
-      }
-    }
-  }
 }
 
 template <int CPL, bool RMS, bool CS>
@@ -742,56 +581,6 @@ static int launch_norm_fwd(const void* x, const void* g, const void* b, void* y,
                            float* rstd, int M, int D, float eps, hipStream_t st) {
   if (D % 8 != 0) return 1;
   const int cpl = (D / 8 + 63) / 64;
-  // RTDC_NORM_FWD4=1: 8-B chunks, rows looped per wave (norm_fwd4_kernel) where they fill every
-  // lane and 16-B ones would not (GPT-2's D = 768); RTDC_NORM_FWD_BPC: its resident 256-thread
-  // blocks per CU (default 4).  Opt-in: measured 12.9-15.0 us against 12.8 us for the one-row-
-  // per-wave form at 16384 x 768 (profiles/layernorm_fwd4_ab_r5.txt) - a 50 MB, ~13 us kernel
-  // sits at its launch/ramp-bound ~4 TB/s either way.
-  static int fwd4 = -1, bpc = 4, cus = 0;
-  if (fwd4 < 0) {
-    const char* e = getenv("RTDC_NORM_FWD4");
-    fwd4 = (e && e[0] == '1') ? 1 : 0;
-    const char* c = getenv("RTDC_NORM_FWD_BPC");
-    if (c && atoi(c) > 0) bpc = atoi(c);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  const int cpl4 = (D / 4) / 64;
-  if (fwd4 && (D / 8) % 64 != 0 && (D / 4) % 64 == 0 && cpl4 >= 1 && cpl4 <= 4) {
-    int nb = (M + 3) / 4;
-    if (nb > cus * bpc) nb = cus * bpc;
-    dim3 grid4(nb), block4(256);
-#define L4(C)                                                                                 \
-  hipLaunchKernelGGL((norm_fwd4_kernel<C, RMS>), grid4, block4, 0, st, (const bf16_t*)x,       \
-                     (const bf16_t*)g, (const bf16_t*)b, (bf16_t*)y, mean, rstd, M, D, eps)
-    if (cpl4 == 1) L4(1);
-    else if (cpl4 == 2) L4(2);
-    else if (cpl4 == 3) L4(3);
-    else L4(4);
-#undef L4
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  }
-  // RTDC_NORM_FWD2R=1: two rows per wave where a row's 16-B chunks are 64k + 32 (A/B)
-  static int fwd2r = -1;
-  if (fwd2r < 0) {
-    const char* e = getenv("RTDC_NORM_FWD2R");
-    fwd2r = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (fwd2r && (D / 8) % 64 == 32 && (D / 8) <= 224) {
-    const int npl = (2 * (D / 8)) / 64;
-    dim3 grid2((M + 7) / 8), block2(256);
-#define L2(C)                                                                                 \
-  hipLaunchKernelGGL((norm_fwd2r_kernel<C, RMS>), grid2, block2, 0, st, (const bf16_t*)x,      \
-                     (const bf16_t*)g, (const bf16_t*)b, (bf16_t*)y, mean, rstd, M, D, eps)
-    if (npl == 1) L2(1);
-    else if (npl == 3) L2(3);
-    else if (npl == 5) L2(5);
-    else L2(7);
-#undef L2
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  }
   dim3 grid((M + 3) / 4), block(256);
 #define L(C)                                                                                  \
   hipLaunchKernelGGL((norm_fwd_kernel<C, RMS>), grid, block, 0, st, (const bf16_t*)x,         \

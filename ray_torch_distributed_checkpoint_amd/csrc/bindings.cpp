@@ -83,7 +83,8 @@ int rtdc_im2col(const void* x, void* cols, int B, int H, int W, int C, int Ho, i
 int rtdc_xent_finalize(const float* loss, const int64_t* target, int M, float fixed_n, int ignore, float* out,
                        hipStream_t st);
 int rtdc_xent_alpha(const float* g, const float* den, float* out, hipStream_t st);
-int rtdc_scale_dev(const void* x, void* y, long long n, int is_bf16, const float* g, const float* den, hipStream_t st);
+int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* target, const float* lse, const float* g,
+                  const float* den, int M, int V, int ignore_index, int is_bf16, hipStream_t st);
 int rtdc_nchw_to_nhwc_bf16(const float* x, void* y, int B, int C, long long HW, hipStream_t st);
 int rtdc_col2im(const void* dcols, void* dx, const void* addend, int B, int H, int W, int C, int Ho, int Wo, int KH,
                 int KW, int stride, int pad, int K, int Kp, hipStream_t st);
@@ -840,15 +841,26 @@ static void xent_alpha(Tensor g, Tensor den, Tensor out) {
   check_rc(rtdc_xent_alpha(g.data_ptr<float>(), den.data_ptr<float>(), out.data_ptr<float>(), cur_stream()),
            "xent_alpha");
 }
-static void scale_dev(Tensor x, Tensor y, Tensor g, Tensor den) {
-  check_dev(x, "x");
-  TORCH_CHECK(x.is_contiguous() && y.is_contiguous() && x.numel() == y.numel() && x.scalar_type() == y.scalar_type() &&
-                  (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat),
-              "scale_dev: matching contiguous bf16/fp32 tensors");
-  TORCH_CHECK(g.scalar_type() == at::kFloat && den.scalar_type() == at::kFloat, "scale_dev: fp32 scalars");
-  check_rc(rtdc_scale_dev(x.data_ptr(), y.data_ptr(), x.numel(), x.scalar_type() == at::kBFloat16 ? 1 : 0,
-                          g.data_ptr<float>(), den.data_ptr<float>(), cur_stream()),
-           "scale_dev");
+// dlogits = (g[0] / den[0]) * (softmax - onehot) of dense [M, V] logits from the saved row logsumexp
+static void xent_bwd(Tensor logits, Tensor dlogits, Tensor target, Tensor lse, Tensor g, Tensor den,
+                     int64_t ignore_index) {
+  TORCH_CHECK(logits.is_cuda() && dlogits.is_cuda(), "xent_bwd: GPU tensors expected");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && dlogits.is_contiguous() &&
+                  dlogits.numel() == logits.numel() && logits.scalar_type() == dlogits.scalar_type() &&
+                  (logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat),
+              "xent_bwd: matching contiguous bf16/fp32 [M, V] tensors");
+  const int64_t M = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(target.is_cuda() && target.scalar_type() == at::kLong && target.is_contiguous() && target.numel() == M,
+              "xent_bwd: int64 target per row");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == M,
+              "xent_bwd: fp32 logsumexp per row");
+  TORCH_CHECK(g.is_cuda() && den.is_cuda() && g.scalar_type() == at::kFloat && den.scalar_type() == at::kFloat &&
+                  g.numel() >= 1 && den.numel() >= 1,
+              "xent_bwd: fp32 scalars");
+  check_rc(rtdc_xent_bwd(logits.data_ptr(), dlogits.data_ptr(), target.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                         g.data_ptr<float>(), den.data_ptr<float>(), (int)M, (int)V, (int)ignore_index,
+                         logits.scalar_type() == at::kBFloat16, cur_stream()),
+           "xent_bwd");
 }
 static void nchw_to_nhwc_bf16(Tensor x, Tensor y) {
   check_dev(x, "x");
@@ -1084,7 +1096,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("xent_finalize", &xent_finalize);
   m.def("xent_alpha", &xent_alpha);
-  m.def("scale_dev", &scale_dev);
+  m.def("xent_bwd", &xent_bwd);
   m.def("nchw_to_nhwc_bf16", &nchw_to_nhwc_bf16);
   m.def("copy2d", &copy2d);
   m.def("maxpool_bwd", &maxpool_bwd);

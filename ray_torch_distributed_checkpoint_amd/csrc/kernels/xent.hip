@@ -424,31 +424,36 @@ __global__ void xent_alpha_kernel(const float* __restrict__ g, const float* __re
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = g[0] / den[0];
 }
 
-// y = x * (g[0] / den[0]) (bf16 or fp32 x, 8 elements per thread)
-template <typename T>
-__global__ __launch_bounds__(256) void scale_dev_kernel(const T* __restrict__ x, T* __restrict__ y, long long n,
-                                                       const float* __restrict__ g, const float* __restrict__ den) {
-  const float a = g[0] / den[0];
-  const long long n8 = n / 8;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    if constexpr (sizeof(T) == 2) {
-      const uint4 q = ((const uint4*)x)[i];
-      const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-      uint32_t o[4];
+// dlogits = (g[0] / den[0]) * (softmax - onehot) of dense rows [M, V] from the logits and the row
+// logsumexp that the forward saved: the upstream loss gradient and the divisor are known only
+// here, so the gradient is formed in fp32 with them and rounded to the output type ONCE (scaling
+// a stored bf16 gradient rounded it twice: up to 0.5 * (1 + mantissa of the scale) ulp).  Rows
+// whose target is ignore_index (or out of range) get exactly 0.  One block per row.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ logits, T* __restrict__ dlogits,
+                                                      const int64_t* __restrict__ target,
+                                                      const float* __restrict__ lse_in, const float* __restrict__ g,
+                                                      const float* __restrict__ den, int M, int V, int ignore_index) {
+  const int row = blockIdx.x;
+  if (row >= M) return;
+  const int64_t tgt = target[row];
+  const bool valid = tgt != ignore_index && tgt >= 0 && tgt < V;
+  const float sc = valid ? g[0] / den[0] : 0.f;
+  const float lse = lse_in[row];
+  const T* x = logits + (long long)row * V;
+  T* dx = dlogits + (long long)row * V;
+  if constexpr (VEC) {  // V % 8 == 0 and an aligned base: every row starts 16-B aligned
+    constexpr int E = 16 / sizeof(T);
+    for (int c = threadIdx.x * E; c < V; c += 256 * E) {
+      float v[E], gv[E];
+      ldvec<T>(x + c, v);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        o[e] = pack_bf2(__uint_as_float(w[e] << 16) * a, __uint_as_float(w[e] & 0xffff0000u) * a);
-      ((uint4*)y)[i] = make_uint4(o[0], o[1], o[2], o[3]);
-    } else {
-      const float4 p = ((const float4*)x)[2 * i], q = ((const float4*)x)[2 * i + 1];
-      ((float4*)y)[2 * i] = make_float4(p.x * a, p.y * a, p.z * a, p.w * a);
-      ((float4*)y)[2 * i + 1] = make_float4(q.x * a, q.y * a, q.z * a, q.w * a);
+      for (int e = 0; e < E; ++e) gv[e] = sc * (__expf(v[e] - lse) - (c + e == tgt ? 1.f : 0.f));
+      stvec<T>(dx + c, gv);
     }
-  }
-  // tail (n % 8)
-  for (long long i = n8 * 8 + blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    if constexpr (sizeof(T) == 2) y[i] = f2bf(bf2f(x[i]) * a);
-    else y[i] = x[i] * a;
+  } else {
+    for (int j = threadIdx.x; j < V; j += 256)
+      stv<T>(dx, j, sc * (__expf(ldv<T>(x, j) - lse) - (j == tgt ? 1.f : 0.f)));
   }
 }
 }  // namespace rtdc
@@ -464,15 +469,20 @@ extern "C" int rtdc_xent_alpha(const float* g, const float* den, float* out, hip
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-extern "C" int rtdc_scale_dev(const void* x, void* y, long long n, int is_bf16, const float* g, const float* den,
-                              hipStream_t st) {
-  long long blocks = (n / 8 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  if (is_bf16)
-    hipLaunchKernelGGL(rtdc::scale_dev_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x,
-                       (bf16_t*)y, n, g, den);
-  else
-    hipLaunchKernelGGL(rtdc::scale_dev_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x,
-                       (float*)y, n, g, den);
+extern "C" int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* target, const float* lse,
+                             const float* g, const float* den, int M, int V, int ignore_index, int is_bf16,
+                             hipStream_t st) {
+  if (M < 1 || V < 1) return 1;
+  // 16 B per lane only where every row starts 16-B aligned (a contiguous view may start anywhere)
+  const bool vec = V % 8 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
+#define XB(T, VEC)                                                                                              \
+  hipLaunchKernelGGL((rtdc::xent_bwd_kernel<T, VEC>), dim3(M), dim3(256), 0, st, (const T*)logits, (T*)dlogits, \
+                     target, lse, g, den, M, V, ignore_index)
+  if (is_bf16) {
+    if (vec) XB(bf16_t, true); else XB(bf16_t, false);
+  } else {
+    if (vec) XB(float, true); else XB(float, false);
+  }
+#undef XB
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

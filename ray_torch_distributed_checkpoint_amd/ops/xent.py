@@ -1,7 +1,8 @@
 """Fused cross-entropy (+ LM-head fusion) on the native row kernel.
 
 `cross_entropy(logits, target)` = nn.CrossEntropyLoss() (mean over non-ignored rows) for fp32
-or bf16 logits: one launch computes per-row loss, logsumexp and the gradient.
+or bf16 logits: one launch computes per-row loss and logsumexp, one more (in the backward) the
+gradient, rounded once.
 `lm_head_cross_entropy(x, w, target, vocab)` computes logits = x w^T on the MFMA GEMM into a
 bf16 buffer that the xent kernel overwrites IN PLACE with d(loss)/d(logits), so the 1.6 GB
 GPT-2 logits tensor is written once and read twice in the whole step; padded vocabulary
@@ -36,21 +37,25 @@ class _CrossEntropy(torch.autograd.Function):
         M, V = logits.shape
         lg = logits.contiguous()
         loss = torch.empty(M, dtype=torch.float32, device=lg.device)
-        grad = torch.empty_like(lg)
+        lse = torch.empty(M, dtype=torch.float32, device=lg.device)
         tgt = target.contiguous()
-        # unscaled softmax gradient; the mean and the 1/divisor (device count of non-ignored
-        # rows, or n_valid) come out of one native reduction - no ATen kernels in the step
-        gpu_ext().xent(lg, grad, tgt, loss, None, None, M, V, V, 1.0, IGNORE_INDEX)
+        # per-row loss and logsumexp; the mean and the 1/divisor (device count of non-ignored
+        # rows, or n_valid) come out of one native reduction - no ATen kernels in the step.
+        # The gradient is formed in the backward from the logits and the saved logsumexp, where
+        # the upstream gradient and the divisor are known: one rounding to the logits' type
+        # (an unscaled bf16 gradient stored here and scaled there was rounded twice).
+        gpu_ext().xent(lg, None, tgt, loss, lse, None, M, V, V, 1.0, IGNORE_INDEX)
         out = torch.empty(2, dtype=torch.float32, device=lg.device)
         gpu_ext().xent_finalize(loss, tgt if n_valid is None else None, float(n_valid or 1), out)
-        ctx.save_for_backward(grad, out)
+        ctx.save_for_backward(lg, tgt, lse, out)
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        grad, out = ctx.saved_tensors
-        dl = torch.empty_like(grad)
-        gpu_ext().scale_dev(grad, dl, g.detach().to(torch.float32).reshape(1).contiguous(), out[1:2])
+        lg, tgt, lse, out = ctx.saved_tensors
+        dl = torch.empty_like(lg)
+        gpu_ext().xent_bwd(lg, dl, tgt, lse, g.detach().to(torch.float32).reshape(1).contiguous(), out[1:2],
+                           IGNORE_INDEX)
         return dl, None, None
 
 

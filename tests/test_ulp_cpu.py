@@ -1,0 +1,182 @@
+"""The ulp yardstick of tests/ulp.py, checked without a GPU:
+
+* the metric: an RNE rounding to bf16 scores <= 0.5 ulp, one element moved by one ulp scores >= 1;
+* the twin condition: on every case generator that tests/test_row_kernels_gpu.py runs, the fp32
+  twin of each reference stays <= 2^-4 ulp (bf16 outputs) / <= 2^-18 relative (fp32 outputs) of
+  the fp64 reference, i.e. the FLOOR_* constants and the inputs are well chosen;
+* sensitivity: a deliberately wrong twin, rounded to bf16, exceeds the allowance that a kernel is
+  given on the same case.
+"""
+import pytest
+import torch
+
+from tests import ulp as U
+
+F64, F32 = U.F64, U.F32
+
+
+# ------------------------------------------------------------------------------- the metric
+def test_metric_rne_rounding_is_half_an_ulp_and_one_step_is_one():
+    gen = torch.Generator().manual_seed(1)
+    ref = torch.cat([torch.randn(4096, generator=gen, dtype=F64) * s for s in (1e-6, 1.0, 3e4)])
+    ref = torch.cat([ref, torch.tensor([1.0, 2.0, 0.99999, 1.00001, -255.9, 2.0 ** -30], dtype=F64)])
+    ref = ref.float().double()  # fp32 values, so that torch's fp64 -> fp32 -> bf16 conversion rounds once
+    out = ref.to(U.BF16)  # torch rounds to nearest even
+    e = U.ulp_err(out, ref, U.TINY)
+    assert 0.25 < e <= 0.5
+    # spacing of the reference's binade
+    assert U.ulp_bf16(torch.tensor([1.0, 1.99, 2.0, 0.75], dtype=F64)).tolist() == [2.0 ** -7, 2.0 ** -7, 2.0 ** -6,
+                                                                                     2.0 ** -8]
+    moved = out.double().clone()
+    moved[17] += U.ulp_bf16(ref[17].abs())
+    assert U.ulp_err(moved, ref, U.TINY) >= 1.0
+    # the floor: an element far below it is judged in the floor's last place
+    assert U.ulp_err(torch.tensor([0.0]), torch.tensor([2.0 ** -20], dtype=F64), 1.0) == 2.0 ** -13
+    # a per-row floor broadcasts
+    r2 = torch.tensor([[1.0, 2.0 ** -12], [4.0, 1.0]], dtype=F64)
+    fl = U.row_floor(r2, 2.0 ** -8)
+    assert fl.shape == (2, 1) and fl[1, 0] == 2.0 ** -6
+    assert U.ulp_err(r2 + torch.tensor([[0.0, 2.0 ** -15], [0.0, 0.0]], dtype=F64), r2, fl) == 1.0
+    # NaN never passes
+    assert not U.ulp_err(torch.tensor([float("nan")]), torch.tensor([1.0], dtype=F64), 1.0) <= 1e30
+
+
+def test_rel_err_and_allowances():
+    ref = torch.tensor([10.0, 0.0], dtype=F64)
+    assert U.rel_err(torch.tensor([10.5, 0.0]), ref, torch.tensor([100.0, 0.0])) == pytest.approx(0.005)
+    assert U.rel_err(torch.tensor([10.0, 1e-30]), ref, torch.tensor([100.0, 0.0])) == float("inf")
+    assert U.allow_bf16(0.0) == 0.5 + 2.0 ** -6 and U.allow_bf16(2.0 ** -4, k=2) == 2.0
+    assert U.allow_f32(0.0, 5) == 21 * 2.0 ** -24 and U.allow_f32(2.0 ** -18, 1) == 2.0 ** -14
+
+
+# ------------------------------------------------------------------------------- twin condition
+@pytest.mark.parametrize("rms", [False, True], ids=["layernorm", "rmsnorm"])
+def test_twin_norm(rms):
+    J = U.Judge()
+    for M, D, eps in U.norm_cases():
+        for dres in ((False, True) if M >= 67 else (True,)):
+            c = U.norm_inputs(M, D, dres=dres)
+            U.judge_norm(J, "rmsnorm" if rms else "layernorm", (M, D, eps, "dres" if dres else ""), c, eps, rms, {})
+    J.check()
+
+
+def test_twin_xent():
+    J = U.Judge()
+    for dt, V, ld, arm in U.XENT_ARMS:
+        for planted in (False, True):
+            c = U.xent_inputs(dt, V, ld, planted)
+            for gs in (1.0, 1.0 / 7):
+                U.judge_xent(J, "xent", (arm, V, ld, "planted" if planted else "randn", round(gs, 3)), c, gs, {})
+    for dt, V in U.XENT_WRAPPER:
+        c = U.xent_wrapper_inputs(dt, V)
+        r = U.judge_xent(J, "xent-wrap", (str(dt)[6:], V), c, 1.0, {})
+        n = int((c["target"] != U.IGNORE_INDEX).sum())
+        (m64, sc), (m32, _) = U.mean_loss_ref(F64, r["loss"], n), U.mean_loss_ref(F32, r["loss"], n)
+        J.rel("xent-wrap", (str(dt)[6:], V), "mean", None, m64, m32, sc, 1)
+    J.check()
+
+
+def test_twin_softmax():
+    J = U.Judge()
+    for rows, T, causal in U.SOFTMAX_CASES:
+        c = U.softmax_inputs(rows, T, causal)
+        _, t = U.judge_softmax_fwd(J, (rows, T, "causal" if causal else "full"), c, T, causal, {})
+        # the backward reads the bf16 P that the forward wrote
+        U.judge_softmax_bwd(J, (rows, T, "causal" if causal else "full"), t["P"].to(U.BF16), c["dP"], T, causal, None)
+    J.check()
+
+
+def test_twin_swiglu_and_rope():
+    J = U.Judge()
+    for M, F in U.SWIGLU_CASES:
+        U.judge_swiglu(J, (M, F), U.swiglu_inputs(M, F), {})
+    for Dh, H, Hkv in U.ROPE_CASES:
+        c = U.rope_inputs(Dh, H, Hkv)
+        for inverse in (False, True):
+            U.judge_rope(J, (Dh, H, Hkv, "inv" if inverse else "fwd"), c["x"], H, Hkv, Dh, inverse, None)
+        U.judge_rope(J, (Dh, H, Hkv, "bwd"), c["dy"], H, Hkv, Dh, True, None, "dx")   # apply_rope's backward
+    J.check()
+
+
+# ------------------------------------------------------------------------------- sensitivity
+def _ulp_caught(mut, ref, twin, floor, k=1):
+    """the mutant, rounded to bf16 like a kernel output, is outside the allowance"""
+    allow = U.allow_bf16(U.ulp_err(twin, ref, floor), k)
+    e = U.ulp_err(mut.to(U.BF16), ref, floor)
+    # the honest twin, rounded the same way, is inside it
+    assert U.ulp_err(twin.to(U.BF16), ref, floor) <= allow
+    return e > allow
+
+
+def _rel_caught(mut, ref, twin, scale, R):
+    allow = U.allow_f32(U.rel_err(twin, ref, scale), R)
+    return U.rel_err(mut, ref, scale) > allow
+
+
+@pytest.mark.parametrize("mutant,outputs", [("beta", ["y"]), ("var", ["y"]), ("eps", ["y", "dx"]), ("m1", ["dx"]),
+                                            ("dres", ["dx"]), ("dgamma", ["dgamma"])])
+def test_mutant_layernorm(mutant, outputs):
+    M, D, eps = 5, 200, 1e-5
+    c = U.norm_inputs(M, D, dres=True)
+    a = (c["x"], c["g"], c["b"], eps, c["dy"], c["dres"], False)
+    r, t, m = U.norm_ref(F64, *a), U.norm_ref(F32, *a), U.norm_ref(F32, *a, mutant=mutant)
+    floors = {"y": U.FLOOR_LN_Y, "dx": U.FLOOR_NORM_DX}
+    caught = []
+    for n in outputs:
+        if n in floors:
+            caught.append(_ulp_caught(m[n], r[n], t[n], U.row_floor(r[n], floors[n])))
+        else:
+            caught.append(_rel_caught(m[n], r[n], t[n], r[n + "_scale"], 1))
+    assert any(caught), (mutant, outputs)
+    if mutant == "dres":  # only the last row differs
+        assert not _ulp_caught(m["dx"][:-1], r["dx"][:-1], t["dx"][:-1], U.row_floor(r["dx"][:-1], U.FLOOR_NORM_DX))
+
+
+@pytest.mark.parametrize("mutant", ["onehot", "padding", "ignored"])
+def test_mutant_xent(mutant):
+    V, ld = 333, 344
+    c = U.xent_inputs(U.BF16, V, ld, planted=False)
+    a = (c["logits"], c["target"], V, 1.0 / 7)
+    r, t, m = U.xent_ref(F64, *a), U.xent_ref(F32, *a), U.xent_ref(F32, *a, mutant=mutant)
+    assert _ulp_caught(m["grad"], r["grad"], t["grad"], U.xent_grad_floor(r, 1.0 / 7))
+
+
+def test_planted_rows_tell_first_from_last_argmax():
+    """a check on the data: on the planted rows an argmax that took the last of equal maxima would
+    differ from first_argmax, which the GPU test compares with torch.equal"""
+    for dt, V, ld, _ in [U.XENT_ARMS[0], U.XENT_ARMS[5], U.XENT_ARMS[10], U.XENT_ARMS[13]]:
+        c = U.xent_inputs(dt, V, ld, planted=True)
+        first, last = U.first_argmax(c["logits"], V), U.last_argmax(c["logits"], V)
+        assert (first[:2] != last[:2]).all() and first[3] == 0 and last[3] == V - 1   # the two tie rows, the equal row
+        assert first[2] == V - 1 and first[4] == V - 1 and (first <= last).all()
+        x = c["logits"][:, :V].double()
+        assert (x.gather(1, first[:, None]) == x.amax(1, keepdim=True)).all()
+
+
+def test_mutant_softmax_diagonal_excluded():
+    rows, T = 24, 8
+    c = U.softmax_inputs(rows, T, True)
+    r, t, m = (U.softmax_ref(F64, c["S"], T, True), U.softmax_ref(F32, c["S"], T, True),
+               U.softmax_ref(F32, c["S"], T, True, mutant="diag"))
+    assert _ulp_caught(m["P"], r["P"], t["P"], U.row_floor(r["P"], U.FLOOR_SOFTMAX_P))
+
+
+@pytest.mark.parametrize("mutant", ["ksign", "nowrap"])
+def test_mutant_rope(mutant):
+    Dh, H, Hkv = 16, 4, 2
+    c = U.rope_inputs(Dh, H, Hkv)
+    a = (c["x"], U.ROPE_T, H, Hkv, Dh)
+    r, t, m = U.rope_ref(F64, *a), U.rope_ref(F32, *a), U.rope_ref(F32, *a, mutant=mutant)
+    assert _ulp_caught(m, r, t, U.row_floor(r, U.FLOOR_ROPE))
+    if mutant == "ksign":  # only the K heads differ
+        assert not _ulp_caught(m[:, :, :H], r[:, :, :H], t[:, :, :H], U.row_floor(r[:, :, :H], U.FLOOR_ROPE))
+    else:                  # only the second batch differs
+        assert not _ulp_caught(m[:1], r[:1], t[:1], U.row_floor(r[:1], U.FLOOR_ROPE))
+
+
+def test_mutant_swiglu_halves_swapped():
+    c = U.swiglu_inputs(5, 520)
+    r, t, m = (U.swiglu_ref(F64, c["gu"], c["dh"]), U.swiglu_ref(F32, c["gu"], c["dh"]),
+               U.swiglu_ref(F32, c["gu"], c["dh"], mutant="swap"))
+    assert _ulp_caught(m["dgu"], r["dgu"], t["dgu"], U.row_floor(r["dgu"], U.FLOOR_SWIGLU))
+    assert not _ulp_caught(m["h"], r["h"], t["h"], U.row_floor(r["h"], U.FLOOR_SWIGLU))

@@ -2,6 +2,14 @@
 Llama-3-8B shapes; random operands, one process, interleaved repetitions.
 
     python benchmarks/attn_bench.py [--reps 20]
+    python benchmarks/attn_bench.py --doc-len T T/8 100 [--only gpt2] [--rounds 7]
+
+--doc-len L times the document-masked kernels (packed sequences: equal documents of length L, the
+last one shorter when L does not divide T) next to the plain causal kernels on the same shape and
+operands: kernel calls alone (the dK/dV head split chosen as the op chooses it), every timed
+window at least --window-ms long, plain and masked alternating over --rounds rounds in one
+process, median and minimum per arm and the plain arm's own run-to-run spread.  L = T (one document) is
+the cost of the mask code with nothing to skip; L is an integer, `T` or `T/<n>`.
 """
 from __future__ import annotations
 
@@ -34,15 +42,87 @@ def timeit(fn, reps):
     return ev[0].elapsed_time(ev[1]) / reps * 1e-3
 
 
+def _doc_len(spec: str, T: int) -> int:
+    if spec.upper().startswith("T"):
+        return T // int(spec[2:]) if len(spec) > 1 else T
+    return int(spec)
+
+
+def doc_mask_ab(args):
+    """Plain vs document-masked kernels, forward and backward, per shape and document length."""
+    from statistics import median
+
+    from ray_torch_distributed_checkpoint_amd.ops import DocLayout
+    from ray_torch_distributed_checkpoint_amd.ops.attention import _dkdv_head_split
+
+    ext = gpu_ext()
+    for name, B, T, H, Hkv, Dh in SHAPES[:2]:
+        if args.only and name != args.only:
+            continue
+        W = (H + 2 * Hkv) * Dh
+        scale = Dh ** -0.5
+        q_ = (torch.randn(B, T, W, device="cuda") * 0.5).bfloat16()
+        o_ = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device="cuda")
+        lse = torch.empty((B * H, T), dtype=torch.float32, device="cuda")
+        dy = torch.randn_like(o_)
+        dqkv = torch.empty_like(q_)
+        delta = torch.empty((B * H, T), dtype=torch.float32, device="cuda")
+        # the GQA head split of dK/dV and its fp32 partials, chosen as causal_attention chooses them
+        qs = _dkdv_head_split(B, T, H, Hkv, q_.device)
+        part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device="cuda") if qs > 1 else None
+        for spec in args.doc_len:
+            L = _doc_len(spec, T)
+            if not 1 <= L <= T:
+                raise SystemExit(f"--doc-len {spec}: need 1 <= L <= T = {T}")
+            row = [L] * (T // L) + ([T % L] if T % L else [])
+            d = DocLayout.from_lengths([row] * B, T, "cuda")
+            arms = {
+                "plain_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale),
+                "doc_fwd": lambda: ext.flash_fwd_doc(q_, o_, lse, d.start, d.end, B, T, H, Hkv, Dh, scale),
+                "plain_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part,
+                                                   qs),
+                "doc_bwd": lambda: ext.flash_bwd_doc(q_, o_, dy, lse, delta, dqkv, d.start, d.end, B, T, H, Hkv, Dh,
+                                                     scale, None, part, qs),
+            }
+            # repetitions per arm so that every timed window is at least --window-ms long (a few ms
+            # measure the clock ramp and the scheduler as much as the kernel)
+            # (calibrated on 200 warm calls, with a quarter to spare for a faster clock later on)
+            reps = {k: max(args.reps, int(1.25 * args.window_ms * 1e-3 / timeit(fn, 200)) + 1) for k, fn in arms.items()}
+            # an arm's forward runs right before its backward, which so reads the o / lse of its
+            # own mask
+            t = {k: [] for k in arms}
+            for _ in range(args.rounds):
+                for kind in ("plain", "doc"):
+                    t[kind + "_fwd"].append(timeit(arms[kind + "_fwd"], reps[kind + "_fwd"]) * 1e6)
+                    t[kind + "_bwd"].append(timeit(arms[kind + "_bwd"], reps[kind + "_bwd"]) * 1e6)
+            res = {"shape": name, "B": B, "T": T, "H": H, "Hkv": Hkv, "Dh": Dh, "doc_len": L, "docs_per_row": len(row),
+                   "dkdv_head_split": qs, "reps": reps, "window_ms": args.window_ms, "rounds": args.rounds}
+            for k, v in t.items():
+                res[k + "_us_median"], res[k + "_us_min"] = round(median(v), 2), round(min(v), 2)
+            for ph in ("fwd", "bwd"):
+                pm, dm = median(t["plain_" + ph]), median(t["doc_" + ph])
+                res[f"plain_{ph}_spread_pct"] = round(100 * (max(t["plain_" + ph]) - min(t["plain_" + ph])) / pm, 2)
+                res[f"doc_vs_plain_{ph}_pct"] = round(100 * (dm - pm) / pm, 2)
+            print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--doc-len", nargs="+", default=None, metavar="L",
+                    help="time the document-masked kernels with equal documents of length L (an integer, T or "
+                         "T/<n>; several allowed) next to the plain ones")
+    ap.add_argument("--rounds", type=int, default=7, help="--doc-len: alternating plain / masked rounds")
+    ap.add_argument("--window-ms", type=float, default=120.0,
+                    help="--doc-len: least length of every timed window (repetitions are scaled to it)")
     args = ap.parse_args()
     torch.manual_seed(0)
     from gemm_bench import warm_up_clocks
 
     warm_up_clocks()
+    if args.doc_len:
+        return doc_mask_ab(args)
     for name, B, T, H, Hkv, Dh in SHAPES:
         if args.only and name != args.only:
             continue

@@ -111,6 +111,16 @@ int rtdc_avgpool(const void* x, void* y, int B, int HW, int C, int backward, hip
 int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                    int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws, float* part, int qs,
                    hipStream_t st);
+int rtdc_flash_fwd_doc(const void* qkv, void* out, float* lse, const int* doc_start, const int* doc_end, int B, int T,
+                       int H, int Hkv, int Dh, float scale, hipStream_t st);
+int rtdc_flash_bwd_doc(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                       const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv, int Dh, float scale,
+                       float* cs_ws, float* part, int qs, hipStream_t st);
+int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, const int* doc_start, int ntok, int T,
+                  int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st);
+int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st);
+int rtdc_synth_doc_flags(const int64_t* ids, int B, int T, long long doc_len, unsigned long long seed_add,
+                         uint8_t* flags, hipStream_t st);
 }
 
 static hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
@@ -575,7 +585,81 @@ static void flash_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor de
            "flash_bwd");
 }
 
+// document layout of packed sequences: start / end int32 [B, T] on the qkv's device
+static void check_docs(const Tensor& qkv, const Tensor& start, const Tensor& end, int64_t B, int64_t T,
+                       const char* what) {
+  TORCH_CHECK(start.is_cuda() && end.is_cuda() && start.device() == qkv.device() && end.device() == qkv.device() &&
+                  start.scalar_type() == at::kInt && end.scalar_type() == at::kInt && start.is_contiguous() &&
+                  end.is_contiguous() && start.dim() == 2 && start.size(0) == B && start.size(1) == T &&
+                  end.sizes() == start.sizes(),
+              what, ": doc start / end must be contiguous int32 [B, T] on the qkv's device");
+}
+static void flash_fwd_doc(Tensor qkv, Tensor out, Tensor lse, Tensor doc_start, Tensor doc_end, int64_t B, int64_t T,
+                          int64_t H, int64_t Hkv, int64_t Dh, double scale) {
+  check_dev(qkv, "qkv");
+  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd_doc: contiguous tensors expected");
+  check_docs(qkv, doc_start, doc_end, B, T, "flash_fwd_doc");
+  check_rc(rtdc_flash_fwd_doc(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), doc_start.data_ptr<int>(),
+                              doc_end.data_ptr<int>(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
+                              cur_stream()),
+           "flash_fwd_doc");
+}
+static void flash_bwd_doc(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, Tensor doc_start,
+                          Tensor doc_end, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh, double scale,
+                          c10::optional<Tensor> cs_ws, c10::optional<Tensor> part, int64_t qs) {
+  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd_doc: contiguous tensors expected");
+  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd_doc: qs must divide the GQA group size");
+  check_docs(qkv, doc_start, doc_end, B, T, "flash_bwd_doc");
+  if (qs > 1)
+    TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
+                    part->numel() >= qs * B * T * Hkv * 2 * Dh,
+                "flash_bwd_doc: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
+  if (cs_ws.has_value())
+    TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
+                    cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
+                "flash_bwd_doc: cs_ws fp32 [B*T/16][W]");
+  check_rc(rtdc_flash_bwd_doc(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
+                              delta.data_ptr<float>(), dqkv.data_ptr(), doc_start.data_ptr<int>(),
+                              doc_end.data_ptr<int>(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
+                              cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
+                              qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
+           "flash_bwd_doc");
+}
+// flags uint8 [B, T] (non-zero: a document starts here; position 0 always does) -> start / end
+static void doc_layout(Tensor flags, Tensor start, Tensor end) {
+  TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kByte && flags.is_contiguous() && flags.dim() == 2,
+              "doc_layout: flags must be a contiguous uint8 [B, T] GPU tensor");
+  check_docs(flags, start, end, flags.size(0), flags.size(1), "doc_layout");
+  check_rc(rtdc_doc_layout(flags.data_ptr<uint8_t>(), (int)flags.size(0), (int)flags.size(1), start.data_ptr<int>(),
+                           end.data_ptr<int>(), cur_stream()),
+           "doc_layout");
+}
+// flags uint8 [B, T] of the synthetic sequences ids[B] (workloads.SyntheticTokens doc_len)
+static void synth_doc_flags(Tensor ids, Tensor flags, int64_t doc_len, int64_t seed_add) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous() && ids.dim() == 1,
+              "synth_doc_flags: ids must be a contiguous 1-D int64 GPU tensor");
+  TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kByte && flags.is_contiguous() && flags.dim() == 2 &&
+                  flags.size(0) == ids.numel(),
+              "synth_doc_flags: flags must be contiguous uint8 [B, T]");
+  check_rc(rtdc_synth_doc_flags(ids.data_ptr<int64_t>(), (int)ids.numel(), (int)flags.size(1), (long long)doc_len,
+                                (unsigned long long)seed_add, flags.data_ptr<uint8_t>(), cur_stream()),
+           "synth_doc_flags");
+}
+
 // ---------------------------------------------------------------------------------- llama ops
+// doc_start (int32 [B, T]): per-document positions, the table row is t - doc_start[b, t]
+static void rope_doc(Tensor x, Tensor y, Tensor cosb, Tensor sinb, Tensor doc_start, int64_t T, int64_t nrot_heads,
+                     int64_t ntot_heads, int64_t Dh, bool inverse) {
+  TORCH_CHECK(x.is_contiguous() && y.is_contiguous(), "rope_doc: contiguous tensors expected");
+  const int64_t ntok = x.numel() / (ntot_heads * Dh);
+  TORCH_CHECK(doc_start.is_cuda() && doc_start.device() == x.device() && doc_start.scalar_type() == at::kInt &&
+                  doc_start.is_contiguous() && doc_start.numel() == ntok,
+              "rope_doc: doc_start must be contiguous int32 [B, T] on x's device");
+  check_rc(rtdc_rope_doc(x.data_ptr(), y.data_ptr(), cosb.data_ptr<float>(), sinb.data_ptr<float>(),
+                         doc_start.data_ptr<int>(), (int)ntok, (int)T, (int)nrot_heads, (int)ntot_heads, (int)Dh,
+                         inverse, cur_stream()),
+           "rope_doc");
+}
 static void rope(Tensor x, Tensor y, Tensor cosb, Tensor sinb, int64_t T, int64_t nrot_heads, int64_t ntot_heads,
                  int64_t Dh, bool inverse) {
   TORCH_CHECK(x.is_contiguous() && y.is_contiguous(), "rope: contiguous tensors expected");
@@ -1079,7 +1163,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_bwd", &flash_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("dqkv"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"),
         py::arg("cs_ws") = py::none(), py::arg("part") = py::none(), py::arg("qs") = 1);
+  m.def("flash_fwd_doc", &flash_fwd_doc);
+  m.def("flash_bwd_doc", &flash_bwd_doc, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("delta"), py::arg("dqkv"), py::arg("doc_start"), py::arg("doc_end"), py::arg("B"), py::arg("T"),
+        py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
+        py::arg("part") = py::none(), py::arg("qs") = 1);
+  m.def("doc_layout", &doc_layout);
+  m.def("synth_doc_flags", &synth_doc_flags);
   m.def("rope", &rope);
+  m.def("rope_doc", &rope_doc);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("im2col", &im2col);

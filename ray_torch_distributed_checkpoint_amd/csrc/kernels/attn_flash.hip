@@ -24,6 +24,14 @@
 //             in its prologue (bwd_dq runs first).
 // Requires T % 64 == 0 and Dh in {64, 128}.
 //
+// DOC = true (packed sequences, rtdc_flash_fwd_doc / rtdc_flash_bwd_doc): row q attends to the
+// keys doc_start[q] <= key <= q of its own document.  The query-row kernels (fwd, dQ) start the
+// key-tile loop at doc_start[first row of the block] / 64 and mask key < doc_start[q] on the
+// tiles that begin before the document of the wave's last row; the key-row kernels (dK/dV) use
+// the equivalent q >= doc_end[key] per key lane and end the query-tile loop with the document
+// of the block's last key.  Everything DOC adds is under `if constexpr (DOC)`: the plain
+// instantiations are the code they were (profiles/attn_doc_mask_isa.txt).
+//
 // Pipelining (all three loops): the streamed tiles (K/V for fwd and dQ; Q, dO and the 64
 // LSE / delta values of a query block for dK/dV) go through an NS-slot LDS ring with NS-1
 // tiles in flight.  Every streamed byte arrives by global_load_lds; the operands a wave keeps
@@ -67,6 +75,11 @@ struct Args {
   // part [qs][B*T][Hkv][2*Dh]; dkdv_reduce_kernel sums them in qsub order (deterministic)
   float* part;
   int qs;
+  // document layout of packed sequences (DOC kernels only; ops/attention.py DocLayout): int32
+  // [B, T], start[b, t] = first token of t's document, end[b, t] = one past its last.  Both are
+  // non-decreasing along t, constant within a document, start[t] <= t < end[t]; never validated
+  const int* doc_start;
+  const int* doc_end;
 };
 
 // column sums over a wave's 16 rows of its stored fragment values v (lane = row (lane & 15) x
@@ -181,6 +194,13 @@ __device__ __forceinline__ bf16x8 gload8(const bf16_t* p) { return *(const bf16x
 // the first use inside the DMA loop
 __device__ __forceinline__ void settle(const bf16x8& x) { asm volatile("" ::"v"(__builtin_bit_cast(f32x4, x))); }
 __device__ __forceinline__ void settle(float x) { asm volatile("" ::"v"(x)); }
+__device__ __forceinline__ void settle(int x) { asm volatile("" ::"v"(x)); }
+
+// DOC kernels: the running max starts at a large finite value, not -inf.  A row whose document
+// starts in a later key tile sees fully masked tiles first (every score -inf); with m = -inf the
+// probability exponent -inf * c - m and the rescale factor 2^(m - m) would both be NaN.  With a
+// finite start they are 2^-inf = 0 and 2^0 = 1, and the first live tile rescales by 2^-huge = 0.
+constexpr float M_INIT_DOC = -1e30f;
 
 // s_waitcnt vmcnt(n) for a wave-uniform runtime n: rounded DOWN to an encoded immediate
 // (waiting for more of the in-flight DMA than needed is always safe).
@@ -223,7 +243,7 @@ __device__ __forceinline__ f32x4 mfma(const bf16x8& a, const bf16x8& b, const f3
 }
 
 // ------------------------------------------------------------------------------ forward
-template <int DH, int NS>
+template <int DH, int NS, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
@@ -245,20 +265,30 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
   uint32_t troff[DH / 16];
   tr_lane_offsets<DH>(troff, lane);
   const int nkb = qb + 1;
+  // DOC: the first key tile any row of the block attends to (start is non-decreasing, so the
+  // block's first row has the minimum) - a scalar load, ahead of the prologue DMAs
+  int kb_lo = 0;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ]) / BKV;
 
 #define KT(s) (smem + (s) * TILE)
 #define VT(s) (smem + (NS + (s)) * TILE)
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
-    if (s < nkb) {
-      stage<DH>(base, W, s * BKV, kcol, KT(s), wave, lane);
-      stage<DH>(base, W, s * BKV, vcol, VT(s), wave, lane);
+    if (kb_lo + s < nkb) {
+      stage<DH>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
+      stage<DH>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
     }
   bf16x8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) qf[ks] = gload8(base + (long long)myq * W + qcol + ks * 32 + g * 8);
+  int mylo = 0;  // DOC: first key of this row's document
+  if constexpr (DOC) mylo = a.doc_start[(long long)b * a.T + myq];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) settle(qf[ks]);
+  if constexpr (DOC) settle(mylo);
+  // DOC: tiles that begin before the document of the wave's last row need the low mask
+  int wlo = 0;
+  if constexpr (DOC) wlo = __builtin_amdgcn_readlane(mylo, 15);
   step_barrier();
 
   f32x4 o[DT];
@@ -271,12 +301,12 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
   bf16x8 ones;
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = (short)0x3F80;
-  float m = -INFINITY;
+  float m = DOC ? M_INIT_DOC : -INFINITY;
 
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int cur = kb % NS;
+  for (int kb = kb_lo; kb < nkb; ++kb) {
+    const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
     if (kb + NS - 1 < nkb) {
-      const int nx = (kb + NS - 1) % NS;
+      const int nx = (kb - kb_lo + NS - 1) % NS;
       stage<DH>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
       stage<DH>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
     }
@@ -292,15 +322,24 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
     // causal mask on the diagonal block, running max of the raw scores (c > 0: scaling into the
     // log2 domain commutes with max, so it folds into one FMA per probability)
     float mx = -INFINITY;
-    const bool diag = (kb == qb);
+    // DOC: the tile also needs a mask when it begins before the document of the wave's last row
+    // (wave-uniform, like diag); keys before the row's document are masked like the keys after
+    // the row - both by ONE unsigned range test, key - mylo <= myq - mylo, so a DOC tile costs
+    // the compare the causal mask costs (the loop is VALU-issue bound)
+    const bool diag = (kb == qb) || (DOC && kb * BKV < wlo);
+    const int koff = kb * BKV + 4 * g - mylo;
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float v = s[t][r];
         if (diag) {
-          const int key = kb * BKV + 16 * t + 4 * g + r;
-          if (key > myq) v = -INFINITY;
+          if constexpr (DOC) {
+            if ((unsigned)(koff + 16 * t + r) > (unsigned)(myq - mylo)) v = -INFINITY;
+          } else {
+            const int key = kb * BKV + 16 * t + 4 * g + r;
+            if (key > myq) v = -INFINITY;
+          }
         }
         s[t][r] = v;
         mx = fmaxf(mx, v);
@@ -362,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
 // Forward, 32 query rows per wave (block = 128 rows): every K fragment read from LDS feeds
 // two S MFMAs and every V fragment two P.V MFMAs, halving LDS bytes per FLOP.  Same
 // accumulator-as-operand layout and the same DMA ring as fwd_kernel.
-template <int DH, int NS>
+template <int DH, int NS, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, QG = 2, BQ2 = 128, PER = DH / 16;
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
@@ -386,40 +425,57 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
   uint32_t troff[DH / 16];
   tr_lane_offsets<DH>(troff, lane);
   const int nkb = (qb + 1) * (BQ2 / BKV);
+  // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
+  int kb_lo = 0;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ2]) / BKV;
 
 #define KT(s) (smem + (s) * TILE)
 #define VT(s) (smem + (NS + (s)) * TILE)
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
-    if (s < nkb) {
-      stage<DH>(base, W, s * BKV, kcol, KT(s), wave, lane);
-      stage<DH>(base, W, s * BKV, vcol, VT(s), wave, lane);
+    if (kb_lo + s < nkb) {
+      stage<DH>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
+      stage<DH>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
     }
   bf16x8 qf[QG][KS];
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[qg][ks] = gload8(base + (long long)myq[qg] * W + qcol + ks * 32 + g * 8);
+  int mylo[QG], wlo[QG];  // DOC: first key of the row's document; that of each group's last row
+#pragma unroll
+  for (int qg = 0; qg < QG; ++qg) {
+    mylo[qg] = 0;
+    if constexpr (DOC) mylo[qg] = a.doc_start[(long long)b * a.T + myq[qg]];
+  }
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) settle(qf[qg][ks]);
+#pragma unroll
+  for (int qg = 0; qg < QG; ++qg) {
+    wlo[qg] = 0;
+    if constexpr (DOC) {
+      settle(mylo[qg]);
+      wlo[qg] = __builtin_amdgcn_readlane(mylo[qg], 15);
+    }
+  }
   step_barrier();
 
   f32x4 o[QG][DT];
   float m[QG], l[QG];
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg) {
-    m[qg] = -INFINITY;
+    m[qg] = DOC ? M_INIT_DOC : -INFINITY;
     l[qg] = 0.f;
 #pragma unroll
     for (int d = 0; d < DT; ++d) o[qg][d] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int cur = kb % NS;
+  for (int kb = kb_lo; kb < nkb; ++kb) {
+    const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
     if (kb + NS - 1 < nkb) {
-      const int nx = (kb + NS - 1) % NS;
+      const int nx = (kb - kb_lo + NS - 1) % NS;
       stage<DH>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
       stage<DH>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
     }
@@ -443,15 +499,23 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
       bf16x8 pp[QG][2];
 #pragma unroll
       for (int qg = 0; qg < QG; ++qg) {
+        // DOC: one unsigned range test masks the keys after the row and those before its
+        // document, on the tiles that meet either edge (wave-uniform; see fwd_kernel)
+        const bool edge = diag || (DOC && kb * BKV < wlo[qg]);
+        const int koff = kb * BKV + 4 * g - mylo[qg];
         float mx = -INFINITY;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float v = sc[qg][t][r];
-            if (diag) {
-              const int key = kb * BKV + 16 * t + 4 * g + r;
-              if (key > myq[qg]) v = -INFINITY;
+            if (edge) {
+              if constexpr (DOC) {
+                if ((unsigned)(koff + 16 * t + r) > (unsigned)(myq[qg] - mylo[qg])) v = -INFINITY;
+              } else {
+                const int key = kb * BKV + 16 * t + 4 * g + r;
+                if (key > myq[qg]) v = -INFINITY;
+              }
             }
             sc[qg][t][r] = v;
             mx = fmaxf(mx, v);
@@ -529,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
 // Ring slot = Q tile | dO tile | LSE[64] | delta[64] of one (q-head, q-block) step.  The 512 B
 // of row constants come by DMA as well (waves 0-1: LSE halves, waves 2-3: delta halves, 8
 // lanes x 16 B each), so every wave issues the same DH/16 + 1 DMA instructions per step.
-template <int DH, int NS>
+template <int DH, int NS, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2;
   constexpr int STG = 2 * TILE + 512, PER = DH / 16 + 1;
@@ -553,7 +617,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
   uint32_t troff[DH / 16];
   tr_lane_offsets<DH>(troff, lane);
 
-  const int nq = nkb - kb;      // q blocks at/after the diagonal
+  // q blocks at/after the diagonal; DOC: up to the block that holds the last row of the document
+  // of the block's last key (end is non-decreasing: the block maximum) - a scalar load, ahead of
+  // the prologue DMAs
+  int nq = nkb - kb;
+  if constexpr (DOC)
+    nq = (__builtin_amdgcn_readfirstlane(a.doc_end[(long long)b * a.T + kb * BKV + BKV - 1]) - 1) / BQ - kb + 1;
   const int total = nq * gper;  // steps over (q-head of this subset, q block)
   const float* rowsrc = wave < 2 ? (const float*)a.lse : a.delta;
   const int rowoff = 32 * (wave & 1) + 4 * (lane & 7);
@@ -577,10 +646,19 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
     kf[ks] = gload8(base + (long long)mykey * W + kcol + ks * 32 + g * 8);
     vf[ks] = gload8(base + (long long)mykey * W + vcol + ks * 32 + g * 8);
   }
+  // DOC: key < start[q] <=> q >= end[key], so the low bound of the query rows' documents is an
+  // upper bound on the query row per key lane - symmetric to the causal q < mykey
+  int myend = 0;
+  if constexpr (DOC) myend = a.doc_end[(long long)b * a.T + mykey];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     settle(kf[ks]);
     settle(vf[ks]);
+  }
+  int wend = 0;  // DOC: q tiles that reach the end of the document of the wave's first key need the mask
+  if constexpr (DOC) {
+    settle(myend);
+    wend = __builtin_amdgcn_readlane(myend, 0);
   }
   step_barrier();
 
@@ -622,6 +700,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (qb * BQ + 16 * t + 4 * g + r < mykey) p[t][r] = 0.f;
+    }
+    if constexpr (DOC) {
+      if (qb * BQ + BQ - 1 >= wend) {  // (wave-uniform) query rows of later documents
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (qb * BQ + 16 * t + 4 * g + r >= myend) p[t][r] = 0.f;
+      }
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -684,7 +771,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
 // §LDS).  Same ring, row-constant DMA and output contract (incl. the GQA head split).
 // (Dh = 128: 2 x 2 x 8 accumulators + 2 x 2 x 4 K / V fragments need the AGPR half of the
 // register file, so one wave per SIMD)
-template <int DH, int NS>
+template <int DH, int NS, bool DOC = false>
 __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a) {
   constexpr int KS = DH / 32, DT = DH / 16, DB = 2, TILE = 64 * DH * 2, KG = 2, BK2 = 128;
   constexpr int STG = 2 * TILE + 512, PER = DH / 16 + 1;
@@ -711,7 +798,10 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
   tr_lane_offsets<DH>(troff, lane);
 
   const int qb0 = kb * (BK2 / BQ);  // first q block that meets the block's keys
-  const int nq = nqb - qb0;
+  // DOC: the q-tile loop ends with the document of the block's last key (as bwd_dkdv_kernel)
+  int nq = nqb - qb0;
+  if constexpr (DOC)
+    nq = (__builtin_amdgcn_readfirstlane(a.doc_end[(long long)b * a.T + kb * BK2 + BK2 - 1]) - 1) / BQ - qb0 + 1;
   const int total = nq * gper;
   const float* rowsrc = wave < 2 ? (const float*)a.lse : a.delta;
   const int rowoff = 32 * (wave & 1) + 4 * (lane & 7);
@@ -737,6 +827,12 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
       kf[kg][ks] = gload8(base + (long long)mykey[kg] * W + kcol + ks * 32 + g * 8);
       vf[kg][ks] = gload8(base + (long long)mykey[kg] * W + vcol + ks * 32 + g * 8);
     }
+  int myend[KG], wend[KG];  // DOC: end of the key's document; that of each group's first key
+#pragma unroll
+  for (int kg = 0; kg < KG; ++kg) {
+    myend[kg] = 0;
+    if constexpr (DOC) myend[kg] = a.doc_end[(long long)b * a.T + mykey[kg]];
+  }
 #pragma unroll
   for (int kg = 0; kg < KG; ++kg)
 #pragma unroll
@@ -744,6 +840,14 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
       settle(kf[kg][ks]);
       settle(vf[kg][ks]);
     }
+#pragma unroll
+  for (int kg = 0; kg < KG; ++kg) {
+    wend[kg] = 0;
+    if constexpr (DOC) {
+      settle(myend[kg]);
+      wend[kg] = __builtin_amdgcn_readlane(myend[kg], 0);
+    }
+  }
   step_barrier();
 
   f32x4 dk[KG][DT], dv[KG][DT];
@@ -798,6 +902,17 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
 #pragma unroll
             for (int r = 0; r < 4; ++r)
               if (qb * BQ + 16 * t + 4 * g + r < mykey[kg]) p[kg][t][r] = 0.f;
+      }
+      if constexpr (DOC) {
+#pragma unroll
+        for (int kg = 0; kg < KG; ++kg)
+          if (qb * BQ + BQ - 1 >= wend[kg]) {  // (wave-uniform) query rows of later documents
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (qb * BQ + 16 * t + 4 * g + r >= myend[kg]) p[kg][t][r] = 0.f;
+          }
       }
       bf16x8 p0[KG], p1[KG], d0[KG], d1[KG];
 #pragma unroll
@@ -901,7 +1016,7 @@ __global__ __launch_bounds__(256) void dkdv_reduce_kernel(Args a) {
 }
 
 // ------------------------------------------------------------------------------ dQ
-template <int DH, int NS>
+template <int DH, int NS, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
@@ -923,14 +1038,17 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
   tr_lane_offsets<DH>(troff, lane);
   const long long r = (long long)bh * a.T + myq;
   const int nkb = qb + 1;
+  // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
+  int kb_lo = 0;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ]) / BKV;
 
 #define KT(s) (smem + (s) * TILE)
 #define VT(s) (smem + (NS + (s)) * TILE)
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
-    if (s < nkb) {
-      stage<DH, DH != 64>(base, W, s * BKV, kcol, KT(s), wave, lane);
-      stage<DH, DH != 64>(base, W, s * BKV, vcol, VT(s), wave, lane);
+    if (kb_lo + s < nkb) {
+      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
+      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
     }
   bf16x8 qf[KS], of[KS];
 #pragma unroll
@@ -945,6 +1063,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) ofw[ks] = gload8(a.out + ((long long)b * a.T + myq) * C + h * DH + ks * 32 + g * 8);
   const float lse2 = a.lse[r];
+  int mylo = 0;  // DOC: first key of this row's document
+  if constexpr (DOC) mylo = a.doc_start[(long long)b * a.T + myq];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     settle(qf[ks]);
@@ -952,6 +1072,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
     settle(ofw[ks]);
   }
   settle(lse2);
+  int wlo = 0;  // DOC: tiles that begin before the document of the wave's last row need the low mask
+  if constexpr (DOC) {
+    settle(mylo);
+    wlo = __builtin_amdgcn_readlane(mylo, 15);
+  }
   float dsum = 0.f;
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
@@ -966,10 +1091,10 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
 #pragma unroll
   for (int d = 0; d < DT; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int cur = kb % NS;
+  for (int kb = kb_lo; kb < nkb; ++kb) {
+    const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
     if (kb + NS - 1 < nkb) {
-      const int nx = (kb + NS - 1) % NS;
+      const int nx = (kb - kb_lo + NS - 1) % NS;
       stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
       stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
     }
@@ -998,6 +1123,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr)
           if (kb * BKV + 16 * t + 4 * g + rr > myq) ds[t][rr] = 0.f;
+    }
+    if constexpr (DOC) {
+      if (kb * BKV < wlo) {  // (wave-uniform) keys before the row's document
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr)
+            if (kb * BKV + 16 * t + 4 * g + rr < mylo) ds[t][rr] = 0.f;
+      }
     }
     const bf16x8 d0 = pack_pair(ds[0], ds[1]), d1 = pack_pair(ds[2], ds[3]);
 #pragma unroll
@@ -1034,7 +1168,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
 // transposed) feeds the MFMAs of two 16-row query groups, halving LDS bytes per MFMA of
 // bwd_dq_kernel - the change that took dK/dV from 130 to 82 us at GPT-2 shapes (bwd_dkdv2_kernel).
 // Same DMA ring, delta prologue, causal skip / mask and output contract.
-template <int DH, int NS>
+template <int DH, int NS, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
   constexpr int QG = 2, BQ2 = 128;
@@ -1059,17 +1193,21 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
   uint32_t troff[DH / 16];
   tr_lane_offsets<DH>(troff, lane);
   const int nkb = (qb + 1) * (BQ2 / BKV);
+  // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
+  int kb_lo = 0;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ2]) / BKV;
 
 #define KT(s) (smem + (s) * TILE)
 #define VT(s) (smem + (NS + (s)) * TILE)
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
-    if (s < nkb) {
-      stage<DH, DH != 64>(base, W, s * BKV, kcol, KT(s), wave, lane);
-      stage<DH, DH != 64>(base, W, s * BKV, vcol, VT(s), wave, lane);
+    if (kb_lo + s < nkb) {
+      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
+      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
     }
   bf16x8 qf[QG][KS], of[QG][KS], ofw[QG][KS];
   float lse2[QG];
+  int mylo[QG], wlo[QG];  // DOC: first key of the row's document; that of each group's last row
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg) {
 #pragma unroll
@@ -1079,6 +1217,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
       ofw[qg][ks] = gload8(a.out + ((long long)b * a.T + myq[qg]) * C + h * DH + ks * 32 + g * 8);
     }
     lse2[qg] = a.lse[(long long)bh * a.T + myq[qg]];
+    mylo[qg] = 0;
+    if constexpr (DOC) mylo[qg] = a.doc_start[(long long)b * a.T + myq[qg]];
   }
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg) {
@@ -1089,6 +1229,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
       settle(ofw[qg][ks]);
     }
     settle(lse2[qg]);
+    wlo[qg] = 0;
+    if constexpr (DOC) {
+      settle(mylo[qg]);
+      wlo[qg] = __builtin_amdgcn_readlane(mylo[qg], 15);
+    }
   }
   // delta = sum_d dO * O per row (the softmax-backward row term), stored for the dK/dV kernel
   float del[QG];
@@ -1110,10 +1255,10 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
 #pragma unroll
     for (int d = 0; d < DT; ++d) dq[qg][d] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int cur = kb % NS;
+  for (int kb = kb_lo; kb < nkb; ++kb) {
+    const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
     if (kb + NS - 1 < nkb) {
-      const int nx = (kb + NS - 1) % NS;
+      const int nx = (kb - kb_lo + NS - 1) % NS;
       stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
       stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
     }
@@ -1154,6 +1299,17 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr)
               if (kb * BKV + 16 * t + 4 * g + rr > myq[qg]) ds[qg][t][rr] = 0.f;
+      }
+      if constexpr (DOC) {
+#pragma unroll
+        for (int qg = 0; qg < QG; ++qg)
+          if (kb * BKV < wlo[qg]) {  // (wave-uniform) keys before the row's document
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int rr = 0; rr < 4; ++rr)
+                if (kb * BKV + 16 * t + 4 * g + rr < mylo[qg]) ds[qg][t][rr] = 0.f;
+          }
       }
       bf16x8 d0[QG], d1[QG];
 #pragma unroll
@@ -1216,12 +1372,16 @@ static int fa_xcd() {
 // 357 us - every extra slot costs a co-resident block per CU (32 / 48 / 64 KiB of LDS per
 // block), and at these 8-16-step loops occupancy hides more HBM latency than a deeper ring.
 // At Dh = 128 a third slot leaves one block per CU.
-#define FA_LAUNCH(KERNEL, DH, GRID, ARGS) hipLaunchKernelGGL((KERNEL<DH, 2>), GRID, dim3(256), 0, st, ARGS)
+#define FA_LAUNCH(KERNEL, DH, GRID, ARGS) hipLaunchKernelGGL((KERNEL<DH, 2, DOC>), GRID, dim3(256), 0, st, ARGS)
 
-extern "C" int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh,
-                              float scale, hipStream_t st) {
+// DOC = true: the document-masked kernels (doc_start / doc_end set); same dispatch
+template <bool DOC>
+static int flash_fwd_launch(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh, float scale,
+                            const int* doc_start, const int* doc_end, hipStream_t st) {
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
+  if (DOC && (doc_start == nullptr || doc_end == nullptr)) return 1;
   fa::Args a{};
+  a.doc_start = doc_start; a.doc_end = doc_end;
   a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)out; a.lse = lse;
   a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
   // measured (benchmarks/attn_bench.py, before the DMA ring): 32 rows/wave wins at Dh = 128
@@ -1242,12 +1402,25 @@ extern "C" int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int B, int
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+extern "C" int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh,
+                              float scale, hipStream_t st) {
+  return flash_fwd_launch<false>(qkv, out, lse, B, T, H, Hkv, Dh, scale, nullptr, nullptr, st);
+}
+
+// packed sequences: row (b, q) attends to keys doc_start[b, q] <= key <= q (doc_start / doc_end: fa::Args)
+extern "C" int rtdc_flash_fwd_doc(const void* qkv, void* out, float* lse, const int* doc_start, const int* doc_end,
+                                  int B, int T, int H, int Hkv, int Dh, float scale, hipStream_t st) {
+  return flash_fwd_launch<true>(qkv, out, lse, B, T, H, Hkv, Dh, scale, doc_start, doc_end, st);
+}
+
 // dQ (it also stores delta), then dK/dV (+ the GQA head-split reduction), all on `st`
-extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                              void* dqkv, int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws,
-                              float* part, int qs, hipStream_t st) {
+template <bool DOC>
+static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                            void* dqkv, int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws, float* part,
+                            int qs, const int* doc_start, const int* doc_end, hipStream_t st) {
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
   if (qs < 1 || (H / Hkv) % qs != 0 || (qs > 1 && part == nullptr) || ((Hkv * 2 * Dh) % 4) != 0) return 1;
+  if (DOC && (doc_start == nullptr || doc_end == nullptr)) return 1;
   // dQ first: it also computes the row terms delta = rowsum(dO * O) that dK/dV read
   fa::Args a{};
   a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)out; a.dout = (const bf16_t*)dout; a.lse = (float*)lse;
@@ -1256,6 +1429,7 @@ extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout
   a.cs_ws = cs_ws;
   a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
   a.part = part; a.qs = qs;
+  a.doc_start = doc_start; a.doc_end = doc_end;
   dim3 g1(T / 64, B * Hkv * qs), g2(T / 64, B * H);
   // dK/dV at Dh = 64: 32 keys per wave (bwd_dkdv2_kernel) unless RTDC_FA_DKDV=1 (16 keys per wave)
   const char* dkdv_env = getenv("RTDC_FA_DKDV");  // (read per call: tests A/B it in one process)
@@ -1291,4 +1465,18 @@ extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout
     else hipLaunchKernelGGL(fa::dkdv_reduce_kernel<128>, gr, dim3(256), 0, st, a);
   }
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                              void* dqkv, int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws,
+                              float* part, int qs, hipStream_t st) {
+  return flash_bwd_launch<false>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs, nullptr,
+                                 nullptr, st);
+}
+
+extern "C" int rtdc_flash_bwd_doc(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                                  void* dqkv, const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv,
+                                  int Dh, float scale, float* cs_ws, float* part, int qs, hipStream_t st) {
+  return flash_bwd_launch<true>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs, doc_start,
+                                doc_end, st);
 }

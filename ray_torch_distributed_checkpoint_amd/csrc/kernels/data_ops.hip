@@ -297,9 +297,74 @@ __global__ __launch_bounds__(256) void synth_tokens_kernel(const int64_t* __rest
   if (j > 0) tgt[b * T + j - 1] = tok;
 }
 
+// Document layout of packed sequences (ops/attention.py DocLayout): from the start flags of a
+// row, start[t] = the last flagged position <= t (a forward running maximum) and end[t] = the
+// first flagged position > t, or T (a backward running minimum).  Position 0 always starts a
+// document, so the outputs are a valid layout for any flags.  One block per row; thread i owns
+// the contiguous chunk [i * per, (i + 1) * per): chunk maximum / minimum -> LDS -> each thread
+// folds the chunks before / after its own -> second walk of the chunk writes both arrays.
+constexpr int DOC_NT = 256;
+
+__global__ __launch_bounds__(DOC_NT) void doc_layout_kernel(const uint8_t* __restrict__ flags, int T,
+                                                            int* __restrict__ start, int* __restrict__ end) {
+  __shared__ int cmax[DOC_NT], cmin[DOC_NT];
+  const long long row = (long long)blockIdx.x * T;
+  const uint8_t* f = flags + row;
+  const int per = (T + DOC_NT - 1) / DOC_NT;
+  const int lo = min(T, (int)threadIdx.x * per), hi = min(T, lo + per);
+  int mx = -1, mn = T;
+  for (int t = lo; t < hi; ++t)
+    if (t == 0 || f[t]) {
+      mx = t;
+      mn = min(mn, t);
+    }
+  cmax[threadIdx.x] = mx;
+  cmin[threadIdx.x] = mn;
+  __syncthreads();
+  int run = 0, nxt = T;
+  for (int i = 0; i < (int)threadIdx.x; ++i) run = max(run, cmax[i]);
+  for (int i = DOC_NT - 1; i > (int)threadIdx.x; --i) nxt = min(nxt, cmin[i]);
+  for (int t = lo; t < hi; ++t) {
+    if (t == 0 || f[t]) run = t;
+    start[row + t] = run;
+  }
+  for (int t = hi - 1; t >= lo; --t) {
+    end[row + t] = nxt;
+    if (t == 0 || f[t]) nxt = t;
+  }
+}
+
+// 1 where position p > 0 of synthetic sequence ids[b] starts a document (workloads.SyntheticTokens
+// doc_len = L): mix(ids[b] * (T + 1) + p, seed2) % L == 0 under the second seed constant
+__global__ __launch_bounds__(256) void synth_doc_flags_kernel(const int64_t* __restrict__ ids, int B, int T,
+                                                              long long doc_len, unsigned long long seed_add,
+                                                              uint8_t* __restrict__ flags) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)B * T) return;
+  const long long b = e / T, p = e - b * T;
+  const uint64_t x = (uint64_t)ids[b] * (uint64_t)(T + 1) + (uint64_t)p;
+  flags[e] = (p > 0 && mix31(x, seed_add) % (uint64_t)doc_len == 0) ? 1 : 0;
+}
+
 }  // namespace rtdc
 
 using namespace rtdc;
+
+// flags: uint8 [B, T] (non-zero = a document starts here); start / end: int32 [B, T]
+extern "C" int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st) {
+  if (B <= 0 || T <= 0) return 1;
+  hipLaunchKernelGGL(doc_layout_kernel, dim3((unsigned)B), dim3(DOC_NT), 0, st, flags, T, start, end);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_synth_doc_flags(const int64_t* ids, int B, int T, long long doc_len, unsigned long long seed_add,
+                                    uint8_t* flags, hipStream_t st) {
+  if (B <= 0 || T <= 0 || doc_len <= 0) return 1;
+  const long long n = (long long)B * T;
+  hipLaunchKernelGGL(synth_doc_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ids, B, T, doc_len,
+                     seed_add, flags);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
 
 // ws: 4 * n uint32 (two key/value ping-pong buffers).  nbits: bits of the largest id.
 extern "C" int rtdc_sort_ids(const int64_t* ids, int n, int nbits, uint32_t* ws, int64_t* sorted, int64_t* perm,

@@ -22,11 +22,12 @@ __device__ __forceinline__ void st8r(bf16_t* p, const float* v) {
 // HF "rotate_half" convention: (x1, x2) = halves of each head;
 //   fwd: y1 = x1 c - x2 s ; y2 = x2 c + x1 s        bwd (sign = -1): rotate by -theta.
 // One thread handles 8 pairs (i .. i+7) of one (token, head).  Heads [0, Hq+Hk) are rotated
-// (q and k), the V heads are copied, so `out` is the full packed tensor.
+// (q and k), the V heads are copied, so `out` is the full packed tensor.  doc_start (optional,
+// int32 [ntok]): the table row is t - doc_start[tok] instead of t.
 __global__ __launch_bounds__(256) void rope_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
                                                   const float* __restrict__ cosb, const float* __restrict__ sinb,
                                                   int ntok, int T, int nrot_heads, int ntot_heads, int Dh,
-                                                  float sign) {
+                                                  float sign, const int* __restrict__ doc_start) {
   const int half = Dh / 2, per_head = half / 8;
   const long long total = (long long)ntok * ntot_heads * per_head;
   for (long long w = blockIdx.x * 256LL + threadIdx.x; w < total; w += (long long)gridDim.x * 256) {
@@ -34,7 +35,8 @@ __global__ __launch_bounds__(256) void rope_kernel(const bf16_t* __restrict__ x,
     const long long th = w / per_head;
     const int head = (int)(th % ntot_heads);
     const long long tok = th / ntot_heads;
-    const int t = (int)(tok % T);
+    int t = (int)(tok % T);
+    if (doc_start) t -= doc_start[tok];  // packed sequences: the position restarts with each document
     const long long base = (tok * ntot_heads + head) * Dh;
     const int i0 = c8 * 8;
     float a[8], b[8];
@@ -111,13 +113,18 @@ static inline unsigned grid_of(long long work) {
   return (unsigned)b;
 }
 
-extern "C" int rtdc_rope(const void* x, void* y, const float* cosb, const float* sinb, int ntok, int T,
-                         int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st) {
+extern "C" int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, const int* doc_start,
+                             int ntok, int T, int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st) {
   if (Dh % 16 != 0) return 1;
   const long long work = (long long)ntok * ntot_heads * (Dh / 16);
   hipLaunchKernelGGL(rope_kernel, dim3(grid_of(work)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, cosb, sinb,
-                     ntok, T, nrot_heads, ntot_heads, Dh, inverse ? -1.f : 1.f);
+                     ntok, T, nrot_heads, ntot_heads, Dh, inverse ? -1.f : 1.f, doc_start);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_rope(const void* x, void* y, const float* cosb, const float* sinb, int ntok, int T,
+                         int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st) {
+  return rtdc_rope_doc(x, y, cosb, sinb, nullptr, ntok, T, nrot_heads, ntot_heads, Dh, inverse, st);
 }
 
 extern "C" int rtdc_swiglu_fwd(const void* gu, void* h, long long M, int F, hipStream_t st) {

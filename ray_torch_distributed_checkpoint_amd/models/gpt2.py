@@ -59,9 +59,9 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x, residual):
+    def forward(self, x, residual, docs=None):
         qkv = self.c_attn(x)
-        y = ops.causal_attention(qkv, self.n_head)
+        y = ops.causal_attention(qkv, self.n_head, docs=docs)
         return self.c_proj(y, residual=residual)
 
 
@@ -83,13 +83,13 @@ class Block(nn.Module):
         self.ln_2 = LayerNorm(cfg.n_embd, cfg.layer_norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, prev_bias=None):
+    def forward(self, x, prev_bias=None, docs=None):
         # the residual stream passes through each LayerNorm so its gradient is summed inside
         # the norm's backward kernel (no separate add of the two branches' gradients); that
         # kernel also reduces the bias gradient of the projection that wrote the stream
         # (prev_bias: the previous block's MLP c_proj, then this block's attention c_proj)
         h, x = self.ln_1(x, passthrough=True, grad_sum_into=prev_bias)
-        x = self.attn(h, residual=x)
+        x = self.attn(h, residual=x, docs=docs)
         h, x = self.ln_2(x, passthrough=True, grad_sum_into=self.attn.c_proj.bias)
         return self.mlp(h, residual=x)
 
@@ -123,11 +123,14 @@ class GPT2(nn.Module):
             n -= (self.cfg.padded_vocab - self.cfg.vocab_size) * self.cfg.n_embd
         return n
 
-    def forward(self, idx: torch.Tensor, targets: torch.Tensor | None = None):
+    def forward(self, idx: torch.Tensor, targets: torch.Tensor | None = None, docs=None):
+        """docs (ops.DocLayout, packed sequences): every block's attention is restricted to the
+        token's own document.  The learned `wpe` positions stay absolute (position t of the
+        row, not of the document): resetting them needs a different embedding backward."""
         x = ops.embedding(idx, self.wte, self.wpe)
         prev_bias = None
         for blk in self.h:
-            x = blk(x, prev_bias)
+            x = blk(x, prev_bias, docs)
             prev_bias = blk.mlp.c_proj.bias
         x = self.ln_f(x, grad_sum_into=prev_bias)
         if targets is not None:

@@ -67,11 +67,11 @@ class Attention(nn.Module):
         self.wqkv = nn.Parameter(torch.empty((cfg.n_heads + 2 * cfg.n_kv_heads) * hd, cfg.dim))
         self.wo = nn.Parameter(torch.empty(cfg.dim, cfg.n_heads * hd))
 
-    def forward(self, x, residual):
+    def forward(self, x, residual, docs=None):
         c = self.cfg
         qkv = ops.linear(x, self.wqkv)
-        qkv = apply_rope(qkv, c.n_heads, c.n_kv_heads, c.rope_theta)
-        y = ops.causal_attention(qkv, c.n_heads, c.n_kv_heads)
+        qkv = apply_rope(qkv, c.n_heads, c.n_kv_heads, c.rope_theta, docs=docs)
+        y = ops.causal_attention(qkv, c.n_heads, c.n_kv_heads, docs=docs)
         return ops.linear(y, self.wo, residual=residual)
 
 
@@ -93,9 +93,9 @@ class TransformerBlock(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x):
+    def forward(self, x, docs=None):
         h, x = self.attention_norm(x, passthrough=True)
-        x = self.attention(h, residual=x)
+        x = self.attention(h, residual=x, docs=docs)
         h, x = self.ffn_norm(x, passthrough=True)
         return self.feed_forward(h, residual=x)
 
@@ -129,10 +129,12 @@ class Llama(nn.Module):
         pad = (self.cfg.padded_vocab - self.cfg.vocab_size) * self.cfg.dim * 2
         return sum(p.numel() for p in self.parameters()) - pad
 
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, docs=None):
+        """docs (ops.DocLayout, packed sequences): in every block the rotary positions restart
+        with each document and attention is restricted to the token's own document."""
         x = ops.embedding(idx, self.tok_embeddings)
         for blk in self.layers:
-            x = blk(x)
+            x = blk(x, docs)
         x = self.norm(x)
         if targets is not None:
             return ops.lm_head_cross_entropy(x, self.output, targets, self.cfg.vocab_size)

@@ -109,18 +109,108 @@ class _CausalAttention(torch.autograd.Function):
         return dqkv, None, None, None, None, None
 
 
+class DocLayout:
+    """Document layout of packed sequences: each row of `T` tokens is a concatenation of
+    documents and a token attends only to earlier tokens of its own document.
+
+    Two contiguous int32 [B, T] tensors: `start[b, t]` = index of the first token of t's document,
+    `end[b, t]` = one past its last.  Every constructor goes through start flags - a position
+    starts a document iff it is 0 or flagged; `start` is the running maximum of the flagged
+    positions and `end` the reverse running minimum of the next one (or T) - so the arrays are
+    valid for any input: both non-decreasing along t, constant within a document, and
+    start[t] <= t < end[t].  The attention kernels rely on that and never validate or clamp.
+    Build it once per batch; every layer shares it.  On the GPU the flags -> (start, end) step is
+    one native launch (`data_ops.hip` doc_layout_kernel); the CPU path is the same scans in torch.
+    """
+
+    __slots__ = ("start", "end")
+
+    def __init__(self, start: torch.Tensor, end: torch.Tensor):
+        self.start, self.end = start, end
+
+    @property
+    def device(self):
+        return self.start.device
+
+    @property
+    def shape(self):
+        return tuple(self.start.shape)
+
+    def to(self, device) -> "DocLayout":
+        return DocLayout(self.start.to(device), self.end.to(device))
+
+    @classmethod
+    def from_flags(cls, flags: torch.Tensor) -> "DocLayout":
+        """flags: [B, T], non-zero where a document starts (position 0 always does)."""
+        if flags.dim() != 2:
+            raise ValueError("DocLayout: start flags must be [B, T]")
+        B, T = flags.shape
+        f = (flags != 0).to(torch.uint8).contiguous()
+        start = torch.empty((B, T), dtype=torch.int32, device=f.device)
+        end = torch.empty_like(start)
+        if f.is_cuda:
+            gpu_ext().doc_layout(f, start, end)
+            return cls(start, end)
+        pos = torch.arange(T, dtype=torch.int64, device=f.device).expand(B, T)
+        fb = f.bool().clone()
+        fb[:, 0] = True
+        st = torch.cummax(torch.where(fb, pos, torch.zeros_like(pos)), dim=1).values
+        # the next start strictly after t: reverse running minimum of the flagged positions > t
+        nxt = torch.where(fb, pos, torch.full_like(pos, T))
+        nxt = torch.cat([nxt[:, 1:], torch.full((B, 1), T, dtype=torch.int64, device=f.device)], dim=1)
+        en = torch.flip(torch.cummin(torch.flip(nxt, dims=[1]), dim=1).values, dims=[1])
+        return cls(st.to(torch.int32).contiguous(), en.to(torch.int32).contiguous())
+
+    @classmethod
+    def from_lengths(cls, lengths, T: int, device=None) -> "DocLayout":
+        """lengths: one list of document lengths per row, each summing to T."""
+        flags = torch.zeros((len(lengths), T), dtype=torch.uint8)
+        for b, row in enumerate(lengths):
+            if any(int(n) <= 0 for n in row) or sum(int(n) for n in row) != T:
+                raise ValueError(f"DocLayout.from_lengths: row {b} lengths must be positive and sum to {T}")
+            at = 0
+            for n in row:
+                flags[b, at] = 1
+                at += int(n)
+        return cls.from_flags(flags.to(device) if device is not None else flags)
+
+    @classmethod
+    def from_eos(cls, tokens: torch.Tensor, eos_id: int) -> "DocLayout":
+        """The token after an EOS starts a document; position 0 always starts one."""
+        flags = torch.zeros(tokens.shape, dtype=torch.uint8, device=tokens.device)
+        flags[:, 1:] = (tokens[:, :-1] == eos_id).to(torch.uint8)
+        return cls.from_flags(flags)
+
+    @classmethod
+    def from_doc_start(cls, t: torch.Tensor) -> "DocLayout":
+        """t[b, i] = index of the first token of i's document.  Position i counts as a start iff
+        t[b, i] == i, so an input that is not a valid layout still yields a valid one."""
+        pos = torch.arange(t.shape[1], device=t.device, dtype=t.dtype)
+        return cls.from_flags(t == pos[None, :])
+
+    def mask(self) -> torch.Tensor:
+        """Boolean [B, T, T]: query q may attend to key k iff start[q] <= k <= q."""
+        T = self.start.shape[1]
+        k = torch.arange(T, device=self.start.device)
+        return (k[None, None, :] >= self.start[:, :, None].long()) & (k[None, None, :] <= k[None, :, None])
+
+
 class _FlashAttention(torch.autograd.Function):
     """Fused causal flash attention (csrc/kernels/attn_flash.hip): no T x T matrix in HBM."""
 
     @staticmethod
-    def forward(ctx, qkv, B, T, H, Hkv, Dh):
+    def forward(ctx, qkv, B, T, H, Hkv, Dh, docs=None):
         qkv = qkv.contiguous()
         out = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B * H, T), dtype=torch.float32, device=qkv.device)
         scale = 1.0 / math.sqrt(Dh)
-        gpu_ext().flash_fwd(qkv, out, lse, B, T, H, Hkv, Dh, scale)
+        if docs is None:
+            gpu_ext().flash_fwd(qkv, out, lse, B, T, H, Hkv, Dh, scale)
+        else:
+            gpu_ext().flash_fwd_doc(qkv, out, lse, docs.start, docs.end, B, T, H, Hkv, Dh, scale)
         ctx.save_for_backward(qkv, out, lse)
         ctx.dims = (B, T, H, Hkv, Dh, scale)
+        ctx.docs = docs  # (int32 layout tensors: no gradient, shared by every layer of the step)
         return out
 
     @staticmethod
@@ -136,10 +226,15 @@ class _FlashAttention(torch.autograd.Function):
         qs = _dkdv_head_split(B, T, H, Hkv, qkv.device)
         part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device=qkv.device) if qs > 1 else None
         dout = dout.contiguous()
-        gpu_ext().flash_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs)
+        docs = ctx.docs
+        if docs is None:
+            gpu_ext().flash_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs)
+        else:
+            gpu_ext().flash_bwd_doc(qkv, out, dout, lse, delta, dqkv, docs.start, docs.end, B, T, H, Hkv, Dh, scale,
+                                    cs, part, qs)
         if cs is not None:
             G.offer_colsum_partials(dqkv, cs)
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 def _dkdv_head_split(B: int, T: int, H: int, Hkv: int, device) -> int:
@@ -166,7 +261,7 @@ def flash_supported(T: int, Dh: int) -> bool:
     return T % 64 == 0 and Dh in (64, 128)
 
 
-def causal_attention_ref(qkv, B, T, H, Hkv, Dh):
+def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None):
     C = H * Dh
     q = qkv[..., :C].reshape(B, T, H, Dh).transpose(1, 2)
     k = qkv[..., C:C + Hkv * Dh].reshape(B, T, Hkv, Dh).transpose(1, 2)
@@ -174,20 +269,37 @@ def causal_attention_ref(qkv, B, T, H, Hkv, Dh):
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=1)
         v = v.repeat_interleave(H // Hkv, dim=1)
-    o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+    if docs is None:
+        o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+    else:  # boolean mask start[q] <= key <= q: the oracle of the document-masked kernels
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=docs.mask()[:, None])
     return o.transpose(1, 2).reshape(B, T, C)
 
 
-def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = None) -> torch.Tensor:
-    """qkv: [B, T, (H + 2*Hkv) * Dh] -> [B, T, H*Dh]."""
+def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = None,
+                     docs: DocLayout | None = None) -> torch.Tensor:
+    """qkv: [B, T, (H + 2*Hkv) * Dh] -> [B, T, H*Dh].  docs (packed sequences): row q attends to
+    the keys start[q] <= key <= q of its own document only; it needs the flash path - there is
+    no unmasked fallback."""
     B, T, W = qkv.shape
     Hkv = n_kv_head or n_head
     Dh = W // (n_head + 2 * Hkv)
+    if docs is not None:
+        if docs.shape != (B, T):
+            raise ValueError(f"causal_attention: docs layout is {docs.shape}, qkv is [{B}, {T}, ...]")
+        if docs.device != qkv.device:
+            raise ValueError(f"causal_attention: docs on {docs.device}, qkv on {qkv.device}")
     if qkv.is_cuda:
         require_dtype(qkv, "causal_attention")
     else:
-        return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh)
+        return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh, docs)
     impl = os.environ.get("RTDC_ATTN", "flash")
+    if docs is not None:
+        if impl != "flash" or not flash_supported(T, Dh):
+            raise RuntimeError(
+                f"causal_attention: document masking needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
+                f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
+        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs)
     if impl == "flash" and flash_supported(T, Dh):
         return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh)
     return _CausalAttention.apply(qkv, B, T, n_head, Hkv, Dh)

@@ -24,28 +24,37 @@ def rope_tables(T: int, Dh: int, theta: float, device) -> tuple[torch.Tensor, to
     return t
 
 
-def rope_ref(qkv: torch.Tensor, H: int, Hkv: int, theta: float) -> torch.Tensor:
+def rope_ref(qkv: torch.Tensor, H: int, Hkv: int, theta: float, docs=None) -> torch.Tensor:
+    """docs (ops.DocLayout): the position restarts with each document (table row t - start[b, t])."""
     B, T, W = qkv.shape
     Dh = W // (H + 2 * Hkv)
     cos, sin = rope_tables(T, Dh, theta, qkv.device)
     x = qkv.view(B, T, H + 2 * Hkv, Dh)
     rot = x[:, :, : H + Hkv].float()
     x1, x2 = rot[..., : Dh // 2], rot[..., Dh // 2:]
-    c, s = cos[None, :, None, :], sin[None, :, None, :]
+    if docs is None:
+        c, s = cos[None, :, None, :], sin[None, :, None, :]
+    else:
+        pos = torch.arange(T, device=qkv.device)[None, :] - docs.start.long()
+        c, s = cos[pos][:, :, None, :], sin[pos][:, :, None, :]
     out = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(qkv.dtype)
     return torch.cat([out, x[:, :, H + Hkv:]], dim=2).view(B, T, W)
 
 
 class _RoPE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, H, Hkv, theta):
+    def forward(ctx, qkv, H, Hkv, theta, docs=None):
         B, T, W = qkv.shape
         Dh = W // (H + 2 * Hkv)
         cos, sin = rope_tables(T, Dh, theta, qkv.device)
         x = qkv.contiguous()
         y = torch.empty_like(x)
-        gpu_ext().rope(x, y, cos, sin, T, H + Hkv, H + 2 * Hkv, Dh, False)
+        if docs is None:
+            gpu_ext().rope(x, y, cos, sin, T, H + Hkv, H + 2 * Hkv, Dh, False)
+        else:
+            gpu_ext().rope_doc(x, y, cos, sin, docs.start, T, H + Hkv, H + 2 * Hkv, Dh, False)
         ctx.meta = (T, H, Hkv, Dh, cos, sin)
+        ctx.docs = docs
         return y
 
     @staticmethod
@@ -53,16 +62,24 @@ class _RoPE(torch.autograd.Function):
         T, H, Hkv, Dh, cos, sin = ctx.meta
         d = dy.contiguous()
         dx = torch.empty_like(d)
-        gpu_ext().rope(d, dx, cos, sin, T, H + Hkv, H + 2 * Hkv, Dh, True)
-        return dx, None, None, None
+        if ctx.docs is None:
+            gpu_ext().rope(d, dx, cos, sin, T, H + Hkv, H + 2 * Hkv, Dh, True)
+        else:
+            gpu_ext().rope_doc(d, dx, cos, sin, ctx.docs.start, T, H + Hkv, H + 2 * Hkv, Dh, True)
+        return dx, None, None, None, None
 
 
-def apply_rope(qkv: torch.Tensor, n_head: int, n_kv_head: int, theta: float = 500000.0) -> torch.Tensor:
+def apply_rope(qkv: torch.Tensor, n_head: int, n_kv_head: int, theta: float = 500000.0, docs=None) -> torch.Tensor:
+    """docs (ops.DocLayout, packed sequences): positions restart with each document, in the
+    forward and in the inverse rotation of the backward."""
+    if docs is not None and (docs.shape != tuple(qkv.shape[:2]) or docs.device != qkv.device):
+        raise ValueError(f"apply_rope: docs layout {docs.shape} on {docs.device} does not match qkv "
+                         f"{tuple(qkv.shape)} on {qkv.device}")
     if qkv.is_cuda:
         require_dtype(qkv, "apply_rope")
     else:
-        return rope_ref(qkv, n_head, n_kv_head, theta)
-    return _RoPE.apply(qkv, n_head, n_kv_head, theta)
+        return rope_ref(qkv, n_head, n_kv_head, theta, docs)
+    return _RoPE.apply(qkv, n_head, n_kv_head, theta, docs)
 
 
 class _SwiGLUMLP(torch.autograd.Function):

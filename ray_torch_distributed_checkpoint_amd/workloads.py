@@ -46,6 +46,7 @@ from . import ops
 from . import train
 from .checkpoint import dcp
 from .checkpoint.state_dict import get_state_dict, set_state_dict
+from .ops.xent import IGNORE_INDEX
 from .optim import FusedAdamW, FusedSGD
 from .parallel.sampler import DistributedSampler
 from .utils.profiling import phase
@@ -68,6 +69,7 @@ class WorkloadConfig:
     async_checkpoint: Optional[bool] = None  # None -> CheckpointConfig.async_checkpoint
     num_classes: int = 10
     max_grad_norm: Optional[float] = None  # clip the global gradient norm inside the fused step (None / 0: off)
+    doc_len: Optional[int] = None  # LMs: packed sequences of documents of this mean length (None / 0: off)
 
     @classmethod
     def from_dict(cls, d: dict) -> "WorkloadConfig":
@@ -91,19 +93,52 @@ def _defaults(name: str):
 
 
 # ---------------------------------------------------------------------------------- data
-def _mix(x: torch.Tensor, seed: int) -> torch.Tensor:
-    """Deterministic integer hash (values stay < 2^31: no signed overflow on any device)."""
-    x = (x + (seed * 7919 + 1)) & 0x7FFFFFFF
+def _mix_add(x: torch.Tensor, add: int) -> torch.Tensor:
+    """Deterministic integer hash of x + add (values stay < 2^31: no signed overflow on any
+    device); `data_ops.hip` mix31 is the same function."""
+    x = (x + add) & 0x7FFFFFFF
     for _ in range(3):
         x = ((x ^ (x >> 13)) * 1103515245 + 12345) & 0x7FFFFFFF
     return x
 
 
-class SyntheticTokens:
-    """`n` sequences of `seq_len + 1` random tokens; sequence i is a function of (seed, i)."""
+def _mix(x: torch.Tensor, seed: int) -> torch.Tensor:
+    """The token hash: `_mix_add` under the first seed constant."""
+    return _mix_add(x, seed * 7919 + 1)
 
-    def __init__(self, n: int, seq_len: int, vocab: int, seed: int = 0):
+
+class SyntheticTokens:
+    """`n` sequences of `seq_len + 1` random tokens; sequence i is a function of (seed, i).
+
+    doc_len = L packs documents into each sequence: position p > 0 of sequence i starts a
+    document iff `_mix_add` of (i, p) under a second seed constant is 0 mod L (mean length L).  The
+    layout is stateless - a function of (seed, i, p) - so exact resume needs no new state.
+    `batch()` then returns (inputs, targets, docs) with the target of each document's last token
+    IGNORE_INDEX (the next token belongs to another document)."""
+
+    def __init__(self, n: int, seq_len: int, vocab: int, seed: int = 0, doc_len: int | None = None):
         self.n, self.seq_len, self.vocab, self.seed = n, seq_len, vocab, seed
+        self.doc_len = int(doc_len) if doc_len else None
+
+    def _doc_seed_add(self) -> int:
+        return self.seed * 104729 + 17  # (tokens: seed * 7919 + 1)
+
+    def _docs(self, idx: torch.Tensor, tgt: torch.Tensor):
+        """(targets with document ends ignored, DocLayout) of the sequences idx."""
+        B, T = tgt.shape
+        if idx.is_cuda:
+            from .ops._ext import gpu_ext
+
+            flags = torch.empty((B, T), dtype=torch.uint8, device=idx.device)
+            gpu_ext().synth_doc_flags(idx.to(torch.int64).contiguous(), flags, self.doc_len, self._doc_seed_add())
+        else:
+            pos = torch.arange(T, device=idx.device, dtype=torch.int64)
+            h = _mix_add(idx.to(torch.int64)[:, None] * (T + 1) + pos, self._doc_seed_add())
+            flags = ((h % self.doc_len == 0) & (pos > 0)[None, :]).to(torch.uint8)
+        docs = ops.DocLayout.from_flags(flags)
+        pos = torch.arange(T, device=idx.device, dtype=torch.int32)
+        last = docs.end == (pos + 1)[None, :]
+        return tgt.masked_fill(last, IGNORE_INDEX), docs
 
     def __len__(self):
         return self.n
@@ -119,9 +154,13 @@ class SyntheticTokens:
             inp = torch.empty((B, self.seq_len), dtype=torch.int64, device=idx.device)
             tgt = torch.empty_like(inp)
             gpu_ext().synth_tokens(ids, inp, tgt, self.vocab, self.seed * 7919 + 1)
+            if self.doc_len:
+                return (inp, *self._docs(ids, tgt))
             return inp, tgt
         pos = torch.arange(self.seq_len + 1, device=idx.device, dtype=torch.int64)
         tok = _mix(idx.to(torch.int64)[:, None] * (self.seq_len + 1) + pos, self.seed) % self.vocab
+        if self.doc_len:
+            return (tok[:, :-1].contiguous(), *self._docs(idx, tok[:, 1:].contiguous()))
         return tok[:, :-1].contiguous(), tok[:, 1:].contiguous()
 
 
@@ -221,8 +260,10 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     else:
         raise ValueError(f"unknown workload model {name!r}")
     opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=clip)
-    data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed)
-    return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S, lambda net, x, y: net(x, y))
+    data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed, doc_len=cfg.doc_len or None)
+    # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle)
+    return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S,
+                    lambda net, x, y, docs=None: net(x, y) if docs is None else net(x, y, docs))
 
 
 # ---------------------------------------------------------------------------------- RNG state
@@ -382,9 +423,9 @@ def train_loop_per_worker(config: dict):
     t_last, n_last = time.perf_counter(), 0
     for step in range(start, cfg.steps):
         train.report_progress(step)
-        x, y = stream.next()
+        batch = stream.next()  # (x, y), or (x, y, docs) for packed sequences (doc_len)
         with phase("fwd"):
-            loss = wl.loss_fn(net, x, y)
+            loss = wl.loss_fn(net, *batch)
         with phase("bwd"):
             loss.backward()
         with phase("opt"):
@@ -449,17 +490,20 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    max_failures: int = 0, seed: int = 1234, grad_comm_dtype: str = "fp32",
                    bucket_cap_mb: float = 32.0, zero_stage: int = -1, progress_timeout_s: float | None = 300.0,
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
-                   report_every_n_steps: int | None = None, max_grad_norm: float | None = None):
+                   report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
+                   doc_len: int | None = None):
     """`train_fashion_mnist`'s counterpart for the bf16 workloads (R/my_ray_module.py:216-251).
     zero_stage -1: `default_zero_stage(model, num_workers)`.  max_grad_norm: clip the global
     gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
-    `grad_norm` / `grad_norms` (pre-clip)."""
+    `grad_norm` / `grad_norms` (pre-clip).  doc_len (LMs): train on packed sequences of synthetic
+    documents of that mean length, attention and RoPE positions restricted to each document
+    (None / 0: off; the report rows are unchanged)."""
     if zero_stage < 0:
         zero_stage = default_zero_stage(model, num_workers)
     cfg = WorkloadConfig(model=model, steps=steps, batch_size_per_worker=batch_size_per_worker, seq_len=seq_len,
                          lr=lr, ckpt_every_n_steps=ckpt_every_n_steps, seed=seed, resume_mode=resume_mode,
                          checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
-                         max_grad_norm=max_grad_norm or None)
+                         max_grad_norm=max_grad_norm or None, doc_len=doc_len or None)
     run_config = train.RunConfig(
         name=name, storage_path=checkpoint_storage_path, verbose=verbose,
         checkpoint_config=train.CheckpointConfig(num_to_keep=num_checkpoints_to_keep,
@@ -491,12 +535,15 @@ def main(argv=None):
                     help="-1: ZeRO-1 for llama* at more than one worker, else replicated")
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="clip the global gradient norm inside the fused optimizer step (default: off)")
+    ap.add_argument("--doc-len", type=int, default=None,
+                    help="LMs: packed sequences of synthetic documents of this mean length, attention and "
+                         "RoPE positions per document (default: off)")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
     use_gpu = torch.cuda.is_available() and not a.cpu
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
-                         zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm)
+                         zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len)
     print(res)
 
 

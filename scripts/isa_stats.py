@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Per-kernel resource figures from the device assembly hipcc keeps with -save-temps.
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -I <csrc> -save-temps -c attn_flash.hip -o /tmp/x.o
+    python scripts/isa_stats.py attn_flash-hip-amdgcn-amd-amdhsa-gfx950.s [other.s]
+
+One row per kernel: VGPR / AGPR / SGPR counts, LDS bytes, scratch bytes (from the amdhsa
+metadata) and the number of instructions in its body.  With two files (parent build, new build)
+the kernels present in both are printed side by side and the rows that differ are flagged - the
+evidence that a template parameter added for a new instantiation left the existing ones alone.
+"""
+from __future__ import annotations
+
+import re
+import subprocess
+import sys
+
+FIELDS = (("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_count"),
+          ("lds", ".group_segment_fixed_size"), ("scratch", ".private_segment_fixed_size"))
+
+
+def demangle(names):
+    try:
+        out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout
+        return dict(zip(names, out.splitlines()))
+    except (OSError, subprocess.CalledProcessError):
+        return {n: n for n in names}
+
+
+def parse(path):
+    text = open(path).read().splitlines()
+    stats, cur = {}, None
+    # amdhsa.kernels metadata: one "- .agpr_count:" ... ".name:" block per kernel
+    for ln in text:
+        s = ln.strip()
+        if s.startswith("- .agpr_count:") or s.startswith("- .args:"):
+            cur = {}
+        if cur is None:
+            continue
+        for key, tag in FIELDS:
+            m = re.match(r"(?:- )?%s:\s+(\d+)" % re.escape(tag), s)
+            if m:
+                cur[key] = int(m.group(1))
+        m = re.match(r"\.name:\s+(\S+)", s)
+        if m:
+            stats[m.group(1)] = cur
+        if s.startswith(".wavefront_size:"):
+            cur = None
+    # instruction counts: lines of the body that are neither labels, directives nor comments
+    for name in stats:
+        n, inside = 0, False
+        for ln in text:
+            if ln.startswith(name + ":"):
+                inside = True
+                continue
+            if inside:
+                s = ln.strip()
+                if s.startswith(".Lfunc_end"):
+                    break
+                if s and not s.startswith((".", ";")) and not s.endswith(":"):
+                    n += 1
+        stats[name]["insts"] = n
+    return stats
+
+
+def short(d):
+    d = re.sub(r"^void rtdc::fa::", "", d)
+    return re.sub(r"\(rtdc::fa::Args\)$", "", d)
+
+
+def main(argv):
+    if not 1 <= len(argv) <= 2:
+        print(__doc__)
+        return 2
+    tabs = [parse(p) for p in argv]
+    # key by the demangled name; a defaulted trailing `false` template argument (the parent's
+    # kernel<DH, NS> is the new kernel<DH, NS, false>) names the same kernel
+    for i, t in enumerate(tabs):
+        d = demangle(sorted(t))
+        tabs[i] = {re.sub(r", false>", ">", d[k]): v for k, v in t.items()}
+    names = sorted(set().union(*tabs))
+    dm = {n: n for n in names}
+    cols = [k for k, _ in FIELDS] + ["insts"]
+    print("%-52s %s" % ("kernel", "  ".join("%-15s" % c if len(tabs) == 2 else "%7s" % c for c in cols)))
+    bad = 0
+    for n in sorted(names, key=lambda x: dm[x]):
+        rows = [t.get(n) for t in tabs]
+        if len(tabs) == 1:
+            print("%-52s %s" % (short(dm[n]), "  ".join("%7d" % rows[0].get(c, -1) for c in cols)))
+            continue
+        cells, diff = [], False
+        for c in cols:
+            a = rows[0].get(c, -1) if rows[0] else None
+            b = rows[1].get(c, -1) if rows[1] else None
+            diff |= a is not None and b is not None and a != b
+            cells.append("%-15s" % ("%s -> %s" % ("-" if a is None else a, "-" if b is None else b)))
+        bad += diff
+        print("%-52s %s%s" % (short(dm[n]), "  ".join(cells), "   DIFFERS" if diff else ""))
+    if len(tabs) == 2:
+        print("kernels in both builds that differ: %d" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

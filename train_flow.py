@@ -54,6 +54,9 @@ class RayTorchTrain(FlowSpec):
     max_grad_norm = Parameter("max_grad_norm", default=0.0,
                               help="bf16 workloads: clip the global gradient norm inside the fused optimizer step "
                                    "(0: off)")
+    doc_len = Parameter("doc_len", default=0,
+                        help="LM workloads: packed sequences of synthetic documents of this mean length, attention "
+                             "and RoPE positions per document (0: off)")
     batch_size_per_worker = Parameter("batch_size_per_worker", default=0,
                                       help="bf16 workloads: samples per worker per step (0: the model's default). "
                                            "--batch_size is the reference MLP's global batch")
@@ -110,7 +113,7 @@ class RayTorchTrain(FlowSpec):
                 resume_mode=mode, max_failures=int(self.max_failures), grad_comm_dtype=self.grad_comm_dtype,
                 zero_stage=int(self.zero_stage),
                 report_every_n_steps=int(self.report_every_n_steps) or None,
-                max_grad_norm=float(self.max_grad_norm) or None)
+                max_grad_norm=float(self.max_grad_norm) or None, doc_len=int(self.doc_len) or None)
         self.next(self.join)
 
     @step

@@ -616,6 +616,8 @@ def load(state_dict: dict, checkpoint_id: str, process_group=None, *, broadcast:
         mdt = md.state_dict_metadata[k]
         if tuple(mdt.size) != tuple(dest.shape):
             raise ValueError(f"{k}: checkpoint shape {tuple(mdt.size)} != destination {tuple(dest.shape)}")
+        if mdt.properties.dtype != dest.dtype:  # (never cast or reinterpret: e.g. bf16 optimizer state)
+            raise ValueError(f"{k}: checkpoint dtype {mdt.properties.dtype} != destination {dest.dtype}")
         for idx, info in chunks_of[k]:
             need.append((k, idx, info, os.path.join(checkpoint_id, info.relative_path)))
     recs = _data_records([(path, info.offset, info.length) for _k, _i, info, path in need], threads)
@@ -630,7 +632,7 @@ def load(state_dict: dict, checkpoint_id: str, process_group=None, *, broadcast:
     # device destinations whose region is one contiguous run of the same dtype stream straight
     # from the file: native pread -> pinned ring -> H2D on the engine's copy stream, pipelined
     # (torchsave.get_engine().read_to_device); anything else (host destinations, resharded
-    # chunks, dtype casts) goes through a pinned staging buffer + copy_
+    # chunks) goes through a pinned staging buffer + copy_
     direct: dict[str, tuple[list, list, list]] = {}
     staged = []
     for r in reqs:

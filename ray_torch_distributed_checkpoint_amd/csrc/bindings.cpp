@@ -43,6 +43,10 @@ int rtdc_xent(const void* logits, void* dlogits, const int64_t* target, float* l
 int rtdc_adamw(const void* chunks, int nchunks, float* p, const float* g, float* m, float* v, void* shadow,
                float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
                float grad_scale, const int* skip, const float* clip, hipStream_t st);
+int rtdc_adamw_bf16state(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v, void* shadow,
+                        float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                        float grad_scale, const int* skip, const float* clip, unsigned long long seed,
+                        unsigned long long step, hipStream_t st);
 int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow, float lr,
              float momentum, float dampening, float wd, int nesterov, int first, float grad_scale,
              const int* skip, const float* clip, hipStream_t st);
@@ -385,10 +389,28 @@ static void check_chunks(const Tensor& chunks, int64_t nchunks, const char* op) 
                   chunks.size(1) == 3 && chunks.size(0) >= nchunks,
               op, ": chunk table must be a contiguous int64 [n, 3] GPU tensor");
 }
+// dispatches on the state dtype: fp32 m / v -> adamw_kernel; bf16 m / v -> adamw_bf16state_kernel
+// (stored state rounded stochastically with Philox bits keyed by (seed, step, flat index))
 static void adamw(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, Tensor m, Tensor v,
                   c10::optional<Tensor> shadow, double lr, double b1, double b2, double eps, double wd, double bc1,
-                  double bc2_sqrt, double grad_scale, int64_t skip_ptr, int64_t clip_ptr) {
+                  double bc2_sqrt, double grad_scale, int64_t skip_ptr, int64_t clip_ptr, uint64_t seed,
+                  int64_t step) {
   check_chunks(chunks, nchunks, "adamw");
+  TORCH_CHECK(m.scalar_type() == v.scalar_type(), "adamw: exp_avg is ", m.scalar_type(), " but exp_avg_sq is ",
+              v.scalar_type());
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "adamw: fp32 parameters and gradients");
+  if (m.scalar_type() == at::kBFloat16) {
+    TORCH_CHECK(step > 0, "adamw: bf16 state needs the step number (>= 1) that keys the rounding bits");
+    check_rc(rtdc_adamw_bf16state(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(),
+                                  m.data_ptr(), v.data_ptr(), ptr_or_null(shadow), (float)lr, (float)b1, (float)b2,
+                                  (float)eps, (float)wd, (float)bc1, (float)bc2_sqrt, (float)grad_scale,
+                                  (const int*)(uintptr_t)skip_ptr, (const float*)(uintptr_t)clip_ptr,
+                                  (unsigned long long)seed, (unsigned long long)step, cur_stream()),
+             "adamw");
+    return;
+  }
+  TORCH_CHECK(m.scalar_type() == at::kFloat, "adamw: optimizer state must be float32 or bfloat16, got ",
+              m.scalar_type());
   check_rc(rtdc_adamw(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                       v.data_ptr<float>(), ptr_or_null(shadow), (float)lr, (float)b1, (float)b2, (float)eps,
                       (float)wd, (float)bc1, (float)bc2_sqrt, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
@@ -1135,7 +1157,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw", &adamw, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("m"),
         py::arg("v"), py::arg("shadow"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
         py::arg("bc1"), py::arg("bc2_sqrt"), py::arg("grad_scale"), py::arg("skip_ptr") = 0,
-        py::arg("clip_ptr") = 0);
+        py::arg("clip_ptr") = 0, py::arg("seed") = 0, py::arg("step") = 0);
   m.def("sgd", &sgd, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("buf"),
         py::arg("shadow"), py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("wd"),
         py::arg("nesterov"), py::arg("first"), py::arg("grad_scale"), py::arg("skip_ptr") = 0,

@@ -30,6 +30,12 @@ the same fp32 norm (their fp64 sums agree to ~1e-15; the norms differ only if th
 lies that close to an fp32 rounding boundary) - with fp32 sums a ZeRO-1 and a replicated run
 got coefficients one ulp apart, which bf16 compute amplifies to visibly different parameters
 within a few steps.  The CPU reference paths sum in fp32.
+
+bf16 moment state (`FusedAdamW(state_dtype=torch.bfloat16)`, off by default): `exp_avg` and
+`exp_avg_sq` live in bf16 flat buffers and are rounded stochastically after every update, with
+Philox bits that are a pure function of (rounding_seed, step, flat element index) - the rule and
+its NumPy twin are in ops/random.py, the kernel is `adamw_bf16state_kernel`.  With bf16 state the
+CPU also steps over the flat buffers (every element needs its flat index).
 """
 from __future__ import annotations
 
@@ -38,6 +44,7 @@ import math
 import torch
 
 from ..ops._ext import gpu_ext
+from ..ops.random import sr_bf16, sr_words
 from ..ops.shadow import bump_generation
 from .flat import FlatParamSpace, space_of
 
@@ -63,6 +70,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._bound: set = set()
         self._have = None  # parameters with a gradient this step (set by the native step)
         self._overlap = None  # optim.overlap.BackwardOverlap (updates run during backward)
+        # dtype of the flat optimizer-state buffers (FusedAdamW(state_dtype=...) may set bfloat16)
+        self.state_dtype = torch.float32
         # DistributedDataParallel(zero_stage=1) leaves p.grad reduced only on this rank's shards:
         # only these optimizers (which update exactly the owned shards) may step such a model
         for p in self._all_params():
@@ -89,7 +98,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         # optimizer state: the whole flat space, or (ZeRO-1) only this rank's owned shards,
         # back to back - 1/world of the bytes (FlatParamSpace.state_numel)
         for k in self._state_keys:
-            self._bufs[k] = torch.zeros(sp.state_numel, dtype=torch.float32, device=sp.device)
+            self._bufs[k] = torch.zeros(sp.state_numel, dtype=self.state_dtype, device=sp.device)
         # adopt any state that already exists (e.g. loaded before the first step)
         for p in params:
             st = self.state.get(p)
@@ -128,7 +137,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 if a < b:
                     rr.append((a - lo, b - lo))
             ranges.append(rr)
-        return FlatShardedTensor(seg.shape, torch.float32, local, ranges, z.rank)
+        return FlatShardedTensor(seg.shape, buf.dtype, local, ranges, z.rank)
 
     def _adopt(self, p, k, v) -> None:
         """Copy a loaded/pre-existing state value into this optimizer's buffers (no-op when it
@@ -180,8 +189,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def _flat_mode(self) -> bool:
         """Updates run over the flat buffers' chunk tables: always on the GPU (native kernels),
-        and on the CPU under ZeRO-1 (owned shards only, compact state - reference path)."""
-        if self._use_native():
+        and on the CPU under ZeRO-1 (owned shards only, compact state - reference path) or with
+        bf16 state (the rounding bits are keyed by the flat element index)."""
+        if self._use_native() or self.state_dtype != torch.float32:
             return True
         sp = space_of(self._all_params())
         return sp is not None and sp.zero is not None
@@ -497,16 +507,31 @@ class FusedAdamW(_FlatOptimizer):
         self._steps.setdefault(p, 0)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 maximize=False, max_grad_norm=None):
+                 maximize=False, max_grad_norm=None, state_dtype=torch.float32, rounding_seed=0):
         """`max_grad_norm`: clip the global gradient norm inside the step (None / 0: off; settable
         later as `opt.max_grad_norm`).  `opt.grad_norm` then holds the pre-clip norm of the last
         step.  `p.grad` is left unscaled - the one visible difference from
-        `torch.nn.utils.clip_grad_norm_`, which rewrites the gradients."""
+        `torch.nn.utils.clip_grad_norm_`, which rewrites the gradients.
+
+        `state_dtype`: torch.float32 (default) or torch.bfloat16.  With bfloat16, `exp_avg` and
+        `exp_avg_sq` are STORED in bf16 (half the state memory and checkpoint bytes, 22 instead of
+        30 B moved per parameter and step) and rounded stochastically - round-to-nearest would
+        freeze `exp_avg_sq` at beta2 = 0.999.  The update of a step uses the fp32 moments before
+        rounding.  The random bits are Philox4x32-10 of (`rounding_seed`, the parameter's step
+        number, the element's offset in the flat parameter space): no RNG state exists, runs and
+        resumes are bit-identical, and the bits do not depend on how the chunk tables are cut.
+        They do depend on the flat layout, so a replicated and a ZeRO-1 run (whose buckets are
+        padded) are not promised equal bits.  Both are attributes, not param-group options:
+        `state_dict()` keeps torch's keys; a checkpoint resumes into the same `state_dtype`."""
         if amsgrad or maximize:
             raise NotImplementedError("amsgrad/maximize are not supported by the fused kernel")
+        if state_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"FusedAdamW state_dtype must be torch.float32 or torch.bfloat16, got {state_dtype!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
                                       fused=None), max_grad_norm)
+        self.state_dtype = state_dtype
+        self.rounding_seed = int(rounding_seed) & ((1 << 64) - 1)
 
     def _native_launches(self, group, ps) -> list:
         """[(params, decay_flags, fn(chunks, n))] of one param group's native update of `ps`
@@ -521,36 +546,65 @@ class FusedAdamW(_FlatOptimizer):
             def fn(chunks, n, clip=0, group=group, b1=b1, b2=b2, wd=wd, step=step):
                 ext.adamw(chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"],
                           sp.shadow, group["lr"], b1, b2, group["eps"], wd, 1 - b1 ** step,
-                          math.sqrt(1 - b2 ** step), sp.grad_scale, sp.skip_ptr, clip)
+                          math.sqrt(1 - b2 ** step), sp.grad_scale, sp.skip_ptr, clip, self.rounding_seed, step)
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out
 
     def _cpu_launches(self, group, ps) -> list:
         """CPU twin of `_native_launches` (ZeRO-1 on gloo): the per-tensor reference math of
-        `step`, applied chunk by chunk to the owned flat slices and the compact state."""
+        `step`, applied chunk by chunk to the owned flat slices and the compact state.  With bf16
+        state the parameter update is that same math on the widened moments (so step 1 equals the
+        fp32-state optimizer bit for bit), while the moments that are rounded and stored are
+        computed with the kernel's own operation order: a few fp32 ulps from the former, and the
+        same bits as the GPU keeps."""
         sp = self._space
         for p in ps:
             self._bind_state(p)
         b1, b2 = group["betas"]
         wd, lr, eps = group["weight_decay"], group["lr"], group["eps"]
         m_all, v_all = self._bufs["exp_avg"], self._bufs["exp_avg_sq"]
+        bf16_state = m_all.dtype == torch.bfloat16
+        if bf16_state:  # the kernel's fp32 coefficients: (float)b and 1.f - (float)b
+            f32 = torch.float32
+            b1f, b2f = torch.tensor(b1, dtype=f32), torch.tensor(b2, dtype=f32)
+            c1f, c2f = 1 - b1f, 1 - b2f
         out = []
         for step, sub in self._count(ps).items():
             def fn(chunks, n, clip=None, step=step):
                 gs = sp.grad_scale if clip is None else sp.grad_scale * clip
+                if bf16_state:  # (the kernel multiplies grad_scale and the coefficient in fp32)
+                    gsf = torch.tensor(sp.grad_scale, dtype=f32)
+                    if clip is not None:
+                        gsf = gsf * torch.tensor(clip, dtype=f32)
                 for start, ln, decay, so in self._rows(chunks, n):
                     p = sp.data[start:start + ln]
                     g = sp.grad[start:start + ln]
+                    ms, vs = m_all[so:so + ln], v_all[so:so + ln]
+                    # bf16 state: widen, do the fp32 math, update p from the unrounded moments
+                    m, v = (ms.float(), vs.float()) if bf16_state else (ms, vs)
+                    if bf16_state:
+                        # What is STORED repeats adamw_bf16state_kernel's operations bit for bit, so the
+                        # two paths keep the same state (one bf16 ulp of difference in a stored moment
+                        # would move the next update by lr * 2^-7): gr = g * gs; m = fma(1 - b1, gr, b1 * m);
+                        # v = fma(b2, v, ((1 - b2) * gr) * gr), every product and constant in fp32.  A
+                        # product of two fp32 values is exact in fp64, so fp64 multiply-add + one rounding
+                        # to fp32 is the fused operation (but for a double rounding, ~2^-29 of the cases).
+                        gr = g * gsf
+                        m_st = (c1f.double() * gr.double() + (b1f * m).double()).float()
+                        v_st = (b2f.double() * v.double() + ((c2f * gr) * gr).double()).float()
                     if gs != 1.0:
                         g = g * gs
-                    m, v = m_all[so:so + ln], v_all[so:so + ln]
                     if decay:
                         p.mul_(1 - lr * wd)
                     m.lerp_(g, 1 - b1)
                     v.mul_(b2).addcmul_(g, g, value=1 - b2)
                     denom = (v.sqrt() / math.sqrt(1 - b2 ** step)).add_(eps)
                     p.addcdiv_(m, denom, value=-lr / (1 - b1 ** step))
+                    if bf16_state:  # the kernel's rounding: bits keyed by (seed, step, flat index)
+                        w = sr_words(self.rounding_seed, step, start, ln)
+                        ms.copy_(sr_bf16(m_st, w & 0xFFFF))
+                        vs.copy_(sr_bf16(v_st, w >> 16))
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out

@@ -70,12 +70,17 @@ class WorkloadConfig:
     num_classes: int = 10
     max_grad_norm: Optional[float] = None  # clip the global gradient norm inside the fused step (None / 0: off)
     doc_len: Optional[int] = None  # LMs: packed sequences of documents of this mean length (None / 0: off)
+    # LMs: dtype the fused AdamW stores exp_avg / exp_avg_sq in: "fp32" | "bf16" (bf16: stochastically
+    # rounded with bits keyed by `seed`; a checkpoint resumes into the same setting)
+    opt_state_dtype: str = "fp32"
 
     @classmethod
     def from_dict(cls, d: dict) -> "WorkloadConfig":
         known = {f for f in cls.__dataclass_fields__}
         return cls(**{k: v for k, v in d.items() if k in known})
 
+
+_OPT_STATE_DTYPES = {"fp32": "float32", "bf16": "bfloat16"}  # option value -> torch dtype name
 
 _DEFAULTS = {
     # name prefix: (batch/worker, seq_len or image side, lr)
@@ -259,7 +264,8 @@ def build(cfg: WorkloadConfig, device) -> Workload:
         model = GPT2(mc).to(device)
     else:
         raise ValueError(f"unknown workload model {name!r}")
-    opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=clip)
+    opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=clip,
+                     state_dtype=getattr(torch, _OPT_STATE_DTYPES[cfg.opt_state_dtype]), rounding_seed=cfg.seed)
     data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed, doc_len=cfg.doc_len or None)
     # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle)
     return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S,
@@ -491,19 +497,24 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    bucket_cap_mb: float = 32.0, zero_stage: int = -1, progress_timeout_s: float | None = 300.0,
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
                    report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
-                   doc_len: int | None = None):
+                   doc_len: int | None = None, opt_state_dtype: str = "fp32"):
     """`train_fashion_mnist`'s counterpart for the bf16 workloads (R/my_ray_module.py:216-251).
     zero_stage -1: `default_zero_stage(model, num_workers)`.  max_grad_norm: clip the global
     gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
     `grad_norm` / `grad_norms` (pre-clip).  doc_len (LMs): train on packed sequences of synthetic
     documents of that mean length, attention and RoPE positions restricted to each document
-    (None / 0: off; the report rows are unchanged)."""
+    (None / 0: off; the report rows are unchanged).  opt_state_dtype (LMs): "fp32" | "bf16" - the
+    dtype FusedAdamW stores its moments in (bf16: half the optimizer memory and checkpoint bytes,
+    stochastic rounding keyed by `seed`; the report rows are unchanged)."""
+    if opt_state_dtype not in _OPT_STATE_DTYPES:
+        raise ValueError(f"opt_state_dtype must be one of {sorted(_OPT_STATE_DTYPES)}, got {opt_state_dtype!r}")
     if zero_stage < 0:
         zero_stage = default_zero_stage(model, num_workers)
     cfg = WorkloadConfig(model=model, steps=steps, batch_size_per_worker=batch_size_per_worker, seq_len=seq_len,
                          lr=lr, ckpt_every_n_steps=ckpt_every_n_steps, seed=seed, resume_mode=resume_mode,
                          checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
-                         max_grad_norm=max_grad_norm or None, doc_len=doc_len or None)
+                         max_grad_norm=max_grad_norm or None, doc_len=doc_len or None,
+                         opt_state_dtype=opt_state_dtype)
     run_config = train.RunConfig(
         name=name, storage_path=checkpoint_storage_path, verbose=verbose,
         checkpoint_config=train.CheckpointConfig(num_to_keep=num_checkpoints_to_keep,
@@ -538,14 +549,22 @@ def main(argv=None):
     ap.add_argument("--doc-len", type=int, default=None,
                     help="LMs: packed sequences of synthetic documents of this mean length, attention and "
                          "RoPE positions per document (default: off)")
+    ap.add_argument("--opt-state-dtype", default="fp32", choices=sorted(_OPT_STATE_DTYPES),
+                    help="LMs: dtype of the fused AdamW's stored moments (bf16: stochastically rounded)")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
     use_gpu = torch.cuda.is_available() and not a.cpu
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
-                         zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len)
+                         zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len,
+                         opt_state_dtype=a.opt_state_dtype)
     print(res)
 
 
 if __name__ == "__main__":
-    main()
+    # run the importable module's main: the training loop is then pickled for the workers by
+    # reference (as `python -m`'s __main__ it would be pickled by value, globals included, which
+    # fails on the torch namespaces among them)
+    from ray_torch_distributed_checkpoint_amd.workloads import main as _main
+
+    _main()

@@ -57,6 +57,9 @@ class RayTorchTrain(FlowSpec):
     doc_len = Parameter("doc_len", default=0,
                         help="LM workloads: packed sequences of synthetic documents of this mean length, attention "
                              "and RoPE positions per document (0: off)")
+    opt_state_dtype = Parameter("opt_state_dtype", default="fp32",
+                                help="LM workloads: fp32 | bf16 - dtype of the fused AdamW's stored moments (bf16: "
+                                     "stochastically rounded, half the optimizer memory and checkpoint bytes)")
     batch_size_per_worker = Parameter("batch_size_per_worker", default=0,
                                       help="bf16 workloads: samples per worker per step (0: the model's default). "
                                            "--batch_size is the reference MLP's global batch")
@@ -113,7 +116,8 @@ class RayTorchTrain(FlowSpec):
                 resume_mode=mode, max_failures=int(self.max_failures), grad_comm_dtype=self.grad_comm_dtype,
                 zero_stage=int(self.zero_stage),
                 report_every_n_steps=int(self.report_every_n_steps) or None,
-                max_grad_norm=float(self.max_grad_norm) or None, doc_len=int(self.doc_len) or None)
+                max_grad_norm=float(self.max_grad_norm) or None, doc_len=int(self.doc_len) or None,
+                opt_state_dtype=str(self.opt_state_dtype))
         self.next(self.join)
 
     @step

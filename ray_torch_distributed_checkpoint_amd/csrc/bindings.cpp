@@ -204,12 +204,15 @@ static int64_t gemm_bf16(Tensor A, Tensor B, Tensor C, c10::optional<Tensor> Cin
 
 // Independent plain products C_i = A_i . B_i in ONE launch of the 8-wave kernel (gemm_8ph.hip
 // gemm8g_kernel): dims = [M, N, K, lda, ldb, ldc] per product.  Layouts / output dtype shared;
-// currently the weight-gradient form (both operands MN-major, fp32 C).
+// currently the weight-gradient form (both operands MN-major, fp32 C).  accumulate (optional,
+// one flag per product): C_i += A_i . B_i for the flagged products, the others overwrite.
 static void gemm_bf16_grouped(std::vector<Tensor> A, std::vector<Tensor> B, std::vector<Tensor> C,
-                              std::vector<int64_t> dims, bool a_kmajor, bool b_kmajor) {
+                              std::vector<int64_t> dims, bool a_kmajor, bool b_kmajor,
+                              c10::optional<std::vector<int64_t>> accumulate) {
   const size_t n = A.size();
   TORCH_CHECK(n >= 1 && n <= 10 && B.size() == n && C.size() == n && dims.size() == 6 * n,
               "gemm_bf16_grouped: 1..10 products, 6 dims each");
+  TORCH_CHECK(!accumulate || accumulate->size() == n, "gemm_bf16_grouped: one accumulate flag per product");
   std::vector<rtdc::GemmArgs> args(n);
   const bool fp32 = C[0].scalar_type() == at::kFloat;
   for (size_t i = 0; i < n; ++i) {
@@ -237,6 +240,11 @@ static void gemm_bf16_grouped(std::vector<Tensor> A, std::vector<Tensor> B, std:
     a.alpha = 1.f;
     a.splitk = 1;
     a.tile_cfg = -1;
+    if (accumulate && (*accumulate)[i]) {
+      TORCH_CHECK(fp32, "gemm_bf16_grouped: accumulate needs fp32 outputs");
+      a.Cin = a.C;
+      a.beta = 1.f;
+    }
   }
   check_rc(rtdc_gemm8_grouped(args.data(), (int)n, a_kmajor, b_kmajor, fp32, cur_stream()), "gemm_bf16_grouped");
 }
@@ -1142,7 +1150,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   m.doc() = "MI355X (gfx950) kernels and native checkpoint engine";
   m.def("gemm_bf16", &gemm_bf16);
-  m.def("gemm_bf16_grouped", &gemm_bf16_grouped);
+  m.def("gemm_bf16_grouped", &gemm_bf16_grouped, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("dims"),
+        py::arg("a_kmajor"), py::arg("b_kmajor"), py::arg("accumulate") = py::none());
   m.def("gemm4b", &rtdc_gemm4b_set, py::arg("v") = -1,
         "route K-major x K-major 256x256 products to the one-barrier 4-wave kernel (1/0), or query (-1); returns the previous setting");
   m.def("gemm_f32", &gemm_f32);

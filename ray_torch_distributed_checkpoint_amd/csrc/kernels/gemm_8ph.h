@@ -734,6 +734,46 @@ __device__ __forceinline__ void tile_store_f32(const GemmArgs& a, f32x4 (&acc)[2
       }
 }
 
+// ---- accumulating fp32 tile store: C += alpha * acc (a later micro-batch of a gradient-
+// accumulation step adds into the parameter's slice of the flat gradient buffer).  Same
+// descriptor, fragment order and BUF_OOB offsets as tile_store_f32; the previous values come
+// in as 16-B buffer loads issued ACC_W fragments ahead of the store that needs them (a load
+// issued right behind stores waits for them too - vmcnt counts both - see tile_epilogue_bf16).
+// The persistent kernel still has A-lo of the K-tile after next in flight here: vm_drained()
+// retires it in a wait hipcc sees, so the waits it inserts for the loads below are counted
+// instead of vmcnt(0) at every fragment.  With alpha = 1 a fragment element is one IEEE add
+// (x * 1 + c contracts to an fma that rounds once), so C is bitwise prev + the plain store.
+constexpr int ACC_W = 4;
+template <int TMQ, int TNQ, int SA, int SB, int BH>
+__device__ __forceinline__ void tile_accum_f32(const GemmArgs& a, f32x4 (&acc)[2][2][TMQ][TNQ], int m0, int n0,
+                                               int wa, int wb, int lane, float alpha) {
+  vm_drained();
+  const long long tile_off = (long long)m0 * a.ldc * 4, rows_bytes = (long long)(a.M - m0) * a.ldc * 4;
+  const auto rC = make_rsrc(a.C, tile_off, rows_bytes);
+  const int rows_left = a.M - m0;
+  constexpr int NF = 4 * TMQ * TNQ, W = ACC_W < NF ? ACC_W : NF;
+  const int lrow = SA * wa + (lane & 15), lcol = n0 + SB * wb + 4 * (lane >> 4);
+  // fragment F = ((qa * 2 + qb) * TMQ + i) * TNQ + j: tile_store_f32's order
+  auto foff = [&](int F) -> uint32_t {
+    const int r = 128 * (F / (2 * TMQ * TNQ)) + 16 * ((F / TNQ) % TMQ) + lrow;
+    const int n = lcol + BH * ((F / (TMQ * TNQ)) % 2) + 16 * (F % TNQ);
+    return (r < rows_left && n < a.N) ? (uint32_t)(r * a.ldc + n) * 4u : BUF_OOB;
+  };
+  u32x4 prev[NF];
+#pragma unroll
+  for (int F = 0; F < W; ++F) prev[F] = buf_load16(rC, foff(F));
+#pragma unroll
+  for (int F = 0; F < NF; ++F) {
+    if (F + W < NF) prev[F + W] = buf_load16(rC, foff(F + W));
+    f32x4& x = acc[F / (2 * TMQ * TNQ)][(F / (TMQ * TNQ)) % 2][(F / TNQ) % TMQ][F % TNQ];
+    u32x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = __float_as_uint(x[r] * alpha + __uint_as_float(prev[F][r]));
+    buf_store16(rC, foff(F), v);
+    x = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
 // ---- grouped persistent variant (gemm8gp_kernel): gemm8p_kernel's cross-tile pipeline over
 // the tiles of a GROUP of independent products with the same K (a layer's weight gradients:
 // K = tokens).  Global tile T indexes the products' tiles back to back (gg.start); the XCD
@@ -763,7 +803,10 @@ __device__ __forceinline__ void group_tile(const GemmGroup& gg, int T, int total
   tn = (local % (GROUP_M * tiles_n)) / gsize;
 }
 
-template <bool AK, bool BKM>
+// ACC: the group has accumulating products (GemmArgs::Cin == C, beta 1: the launcher checks);
+// each tile takes the store of its own product, so a group may mix both kinds.  A separate
+// instantiation: the plain kernel keeps its code.
+template <bool AK, bool BKM, bool ACC = false>
 __global__ __launch_bounds__(512, 1) void gemm8gp_kernel(GemmGroup gg) {
   constexpr int BN = 256, BH = BN / 2, WA = 2, WB = 8 / WA;
   constexpr int SA = 128 / WA, SB = BH / WB, TMQ = SA / 16, TNQ = SB / 16;
@@ -901,7 +944,12 @@ __global__ __launch_bounds__(512, 1) void gemm8gp_kernel(GemmGroup gg) {
       }
     }
     const GemmArgs& a = gg.g[p];
-    tile_store_f32<TMQ, TNQ, SA, SB, BH>(a, acc, m0, n0, wa, wb, lane, a.alpha);
+    if constexpr (ACC) {
+      if (a.Cin != nullptr) tile_accum_f32<TMQ, TNQ, SA, SB, BH>(a, acc, m0, n0, wa, wb, lane, a.alpha);
+      else tile_store_f32<TMQ, TNQ, SA, SB, BH>(a, acc, m0, n0, wa, wb, lane, a.alpha);
+    } else {
+      tile_store_f32<TMQ, TNQ, SA, SB, BH>(a, acc, m0, n0, wa, wb, lane, a.alpha);
+    }
   }
 }
 

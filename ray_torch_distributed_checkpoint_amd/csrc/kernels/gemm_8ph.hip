@@ -79,15 +79,21 @@ extern "C" int rtdc_gemm8p_launch(const GemmArgs* args, int a_kmajor, int b_kmaj
 }
 
 // Grouped 8-wave launch (gemm8g_kernel): n <= 8 products, every one K % 64 == 0, splitk 1,
-// 256x256 tiles; layouts and output dtype shared.  Returns 1 for an unsupported group.
+// 256x256 tiles; layouts and output dtype shared.  A product with Cin == C and beta 1 adds into
+// its output (the one-block-per-tile form through epilogue4's Cin term, the persistent form
+// through tile_accum_f32); the others overwrite.  Returns 1 for an unsupported group.
 extern "C" int rtdc_gemm8_grouped(const GemmArgs* args, int n, int a_kmajor, int b_kmajor, int out_fp32,
                                   hipStream_t st) {
   if (n < 1 || n > g8::G8_MAX_GROUP) return 1;
   g8::GemmGroup gg{};
   int tiles = 0;
+  bool any_acc = false;
   for (int i = 0; i < n; ++i) {
     const GemmArgs& a = args[i];
     if (a.K % gemm::BK != 0 || a.K < gemm::BK || a.splitk > 1 || a.M % 8 != 0 || a.N % 8 != 0) return 1;
+    // an accumulating product (C += A.B) says so as Cin == C, beta 1; nothing else is added here
+    if (a.Cin != nullptr && (a.Cin != a.C || a.beta != 1.f || a.alpha != 1.f || a.alpha_dev != nullptr)) return 1;
+    any_acc = any_acc || a.Cin != nullptr;
     gg.g[i] = a;
     gg.g[i].splitk = 1;
     gg.start[i] = tiles;
@@ -117,7 +123,8 @@ extern "C" int rtdc_gemm8_grouped(const GemmArgs* args, int n, int a_kmajor, int
     long long gsz = (g_num_cus / 8) * 8;
     if (gsz < 8) gsz = 8;
     if (tiles < gsz) gsz = tiles;
-    hipLaunchKernelGGL((g8::gemm8gp_kernel<false, false>), dim3((unsigned)gsz), dim3(512), 0, st, gg);
+    if (any_acc) hipLaunchKernelGGL((g8::gemm8gp_kernel<false, false, true>), dim3((unsigned)gsz), dim3(512), 0, st, gg);
+    else hipLaunchKernelGGL((g8::gemm8gp_kernel<false, false>), dim3((unsigned)gsz), dim3(512), 0, st, gg);
     return hipGetLastError() == hipSuccess ? 0 : 2;
   }
   dim3 grid((unsigned)tiles, 1, 1), block(512);

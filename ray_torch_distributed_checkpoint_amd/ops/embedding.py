@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from ._ext import gpu_ext
-from .gradbuf import claimed_target, grad_target
+from .gradbuf import claimed_target, grad_slot
 from .shadow import shadow_of
 
 
@@ -110,12 +110,13 @@ class _Embedding(torch.autograd.Function):
         B, T = idx.shape
         wte_shape, wpe_shape = ctx.shapes
         wte, wpe = ctx.params
-        dwte = grad_target(wte)
-        accumulate = False
+        # (a later micro-batch of an accumulated step adds into the slot: grad_slot's flag)
+        dwte, accumulate = grad_slot(wte)
+        in_place = False
         if dwte is None:
             # tied table (GPT-2 LM head): add into the gradient the LM head already wrote
             dwte = claimed_target(wte)
-            accumulate = dwte is not None
+            accumulate = in_place = dwte is not None
         ext = gpu_ext()
         if dwte is None:
             dwte = torch.empty(wte_shape, dtype=torch.float32, device=idx.device)
@@ -123,10 +124,10 @@ class _Embedding(torch.autograd.Function):
             _zero(ext, dwte)  # rows no token uses (the kernel writes only the used ones)
         dwpe = None
         if wpe_shape is not None:
-            dwpe = grad_target(wpe)
+            dwpe, acc_wpe = grad_slot(wpe)
             if dwpe is None:
                 dwpe = torch.empty(wpe_shape, dtype=torch.float32, device=idx.device)
-            if T < wpe_shape[0]:
+            if T < wpe_shape[0] and not acc_wpe:
                 _zero(ext, dwpe[T:])  # the kernel writes (not adds) positions [0, T)
         if ctx.sorted is not None:
             if ctx.sorted in _pending:
@@ -136,8 +137,8 @@ class _Embedding(torch.autograd.Function):
                 torch.cuda.current_stream(idx.device).wait_event(done)
         else:
             sidx, perm = sort_ids(idx.reshape(-1), wte_shape[0])
-        ext.embed_bwd(sidx, perm, dout.contiguous(), dwte, dwpe, B, T, False, accumulate)
-        return None, (None if accumulate else dwte), dwpe, None
+        ext.embed_bwd(sidx, perm, dout.contiguous(), dwte, dwpe, B, T, wpe_shape is not None and acc_wpe, accumulate)
+        return None, (None if in_place else dwte), dwpe, None
 
 
 def embedding(idx: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor | None = None,

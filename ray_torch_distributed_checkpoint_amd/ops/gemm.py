@@ -184,7 +184,7 @@ def _deferrable(out) -> bool:
 
 class _WgradGroup:
     def __init__(self):
-        self.items = []      # (dy, x2d, out, tiles)
+        self.items = []      # (dy, x2d, out, tiles, whole_rounds, accumulate)
         self.jobs = []       # deferred column sums [ws, W, D, out alias, accumulate]
         self.tiles = 0
         self.ptrs = set()    # data_ptr of every pending output
@@ -220,7 +220,7 @@ class _WgradGroup:
                 return j
         return None
 
-    def add(self, dy, x2d, out, tiles, whole_rounds=False) -> bool:
+    def add(self, dy, x2d, out, tiles, whole_rounds=False, accumulate=False) -> bool:
         if not self._arm():
             return False
         # keep an alias, not `out` itself: AccumulateGrad adopts the returned tensor as p.grad
@@ -232,7 +232,7 @@ class _WgradGroup:
             # + 256 + 384 = 3328 tiles = 13 rounds, 14 when launched one by one
             if self.items and (len(self.items) >= _GROUP_MAX or not self.items[-1][4]):
                 self.flush()
-            self.items.append((dy, x2d, out.view(out.shape), tiles, True))
+            self.items.append((dy, x2d, out.view(out.shape), tiles, True, bool(accumulate)))
             self.tiles += tiles
             self.ptrs.add(out.data_ptr())
             if self.tiles % _ROUND == 0 or self.tiles > _BIG_TILES:
@@ -242,7 +242,7 @@ class _WgradGroup:
         # product would not fit the round any more (GPT-2: 252-tile groups of 9 products)
         if self.items and (self.tiles + tiles > _ROUND or len(self.items) >= _GROUP_MAX or self.items[-1][4]):
             self.flush()
-        self.items.append((dy, x2d, out.view(out.shape), tiles, False))
+        self.items.append((dy, x2d, out.view(out.shape), tiles, False, bool(accumulate)))
         self.tiles += tiles
         self.ptrs.add(out.data_ptr())
         if self.tiles >= _ROUND:
@@ -256,10 +256,11 @@ class _WgradGroup:
     def _launch_split(self, items):
         """A remainder far below a round (the last layer's products): each product on its own
         with split-K slabs, which spreads it over the chip."""
-        for dy, x2d, out, _, _ in items:
+        for dy, x2d, out, _, _, acc in items:
             M, N = dy.shape
             K = x2d.shape[1]
-            gemm_bf16(dy, x2d, out, N, K, M, N, K, K, False, False)
+            gemm_bf16(dy, x2d, out, N, K, M, N, K, K, False, False, Cin=out if acc else None,
+                      beta=1.0 if acc else 0.0)
 
     def pending(self, t) -> bool:
         return t is not None and bool(self.ptrs) and t.data_ptr() in self.ptrs
@@ -273,12 +274,14 @@ class _WgradGroup:
         for i in range(0, len(items), _GROUP_MAX):
             chunk = items[i:i + _GROUP_MAX]
             dims = []
-            for dy, x2d, out, _, _ in chunk:
+            for dy, x2d, out, _, _, _ in chunk:
                 M, N = dy.shape
                 K = x2d.shape[1]
                 dims += [N, K, M, N, K, K]
+            # (no flag list for an all-overwriting group: the single-backward call is unchanged)
+            acc = [int(c[5]) for c in chunk]
             gpu_ext().gemm_bf16_grouped([c[0] for c in chunk], [c[1] for c in chunk], [c[2] for c in chunk],
-                                        dims, False, False)
+                                        dims, False, False, acc if any(acc) else None)
 
     @staticmethod
     def _launch_jobs(jobs):
@@ -312,7 +315,7 @@ class _WgradGroup:
                     self._launch(items)
                 if jobs:
                     self._launch_jobs(jobs)
-                for dy, x2d, _, _, _ in items:  # the compute stream may recycle them before the kernel ran
+                for dy, x2d, _, _, _, _ in items:  # the compute stream may recycle them before the kernel ran
                     dy.record_stream(self.side)
                     x2d.record_stream(self.side)
                 for j in jobs:
@@ -369,7 +372,7 @@ def _groupable(dy, x2d, out, accumulate, alpha, alpha_dev) -> int:
     products that would otherwise split K (fewer than 200 output tiles, long K), or - over a
     short K (M < 4096 tokens: Llama-3-8B at 2048 per GPU) - multi-round products that are
     packed into whole rounds of the chip (returned negative)."""
-    if not (_GROUP_ON and dy.is_cuda and out is not None and not accumulate and alpha == 1.0 and alpha_dev is None
+    if not (_GROUP_ON and dy.is_cuda and out is not None and alpha == 1.0 and alpha_dev is None
             and out.dtype == torch.float32 and out.is_contiguous() and dy.is_contiguous() and x2d.is_contiguous()
             and dy.dtype == torch.bfloat16 and x2d.dtype == torch.bfloat16):
         return 0
@@ -393,7 +396,7 @@ def linear_wgrad(dy: torch.Tensor, x2d: torch.Tensor, out=None, accumulate=False
     M, N = dy.shape
     K = x2d.shape[1]
     tiles = _groupable(dy, x2d, out, accumulate, alpha, alpha_dev)
-    if tiles and _WG.add(dy, x2d, out, abs(tiles), whole_rounds=tiles < 0):
+    if tiles and _WG.add(dy, x2d, out, abs(tiles), whole_rounds=tiles < 0, accumulate=accumulate):
         return out
     if out is None:
         out = torch.empty((N, K), dtype=torch.float32, device=dy.device)

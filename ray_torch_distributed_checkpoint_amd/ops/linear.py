@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from . import gemm as G
 from ._ext import gpu_ext
-from .gradbuf import grad_target
+from .gradbuf import grad_slot, grad_target
 from .shadow import kmajor_image, kmajor_prefetch, kmajor_wanted, shadow_of
 
 
@@ -29,6 +29,19 @@ def _relu_mask_bwd(dy: torch.Tensor, y: torch.Tensor, p: float = 0.0) -> torch.T
     dx = torch.empty_like(dy)
     gpu_ext().relu_dropout(y, None, dy, dx, float(p), 0, 0, 2 if p > 0.0 else 1)
     return dx
+
+
+def _wgrad(dy2, x2, w):
+    """w's gradient dy2^T x2 into its flat-buffer slot: written, or - a later micro-batch of an
+    accumulated step (gradbuf.grad_slot) - added in the GEMM's epilogue."""
+    out, acc = grad_slot(w)
+    return G.linear_wgrad(dy2, x2, out=out, accumulate=acc)
+
+
+def _bgrad(dy2, b):
+    """b's gradient (column sums of dy2) into its slot, written or added like _wgrad."""
+    out, acc = grad_slot(b)
+    return G.colsum(dy2, out=out, accumulate=acc)
 
 
 class _LinearBF16(torch.autograd.Function):
@@ -64,8 +77,8 @@ class _LinearBF16(torch.autograd.Function):
         w, b = ctx.params
         dx = (G.linear_dgrad(dpre, ws, w_kmajor=kmajor_image(w) if ctx.kimg else None).view(ctx.in_shape)
               if ctx.needs_input_grad[0] else None)
-        dw = G.linear_wgrad(dpre, x2, out=grad_target(w)) if ctx.needs_input_grad[1] else None
-        db = G.colsum(dpre, out=grad_target(b)) if ctx.has_b and ctx.needs_input_grad[2] else None
+        dw = _wgrad(dpre, x2, w) if ctx.needs_input_grad[1] else None
+        db = _bgrad(dpre, b) if ctx.has_b and ctx.needs_input_grad[2] else None
         dres = dy if ctx.has_res else None
         return dx, dw, db, dres, None
 
@@ -189,8 +202,8 @@ class _FusedMLP(torch.autograd.Function):
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         w_fc, b_fc, w_proj, b_proj = ctx.params
-        dw_proj = G.linear_wgrad(dy2, g, out=grad_target(w_proj))
-        db_proj = G.colsum(dy2, out=grad_target(b_proj))
+        dw_proj = _wgrad(dy2, g, w_proj)
+        db_proj = _bgrad(dy2, b_proj)
         # c_fc's bias gradient = column sums of dpre, reduced in the dgrad GEMM's epilogue
         db_fc = grad_target(b_fc)
         if db_fc is None and b_fc is not None:
@@ -198,7 +211,7 @@ class _FusedMLP(torch.autograd.Function):
         act = G.ACT_MUL if _GELU_SAVE_GRAD else G.ACT_GELU_BWD
         dpre = G.linear_dgrad(dy2, wps, act_bwd=act, aux_in=pre, colsum_out=db_fc,
                               w_kmajor=kmajor_image(w_proj) if ctx.kimg else None)
-        dw_fc = G.linear_wgrad(dpre, x2, out=grad_target(w_fc))
+        dw_fc = _wgrad(dpre, x2, w_fc)
         dx = G.linear_dgrad(dpre, wfs, w_kmajor=kmajor_image(w_fc) if ctx.kimg else None).view(ctx.in_shape)
         return dx, dw_fc, db_fc, dw_proj, db_proj, (dy if ctx.has_res else None)
 

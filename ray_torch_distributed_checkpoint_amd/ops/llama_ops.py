@@ -6,7 +6,7 @@ import torch.nn.functional as F
 
 from . import gemm as G
 from ._ext import gpu_ext, require_dtype
-from .gradbuf import grad_target
+from .gradbuf import grad_slot
 from .shadow import shadow_of
 
 _tables: dict = {}
@@ -112,11 +112,13 @@ class _SwiGLUMLP(torch.autograd.Function):
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         w13, w2 = ctx.params
-        dw2 = G.linear_wgrad(dy2, h, out=grad_target(w2))
+        o2, a2 = grad_slot(w2)  # (written, or added to in a later micro-batch of an accumulated step)
+        dw2 = G.linear_wgrad(dy2, h, out=o2, accumulate=a2)
         dh = G.linear_dgrad(dy2, w2s)
         dgu = torch.empty_like(gu)
         gpu_ext().swiglu_bwd(gu, dh, dgu)
-        dw13 = G.linear_wgrad(dgu, x2, out=grad_target(w13))
+        o13, a13 = grad_slot(w13)
+        dw13 = G.linear_wgrad(dgu, x2, out=o13, accumulate=a13)
         dx = G.linear_dgrad(dgu, w13s).view(ctx.in_shape)
         return dx, dw13, dw2, (dy if ctx.has_res else None)
 

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 from . import gemm as G
 from ._ext import gpu_ext, require_dtype
-from .gradbuf import grad_target
+from .gradbuf import grad_slot, grad_target
 from .shadow import shadow_of
 
 
@@ -58,7 +58,8 @@ class _LayerNorm(torch.autograd.Function):
         wsp = G.workspace(xc.device, _bwd_ws_elems(nw, D), "ln_bwd")
         dx = torch.empty_like(xc)
         w, b = ctx.params
-        dg, db = grad_target(w), grad_target(b)
+        # (slot, add): a later micro-batch of an accumulated step adds into the slots
+        (dg, ag), (db, ab) = grad_slot(w), grad_slot(b)
         if dg is None or db is None:
             dgb = torch.empty((2, D), dtype=torch.float32, device=xc.device)
             dg = dgb[0] if dg is None else dg
@@ -71,23 +72,35 @@ class _LayerNorm(torch.autograd.Function):
         # which then returns them as the bias gradient without touching dx again.
         dxsum = None
         if ctx.sum_param is not None:
-            dxsum = grad_target(ctx.sum_param)
+            dxsum, asum = grad_slot(ctx.sum_param)
             if dxsum is None:
                 dxsum = torch.empty(D, dtype=torch.float32, device=xc.device)
         outs = [dg, db] + ([dxsum] if dxsum is not None else [])
+        accs = [ag, ab] + ([asum] if dxsum is not None else [])
+        if any(accs) and not all(G._deferrable(o) for o in outs):
+            # the immediate launch below overwrites its outputs: an adding output goes to a
+            # temporary instead, which the fold-back adds to the slot (D-sized vectors)
+            outs = [torch.empty(D, dtype=torch.float32, device=xc.device) if a else o for o, a in zip(outs, accs)]
+            for p, a in zip((w, b, ctx.sum_param), accs):
+                if a:
+                    p._rtdc_claim = -1  # slot not used after all: the projection's colsum() adds the sums itself
+            accs = [False] * len(outs)
+            dg, db = outs[0], outs[1]
+            dxsum = outs[2] if dxsum is not None else None
         if all(G._deferrable(o) for o in outs):
             # partial rows into a buffer of their own, reduced with the deferred window (gemm.py)
             part = torch.empty(len(outs) * (nw // 4 + 64) * D, dtype=torch.float32, device=xc.device)
             nblk = gpu_ext().layernorm_bwd(dy.contiguous(), xc, ws, mean, rstd, dres, dx, part, dg, db, dxsum, nw,
                                            False, True)
             rows = part[: len(outs) * nblk * D].view(len(outs), nblk * D)
-            done = [G._WG.add_job(rows[z], nblk, D, o, False) for z, o in enumerate(outs)]
+            done = [G._WG.add_job(rows[z], nblk, D, o, accs[z]) for z, o in enumerate(outs)]
             if not all(done):
                 if any(done):
                     G.flush_wgrads()
                 gpu_ext().colsum_multi([rows[z] for z, d in enumerate(done) if not d],
                                        [o for o, d in zip(outs, done) if not d],
-                                       [nblk] * done.count(False), [D] * done.count(False), [0] * done.count(False))
+                                       [nblk] * done.count(False), [D] * done.count(False),
+                                       [int(a) for a, d in zip(accs, done) if not d])
         else:
             gpu_ext().layernorm_bwd(dy.contiguous(), xc, ws, mean, rstd, dres, dx, wsp, dg, db, dxsum, nw, False,
                                     False)

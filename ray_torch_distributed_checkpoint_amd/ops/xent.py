@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from . import gemm as G
 from ._ext import gpu_ext
 from .embedding import launch_pending_sorts
-from .gradbuf import grad_target
+from .gradbuf import grad_slot
 from .shadow import kmajor_image, kmajor_prefetch, kmajor_wanted, shadow_of
 
 IGNORE_INDEX = -100
@@ -155,7 +155,8 @@ class _LMHeadXent(torch.autograd.Function):
             gpu_ext().xent_alpha(gs, cnt, a)
             gs = a
         dx = G.linear_dgrad(dlogits, ws, alpha_dev=gs, w_kmajor=kmajor_image(ctx.w) if ctx.kimg else None)
-        dw = G.linear_wgrad(dlogits, x2, out=grad_target(ctx.w), alpha_dev=gs)
+        out, acc = grad_slot(ctx.w)  # (a later micro-batch of an accumulated step: Cin = out, beta 1)
+        dw = G.linear_wgrad(dlogits, x2, out=out, accumulate=acc, alpha_dev=gs)
         return dx.view(ctx.in_shape), dw, None, None, None
 
 

@@ -116,6 +116,13 @@ class FlatParamSpace:
         # or an add, and no memset of the buffer is needed.
         self.fresh = False
         self.step_id = 0
+        # gradient accumulation over micro-batches (next_micro_step): `accumulating` from the
+        # second micro-batch of a step on, `_touched[i]` = parameter i's slice holds the sum of
+        # this step's earlier micro-batches (a later contribution is added, not written)
+        self.accumulating = False
+        self._touched: list | None = None
+        self._claim_bufs: dict = {}       # id(p) -> this micro-batch's temporary of a twice-used weight
+        self._sum_has_slice: set = set()  # segments whose out-of-buffer gradient already includes the slice
         off = 0
         align_after = align_after or {}
         for i, p in enumerate(uniq):
@@ -206,6 +213,11 @@ class FlatParamSpace:
         if self.grad is None:
             return
         self.wait_pending_tail()
+        self.accumulating = False  # (a new step: the slices hold nothing of it yet)
+        self._touched = None
+        if self._claim_bufs:
+            self._claim_bufs.clear()
+        self._sum_has_slice.clear()
         if set_to_none:
             for p in self.params:
                 p.grad = None
@@ -219,10 +231,61 @@ class FlatParamSpace:
             if p.grad is None or p.grad.data_ptr() != v.data_ptr():
                 p.grad = v
 
+    # ---- gradient accumulation over micro-batches -----------------------------------------
+    def touched(self, p) -> bool:
+        """p's slice holds the sum of this step's earlier micro-batches."""
+        return self._touched is not None and self._touched[self._seg_of[id(p)].index]
+
+    def next_micro_step(self) -> None:
+        """Between two backward passes of ONE optimizer step: remember which parameters have a
+        gradient so far, and detach every `p.grad` again.  The next backward then runs in the
+        same adopt-the-view protocol as the first (`p.grad is None`: AccumulateGrad adopts the
+        flat view an op returns, the post-accumulate hooks fire), but `ops.gradbuf.grad_slot`
+        tells the ops to ADD into the slices of the remembered parameters; a gradient that still
+        arrives outside the buffer is added by the fold-back.  `zero_grad` ends the mode."""
+        if self.grad is None:
+            raise RuntimeError("next_micro_step needs a flat gradient buffer (FlatParamSpace(grads=True))")
+        from ..ops.gemm import flush_wgrads
+
+        flush_wgrads()  # every deferred product of the finished micro-batch is in its slice
+        self.wait_pending_tail()
+        self.fold_grads()
+        self._claim_bufs.clear()
+        self._sum_has_slice.clear()
+        if self._touched is None:
+            self._touched = [False] * len(self.params)
+        for i, p in enumerate(self.params):
+            if p.grad is not None:
+                self._touched[i] = True
+                p.grad = None
+        self.fresh = True
+        self.accumulating = True
+        self.step_id += 1
+
+    def _fold(self, p, s: Segment) -> None:
+        """p.grad lives outside the flat buffer: bring it into p's slice - added to what the
+        earlier micro-batches left there in accumulate mode, copied otherwise."""
+        v = self.view(self.grad, s)
+        with torch.no_grad():
+            if self.accumulating and self._touched[s.index] and s.index not in self._sum_has_slice:
+                v.add_(p.grad)
+            else:
+                v.copy_(p.grad)
+        p.grad = v
+
+    def fold_grads(self) -> None:
+        """Fold every gradient that sits outside the flat buffer into its slice."""
+        st = self._grad_status(self.grad.data_ptr())
+        for p, s, k in zip(self.params, self.segments, st):
+            if k == 2:
+                self._fold(p, s)
+
     def ensure_grad_views(self) -> list:
         """Fold gradients that autograd allocated outside the flat buffer back into it and
         return the parameters that have a gradient this step (the optimizers skip the rest,
-        like torch).  One native pass over the parameters when the extension is loaded."""
+        like torch).  One native pass over the parameters when the extension is loaded.
+        In accumulate mode a parameter that an earlier micro-batch gave a gradient counts even
+        if the last one did not: its view is re-attached."""
         if self.grad is None:
             return [p for p in self.params if p.grad is not None]
         base = self.grad.data_ptr()
@@ -230,14 +293,15 @@ class FlatParamSpace:
         have = []
         for p, s, k in zip(self.params, self.segments, st):
             if k == 0:
+                if self.accumulating and self._touched[s.index]:
+                    p.grad = self.view(self.grad, s)
+                    have.append(p)
                 continue
             have.append(p)
             if k == 1:
                 continue
             self.wait_pending_tail()  # never write into a slice a collective still owns
-            v = self.view(self.grad, s)
-            v.copy_(p.grad)
-            p.grad = v
+            self._fold(p, s)
         return have
 
     def _grad_status(self, base: int):

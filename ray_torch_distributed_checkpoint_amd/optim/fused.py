@@ -296,6 +296,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._space.zero_grad(set_to_none=set_to_none)
         else:
             super().zero_grad(set_to_none=set_to_none)
+            sp = space_of(self._all_params())
+            if sp is not None and sp.accumulating:
+                # the per-tensor CPU step over a space someone else built (a DDP wrap): the
+                # accumulated step ends here too
+                sp.zero_grad(set_to_none=set_to_none)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -483,7 +488,26 @@ class _FlatOptimizer(torch.optim.Optimizer):
         for p in ps:
             g = p.grad.float()
             ws["local"] += (g * g).sum()
-        return self._write_clip(ws["out"], ws["local"][0], 1.0, float(self.max_grad_norm))
+        sp = space_of(self._all_params())
+        return self._write_clip(ws["out"], ws["local"][0], 1.0 if sp is None else sp.grad_scale,
+                                float(self.max_grad_norm))
+
+    def _plain_prelude(self):
+        """Start of the per-tensor CPU step: wait for a deferred collective, bring an
+        accumulated step's gradients into their slices (FlatParamSpace.ensure_grad_views: the
+        add fold-back, and the views of parameters only an earlier micro-batch touched), and
+        return the factor on every gradient (clip coefficient x the space's grad_scale; None: 1)."""
+        sp = space_of(self._all_params())
+        gs = 1.0
+        if sp is not None:
+            sp.wait_pending_tail()
+            if sp.accumulating:
+                sp.ensure_grad_views()
+            gs = sp.grad_scale
+        coef = self._plain_clip()
+        if coef is None:
+            return None if gs == 1.0 else gs
+        return coef * gs
 
     def _use_native(self):
         ps = self._all_params()
@@ -634,10 +658,7 @@ class FusedAdamW(_FlatOptimizer):
                                    "(use eager steps, or FusedSGD inside utils.graphs.CapturedStep)")
             self._flat_step()
             return loss
-        sp = space_of(self._all_params())
-        if sp is not None:
-            sp.wait_pending_tail()
-        coef = self._plain_clip()
+        coef = self._plain_prelude()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             ps = self._with_grad(group)
@@ -746,10 +767,7 @@ class FusedSGD(_FlatOptimizer):
         if self._flat_mode():
             self._flat_step()
             return loss
-        sp = space_of(self._all_params())
-        if sp is not None:
-            sp.wait_pending_tail()
-        coef = self._plain_clip()
+        coef = self._plain_prelude()
         for group in self.param_groups:
             mom = group["momentum"]
             for p in self._with_grad(group):

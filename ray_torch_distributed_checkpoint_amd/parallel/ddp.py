@@ -364,10 +364,8 @@ class DistributedDataParallel(nn.Module):
             s = sp.segment_of(p) if g.data_ptr() < sp.grad.data_ptr() or \
                 g.data_ptr() >= sp.grad.data_ptr() + sp.grad.numel() * 4 else None
             if s is not None:
-                seg_view = FlatParamSpace.view(sp.grad, s)
-                with torch.no_grad():
-                    seg_view.copy_(g)
-                p.grad = seg_view
+                # (added to the earlier micro-batches' sum in accumulate mode, copied otherwise)
+                sp._fold(p, s)
         if self._engine is not None:
             self._engine.mark_ready(self._pidx[id(p)])
             return

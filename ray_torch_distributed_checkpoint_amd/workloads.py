@@ -47,7 +47,7 @@ from . import train
 from .checkpoint import dcp
 from .checkpoint.state_dict import get_state_dict, set_state_dict
 from .ops.xent import IGNORE_INDEX
-from .optim import FusedAdamW, FusedSGD
+from .optim import FusedAdamW, FusedSGD, GradAccumulator
 from .parallel.sampler import DistributedSampler
 from .utils.profiling import phase
 
@@ -73,6 +73,9 @@ class WorkloadConfig:
     # LMs: dtype the fused AdamW stores exp_avg / exp_avg_sq in: "fp32" | "bf16" (bf16: stochastically
     # rounded with bits keyed by `seed`; a checkpoint resumes into the same setting)
     opt_state_dtype: str = "fp32"
+    # micro-batches per optimizer step (optim.GradAccumulator): each step draws this many batches,
+    # adds their gradients in place in the flat buffer and applies their mean
+    grad_accum_steps: int = 1
 
     @classmethod
     def from_dict(cls, d: dict) -> "WorkloadConfig":
@@ -361,6 +364,12 @@ def _set_rng(blob: bytes, rank: int, device) -> bool:
 
 
 # ---------------------------------------------------------------------------------- loop
+def samples_per_s(steps: int, grad_accum_steps: int, batch: int, world: int, dt: float) -> float:
+    """Samples per second of `steps` optimizer steps in dt seconds: each step consumes
+    grad_accum_steps micro-batches of `batch` samples on each of `world` workers."""
+    return round(steps * grad_accum_steps * batch * world / max(dt, 1e-9), 3)
+
+
 def _unwrap(m):
     return m.module if hasattr(m, "module") else m
 
@@ -427,17 +436,35 @@ def train_loop_per_worker(config: dict):
     clipping = bool(cfg.max_grad_norm)
     norms = []  # per-step pre-clip gradient norms (device scalars, read with the losses)
     t_last, n_last = time.perf_counter(), 0
+    k = int(cfg.grad_accum_steps or 1)
+    if k < 1:
+        raise ValueError(f"grad_accum_steps must be >= 1, got {k}")
+    # k > 1: every optimizer step draws k batches; only the last backward reduces across ranks
+    acc = GradAccumulator(opt, steps=k, ddp=net if hasattr(net, "no_sync") else None) if k > 1 else None
     for step in range(start, cfg.steps):
         train.report_progress(step)
-        batch = stream.next()  # (x, y), or (x, y, docs) for packed sequences (doc_len)
-        with phase("fwd"):
-            loss = wl.loss_fn(net, *batch)
-        with phase("bwd"):
-            loss.backward()
+        if acc is None:
+            batch = stream.next()  # (x, y), or (x, y, docs) for packed sequences (doc_len)
+            with phase("fwd"):
+                loss = wl.loss_fn(net, *batch)
+            with phase("bwd"):
+                loss.backward()
+            loss = loss.detach()
+        else:
+            micro = []
+            for i in range(k):
+                batch = stream.next()
+                with acc.micro_step(i):
+                    with phase("fwd"):
+                        li = wl.loss_fn(net, *batch)
+                    with phase("bwd"):
+                        li.backward()
+                micro.append(li.detach())
+            loss = torch.stack(micro).float().mean()  # (on the device: still one host sync per report)
         with phase("opt"):
             opt.step()
             opt.zero_grad(set_to_none=True)
-        losses.append(loss.detach())
+        losses.append(loss)
         if clipping:
             norms.append(opt.grad_norm.clone())
         n_last += 1
@@ -452,7 +479,7 @@ def train_loop_per_worker(config: dict):
         vals, gnorms = vals[:len(losses)], vals[len(losses):]
         dt = time.perf_counter() - t_last
         metrics = {"step": done, "loss": vals[-1], "losses": vals, "epoch": stream.epoch,
-                   "samples_per_s": round(n_last * wl.batch * world / max(dt, 1e-9), 3)}
+                   "samples_per_s": samples_per_s(n_last, k, wl.batch, world, dt)}
         if wl.tokens_per_sample:
             metrics["tokens_per_s"] = round(metrics["samples_per_s"] * wl.tokens_per_sample, 1)
         if clipping:
@@ -497,7 +524,7 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    bucket_cap_mb: float = 32.0, zero_stage: int = -1, progress_timeout_s: float | None = 300.0,
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
                    report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
-                   doc_len: int | None = None, opt_state_dtype: str = "fp32"):
+                   doc_len: int | None = None, opt_state_dtype: str = "fp32", grad_accum_steps: int = 1):
     """`train_fashion_mnist`'s counterpart for the bf16 workloads (R/my_ray_module.py:216-251).
     zero_stage -1: `default_zero_stage(model, num_workers)`.  max_grad_norm: clip the global
     gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
@@ -505,7 +532,12 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     documents of that mean length, attention and RoPE positions restricted to each document
     (None / 0: off; the report rows are unchanged).  opt_state_dtype (LMs): "fp32" | "bf16" - the
     dtype FusedAdamW stores its moments in (bf16: half the optimizer memory and checkpoint bytes,
-    stochastic rounding keyed by `seed`; the report rows are unchanged)."""
+    stochastic rounding keyed by `seed`; the report rows are unchanged).  grad_accum_steps = k:
+    every optimizer step accumulates k micro-batches in place (optim.GradAccumulator) and applies
+    their mean; `steps` stays optimizer steps, a row's loss is the mean over its k micro-batches
+    and samples_per_s / tokens_per_s count k x the batch."""
+    if int(grad_accum_steps) < 1:
+        raise ValueError(f"grad_accum_steps must be >= 1, got {grad_accum_steps}")
     if opt_state_dtype not in _OPT_STATE_DTYPES:
         raise ValueError(f"opt_state_dtype must be one of {sorted(_OPT_STATE_DTYPES)}, got {opt_state_dtype!r}")
     if zero_stage < 0:
@@ -514,7 +546,7 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                          lr=lr, ckpt_every_n_steps=ckpt_every_n_steps, seed=seed, resume_mode=resume_mode,
                          checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
                          max_grad_norm=max_grad_norm or None, doc_len=doc_len or None,
-                         opt_state_dtype=opt_state_dtype)
+                         opt_state_dtype=opt_state_dtype, grad_accum_steps=int(grad_accum_steps))
     run_config = train.RunConfig(
         name=name, storage_path=checkpoint_storage_path, verbose=verbose,
         checkpoint_config=train.CheckpointConfig(num_to_keep=num_checkpoints_to_keep,
@@ -551,13 +583,15 @@ def main(argv=None):
                          "RoPE positions per document (default: off)")
     ap.add_argument("--opt-state-dtype", default="fp32", choices=sorted(_OPT_STATE_DTYPES),
                     help="LMs: dtype of the fused AdamW's stored moments (bf16: stochastically rounded)")
+    ap.add_argument("--grad-accum-steps", type=int, default=1,
+                    help="micro-batches accumulated in place per optimizer step (default 1: off)")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
     use_gpu = torch.cuda.is_available() and not a.cpu
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
                          zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len,
-                         opt_state_dtype=a.opt_state_dtype)
+                         opt_state_dtype=a.opt_state_dtype, grad_accum_steps=a.grad_accum_steps)
     print(res)
 
 

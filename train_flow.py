@@ -60,6 +60,9 @@ class RayTorchTrain(FlowSpec):
     opt_state_dtype = Parameter("opt_state_dtype", default="fp32",
                                 help="LM workloads: fp32 | bf16 - dtype of the fused AdamW's stored moments (bf16: "
                                      "stochastically rounded, half the optimizer memory and checkpoint bytes)")
+    grad_accum_steps = Parameter("grad_accum_steps", default=1,
+                                 help="bf16 workloads: micro-batches accumulated in place per optimizer step; "
+                                      "--steps stays optimizer steps (1: off)")
     batch_size_per_worker = Parameter("batch_size_per_worker", default=0,
                                       help="bf16 workloads: samples per worker per step (0: the model's default). "
                                            "--batch_size is the reference MLP's global batch")
@@ -117,7 +120,7 @@ class RayTorchTrain(FlowSpec):
                 zero_stage=int(self.zero_stage),
                 report_every_n_steps=int(self.report_every_n_steps) or None,
                 max_grad_norm=float(self.max_grad_norm) or None, doc_len=int(self.doc_len) or None,
-                opt_state_dtype=str(self.opt_state_dtype))
+                opt_state_dtype=str(self.opt_state_dtype), grad_accum_steps=int(self.grad_accum_steps))
         self.next(self.join)
 
     @step

@@ -280,7 +280,7 @@ def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = Non
                      docs: DocLayout | None = None) -> torch.Tensor:
     """qkv: [B, T, (H + 2*Hkv) * Dh] -> [B, T, H*Dh].  docs (packed sequences): row q attends to
     the keys start[q] <= key <= q of its own document only; it needs the flash path - there is
-    no unmasked fallback."""
+    no unmasked fallback.  Without docs any T runs: the composed path pads T to a multiple of 64."""
     B, T, W = qkv.shape
     Hkv = n_kv_head or n_head
     Dh = W // (n_head + 2 * Hkv)
@@ -302,4 +302,10 @@ def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = Non
         return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs)
     if impl == "flash" and flash_supported(T, Dh):
         return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh)
+    if T % 64:
+        # the composed GEMMs take T as a reduction length and as the row pitch of P (gemm_bf16 needs
+        # K % 64 == 0): zero rows are appended.  Causality keeps them out of every real row, and their
+        # dO is zero in the backward (the slice's gradient), so they add nothing to dK / dV either.
+        pad = -T % 64
+        return _CausalAttention.apply(F.pad(qkv, (0, 0, 0, pad)), B, T + pad, n_head, Hkv, Dh)[:, :T]
     return _CausalAttention.apply(qkv, B, T, n_head, Hkv, Dh)

@@ -5,7 +5,11 @@
   twin of each reference stays <= 2^-4 ulp (bf16 outputs) / <= 2^-18 relative (fp32 outputs) of
   the fp64 reference, i.e. the FLOOR_* constants and the inputs are well chosen;
 * sensitivity: a deliberately wrong twin, rounded to bf16, exceeds the allowance that a kernel is
-  given on the same case.
+  given on the same case;
+* attention (the last section): the twin with the kernels' bf16 roundings stays inside the derived
+  per-element allowance on every case of the table, plain and under every document layout; ten
+  deliberate errors leave it; the launch grids of the table meet every branch of xcd_grid; the
+  older whole-tensor yardstick accepts three of those errors.
 """
 import pytest
 import torch
@@ -180,3 +184,149 @@ def test_mutant_swiglu_halves_swapped():
                U.swiglu_ref(F32, c["gu"], c["dh"], mutant="swap"))
     assert _ulp_caught(m["dgu"], r["dgu"], t["dgu"], U.row_floor(r["dgu"], U.FLOOR_SWIGLU))
     assert not _ulp_caught(m["h"], r["h"], t["h"], U.row_floor(r["h"], U.FLOOR_SWIGLU))
+
+
+# ------------------------------------------------------------------------------- flash attention
+def _attn_docs(layout, T, B):
+    return None if layout is None else U.doc_arrays(U.attn_layout(layout, T, B), T)
+
+
+def _attn_pair(c, layout=None, path="flash"):
+    """(fp64 reference with its allowance, fp32 twin with the kernel's roundings) of one case"""
+    B, T, H, Hkv, Dh, gen = c
+    x = U.attn_inputs(gen, B, T, H, Hkv, Dh)
+    docs = _attn_docs(layout, T, B)
+    a = (x["qkv"], x["dout"], B, T, H, Hkv, Dh, docs)
+    return U.attn_ref(F64, *a, path=path), U.attn_ref(F32, *a, twin=True, path=path)
+
+
+@pytest.mark.parametrize("c", U.ATTN_CASES, ids=U.attn_case_id)
+def test_twin_attention(c):
+    """the derivation holds: with the kernel's bf16 roundings in place the fp32 twin stays inside
+    the per-element allowance on every output, plain and under every document layout"""
+    J = U.Judge()
+    fams = dict.fromkeys(U.ATTN_OUTPUTS, "attn")
+    for layout in (None,) + U.ATTN_LAYOUTS:
+        r, t = _attn_pair(c, layout)
+        U.judge_attn(J, fams, (U.attn_case_id(c), layout or "plain"), r, t, {}, U.ATTN_OUTPUTS)
+        assert all(bool((r["allow_" + n] > 0).all()) for n in U.ATTN_OUTPUTS)
+    J.check()
+
+
+@pytest.mark.parametrize("c", U.ATTN_GEMM, ids=U.attn_case_id)
+def test_twin_attention_composed(c):
+    J = U.Judge()
+    r, t = _attn_pair(c, path="gemm")
+    U.judge_attn(J, dict.fromkeys(U.ATTN_OUTPUTS, "attn-gemm"), U.attn_case_id(c), r, t, {})
+    J.check()
+
+
+def test_attn_layouts_and_masks():
+    """the two forms of the document mask (start per query row, end per key row) are one set; the
+    layouts have the features their comment names"""
+    for T in (64, 128, 192, 256, 384):
+        for name in U.ATTN_LAYOUTS:
+            lengths = U.attn_layout(name, T, 3)
+            st, en = U.doc_arrays(lengths, T)
+            kq, kkv, same = U.attn_masks(3, T, (st, en), "cpu")
+            assert same and torch.equal(kq, kkv) and bool(kq.diagonal(dim1=1, dim2=2).all())
+        a = U.attn_layout("A", T, 3)
+        assert a[0][0] == 5 and a[0][2:4] == [1, 1] and a[1] == [T] and a[2] == a[0][::-1]
+        assert all(n % 64 == 0 for row in U.attn_layout("aligned", T, 3) for n in row)
+    from tests.test_attn_docmask_gpu import LAYOUT_A
+
+    for T, rows in LAYOUT_A.items():
+        assert U.attn_layout("A", T, 2) == rows
+
+
+def test_attn_spikes_straddle_the_lazy_rescale():
+    """a check on the data: in the last 64-row block every row's running maximum rises by clearly
+    less than 8 (log2 domain) at key tile 1 - against the stale maximum of tile 0, as the kernel
+    compares - and by clearly more than 8 at tile 2, at the smallest T with four key tiles"""
+    cases = [c for c in U.ATTN_CASES if c[5] == "spikes"]
+    assert cases and all(c[1] == 256 for c in cases)
+    for B, T, H, Hkv, Dh, gen in cases:
+        x = U.attn_inputs(gen, B, T, H, Hkv, Dh)
+        r1, r2, r20 = U.attn_spike_rises(x["qkv"], B, T, H, Hkv, Dh)
+        assert 1.0 < r1.min().item() and r1.max().item() < 7.0, (r1.min().item(), r1.max().item())
+        assert r2.min().item() > 9.0 and r20.min().item() > 9.0
+
+
+def test_attn_offset_heads():
+    """a check on the data: q-head 0's scores lie near +60, the last head's near -40 (log2 domain)"""
+    for B, T, H, Hkv, Dh, gen in [c for c in U.ATTN_CASES if c[5] == "offset"]:
+        x = U.attn_inputs(gen, B, T, H, Hkv, Dh)
+        r = U.attn_ref(F64, x["qkv"], x["dout"], B, T, H, Hkv, Dh)
+        lse = r["lse"].view(B, H, T)
+        assert (lse[:, 0] - 60).abs().max().item() < 12 and (lse[:, H - 1] + 40).abs().max().item() < 12
+
+
+def test_attn_grids_meet_every_xcd_branch():
+    """every kernel of attn_flash.hip is launched, over the case table x variants x head splits, on
+    grids that take each branch of xcd_grid: gridDim.y % 8 == 0; n % 8 == 0 with gridDim.y % 8 != 0;
+    n % 8 != 0, once with n < 8.  The table also holds every value the issue lists."""
+    seen = {}
+    for B, T, H, Hkv, Dh, _ in U.ATTN_CASES:
+        for v in U.ATTN_VARIANTS:
+            for qs in U.attn_head_splits(H, Hkv):
+                for fam, gx, gy in U.attn_launches(B, T, H, Hkv, Dh, v, qs):
+                    seen.setdefault(fam, set()).add(U.xcd_branch(gx, gy))
+    assert set(seen) == {"fwd", "fwd2", "dq", "dq2", "dkdv", "dkdv2"}
+    for fam, br in seen.items():
+        assert {"rows", "even"} <= br and br & {"ragged", "ragged<8"}, (fam, br)
+    for fams in (("fwd", "fwd2"), ("dq", "dq2"), ("dkdv", "dkdv2")):
+        assert any("ragged<8" in seen[f] for f in fams), fams
+    col = lambda i: {c[i] for c in U.ATTN_CASES}
+    assert col(0) == {1, 2, 3} and col(1) == {64, 128, 192, 256, 384} and col(4) == {64, 128}
+    assert {(c[2], c[3]) for c in U.ATTN_CASES} == {(1, 1), (4, 4), (4, 2), (8, 2), (8, 1)}
+    assert col(5) == set(U.ATTN_GENS)
+    assert {qs for c in U.ATTN_CASES for qs in U.attn_head_splits(c[2], c[3])} == {1, 2, 4}
+    assert {k for v in U.ATTN_VARIANTS for k in v} == {1, 2} and (1, 1, 1) in U.ATTN_VARIANTS and (2, 2, 2) in U.ATTN_VARIANTS
+    assert U.xcd_branch(2, 8) == "rows" and U.xcd_branch(4, 2) == "even" and U.xcd_branch(3, 4) == "ragged"
+
+
+# mutant -> the outputs on which it must leave the allowance
+ATTN_MUTANT_OUTPUTS = {
+    "diag_upper": ("out", "dv"), "diag_wave_last": ("dk", "dv"), "drop_key": ("out", "dv"),
+    "scores_x102": ("lse", "dv"), "bwd_p_x102": ("dv",), "l_low": ("lse", "dv"),
+    "dout_dropped": ("delta", "dq", "dk", "dv"), "group_first_only": ("dk", "dv"), "doc_start_low": ("out", "dq"),
+    "doc_end_low": ("dk", "dv"),
+}
+ATTN_MUTANT_CASES = [(2, 256, 4, 2, 64, "randn"), max(U.ATTN_CASES, key=lambda c: (c[1], c[0] * c[2]))]
+_attn_refs: dict = {}
+
+
+def _attn_mutant_scores(c, mutant):
+    layout = "A" if mutant.startswith("doc_") else None
+    B, T, H, Hkv, Dh, gen = c
+    x = U.attn_inputs(gen, B, T, H, Hkv, Dh)
+    a = (x["qkv"], x["dout"], B, T, H, Hkv, Dh, _attn_docs(layout, T, B))
+    if (c, layout) not in _attn_refs:
+        _attn_refs[(c, layout)] = U.attn_ref(F64, *a)
+    r = _attn_refs[(c, layout)]
+    t = U.attn_ref(F32, *a, twin=True, mutant=mutant)
+    return r, t, {n: U.allow_err(t[n], r[n], r["allow_" + n]) for n in U.ATTN_OUTPUTS}
+
+
+@pytest.mark.parametrize("c", ATTN_MUTANT_CASES, ids=U.attn_case_id)
+@pytest.mark.parametrize("mutant", U.ATTN_MUTANTS)
+def test_mutant_attention(mutant, c):
+    """each deliberate error, computed like a kernel would (fp32, bf16 roundings), leaves the
+    allowance on every output named for it, at T = 256 and at the largest T of the table"""
+    assert c[1] in (256, max(k[1] for k in U.ATTN_CASES))
+    _, _, s = _attn_mutant_scores(c, mutant)
+    print(mutant, {n: round(v, 3) for n, v in s.items()})
+    for n in ATTN_MUTANT_OUTPUTS[mutant]:
+        assert s[n] > 1.0, (mutant, n, s)
+
+
+def test_old_yardstick_accepts_attention_mutants():
+    """the gap this yardstick closes, kept on record: max |err| <= 2e-2 (out) / 3e-2 (gradients) x
+    max |ref| over the whole tensor accepts scores x 1.02, the backward's P x 1.02 and a row sum
+    2^-6 low on all four outputs at T = 256, while each leaves the per-element allowance"""
+    c = ATTN_MUTANT_CASES[0]
+    for mutant in ("scores_x102", "bwd_p_x102", "l_low"):
+        r, t, s = _attn_mutant_scores(c, mutant)
+        for n, rel in (("out", 2e-2), ("dq", 3e-2), ("dk", 3e-2), ("dv", 3e-2)):
+            assert U.old_yardstick(t[n], r[n], rel), (mutant, n)
+        assert max(s.values()) > 1.0

@@ -19,6 +19,11 @@ this file (tests/test_ulp_cpu.py holds that condition); what cancels is said nex
 
 The case generators at the bottom are shared by tests/test_ulp_cpu.py (twin condition, mutant
 sensitivity) and tests/test_row_kernels_gpu.py (the kernels).
+
+The last section does the same for the attention kernels (attn_flash.hip and the composed path),
+with one difference said there: those kernels round to bf16 inside the computation, so their
+allowance is a per-element tensor derived from those roundings (`attn_ref`, `Judge.within`), not
+a multiple of an unrounded twin's error.  tests/test_attn_ulp_gpu.py runs the kernels against it.
 """
 from __future__ import annotations
 
@@ -107,6 +112,11 @@ class Judge:
         t = rel_err(twin, ref64, scale)
         self._note(op, shape, what, "rel", None if out is None else rel_err(out, ref64, scale), t,
                    allow_f32(t, R), TWIN_REL_CEIL)
+
+    def within(self, op, shape, what, out, ref64, twin, allow):
+        """a per-element allowance tensor (attn_ref): max |out - ref| / allowance <= 1, the twin too"""
+        self._note(op, shape, what, "x allowance", None if out is None else allow_err(out, ref64, allow),
+                   allow_err(twin, ref64, allow), 1.0, 1.0)
 
     def check(self):
         for (op, what, unit), (k, t, a, shape) in sorted(self.worst.items()):
@@ -533,3 +543,355 @@ def judge_rope(J, shape, x, H, Hkv, Dh, inverse, out, what="y"):
     r, t = rope_ref(F64, *a), rope_ref(F32, *a)
     J.ulp("rope", shape, what, None if out is None else out.reshape(r.shape), r, t, row_floor(r, FLOOR_ROPE))
     return r
+
+
+# ------------------------------------------------------------------------------- flash attention
+# attn_flash.hip (fwd, fwd2, bwd_dq, bwd_dq2, bwd_dkdv, bwd_dkdv2, dkdv_reduce) and the composed
+# GEMM + softmax path of ops/attention.py, judged per element against an explicit fp64 forward and
+# backward.  Unlike the row kernels these round to bf16 INSIDE the computation (the probabilities
+# feed MFMAs as bf16 operands), so the allowance is not measured from an unrounded twin: it is the
+# first-order bound of those roundings, counted from the source, each term taken with the absolute
+# values of its leaves.  The twin applies the same roundings in fp32 and has to stay inside it
+# (tests/test_ulp_cpu.py); no coefficient is tuned against a kernel.
+# Relative error of one round-to-nearest conversion to bf16 (8 significant bits): half a spacing,
+# 2^-8 of the binade's lower end.  (2^-9 is its value at the upper end; with it the twin, which
+# only rounds where the kernels do, left the allowance on dV by up to 1.29 x and on out by 1.04 x.)
+U_BF16 = 2.0 ** -8
+U2 = (1.0 + U_BF16) ** 2 - 1.0     # two such roundings in a product chain (2u + u^2)
+LOG2E = 1.4426950408889634
+ATTN_OUTPUTS = ("out", "lse", "delta", "dq", "dk", "dv")
+ATTN_MUTANTS = ("diag_upper", "diag_wave_last", "drop_key", "scores_x102", "bwd_p_x102", "l_low", "dout_dropped",
+                "group_first_only", "doc_start_low", "doc_end_low")
+
+
+def _f32_terms(n: int) -> float:
+    """the fp32 share of an allowance: n serially added terms + 64 (v_exp / v_log / v_rcp, the MFMA's
+    own accumulation, another summation order), in units of 2^-24 of the sum of |terms|"""
+    return (n + 64) * 2.0 ** -24
+
+
+def _rb(x: torch.Tensor, on: bool) -> torch.Tensor:
+    return x.to(BF16).to(x.dtype) if on else x
+
+
+def _stored(ref: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """allowance of a value the kernel stores as bf16, a = the allowance before that rounding: the
+    value rounded is within a of ref, so the rounding adds at most half a spacing of |ref| + a"""
+    return a + 0.5 * ulp_bf16((ref.abs() + a).clamp_min(TINY))
+
+
+def doc_arrays(lengths, T, dev="cpu"):
+    """(start, end) int64 [B, T] of a list of document lengths per batch row (what DocLayout holds)."""
+    st, en = [], []
+    for row in lengths:
+        assert sum(row) == T and min(row) > 0
+        s, e, at = [], [], 0
+        for n in row:
+            s += [at] * n
+            e += [at + n] * n
+            at += n
+        st.append(s)
+        en.append(e)
+    return torch.tensor(st, device=dev), torch.tensor(en, device=dev)
+
+
+def attn_masks(B, T, docs, dev, mutant=""):
+    """keep_q [B, Tq, Tk]: start[q] <= k <= q, as the query-row kernels (fwd, dQ) test it;
+    keep_kv: k <= q < end[k], as the key-row kernels (dK/dV) do.  The same set for a valid layout."""
+    pos = torch.arange(T, device=dev)
+    if docs is None:
+        start, end = torch.zeros(B, T, dtype=torch.int64, device=dev), torch.full((B, T), T, device=dev)
+    else:
+        start, end = docs[0].long().clone(), docs[1].long().clone()
+    if mutant in ("doc_start_low", "doc_end_low"):
+        # the longest document of batch row 0 that does not begin the row
+        s0 = start[0]
+        cand = torch.unique(s0[s0 > 0])
+        assert cand.numel(), "the mutant needs a second document"
+        first = cand[torch.stack([(s0 == c).sum() for c in cand]).argmax()]
+        if mutant == "doc_start_low":
+            start[0, s0 == first] -= 1
+        else:
+            end[0, s0 == first] -= 1
+    q, k = pos[None, :, None], pos[None, None, :]
+    keep_q = (k >= start[:, :, None]) & (k <= q)
+    keep_kv = (k <= q) & (q < end[:, None, :])
+    if mutant in ("diag_upper", "diag_wave_last", "drop_key"):
+        if mutant == "diag_upper":
+            hit = (k == q) & (q >= T // 2)
+        elif mutant == "diag_wave_last":
+            hit = (k == q) & (q >= T - 64) & (q % 16 == 15)
+        else:
+            hit = (k == T // 2 - 3) & (q >= T - 64)
+        keep_q = keep_q & ~hit
+        keep_kv = keep_kv & ~hit
+    return keep_q, keep_kv, mutant != "doc_end_low"
+
+
+def attn_ref(dtype, qkv, dout, B, T, H, Hkv, Dh, docs=None, twin=False, mutant="", path="flash"):
+    """Causal (document-masked with docs = (start, end)) attention on packed qkv [B, T, (H + 2 Hkv) Dh]
+    with GQA, forward and backward written out: S, m, e, l, O, lse | delta, P, dP, dS, dQ, dK, dV.
+
+    dtype float64, twin False: the reference; it also returns the per-element allowance of every
+    output ("allow_<name>").  twin=True (float32): the kernel's bf16 roundings where attn_flash.hip
+    places them - e ahead of P.V and of the row sum (pack_pair in fwd_kernel; fwd2_kernel sums the
+    unrounded e, one rounding fewer), O as stored and as delta reads it, P ahead of dV, dS ahead of
+    dQ / dK, each stored gradient once after the fp32 sum over the group (registers, or the
+    head-split partials).  path="gemm": the composed path of ops/attention.py, which also stores
+    S, P, dP and dS as bf16 matrices and adds the group's dK / dV in bf16.
+    Masked entries are never looked at.  `mutant`: a deliberate error (ATTN_MUTANTS)."""
+    assert mutant == "" or mutant in ATTN_MUTANTS
+    dev, G, C = qkv.device, H // Hkv, H * Dh
+    gemm = path == "gemm"
+    rq = twin and not gemm   # the flash kernels' roundings
+    rg = twin and gemm       # the composed path's
+    scale = _f32(1.0 / math.sqrt(Dh))   # a float in the kernels
+    x = qkv.to(dtype)
+    heads = lambda t, n, g: t.reshape(B, T, n, g, Dh).permute(0, 2, 3, 1, 4)   # [B, n, g, T, Dh]; head = n * G + g
+    q, k, v = heads(x[..., :C], Hkv, G), heads(x[..., C:C + Hkv * Dh], Hkv, 1), heads(x[..., C + Hkv * Dh:], Hkv, 1)
+    do = heads(dout.to(dtype), Hkv, G)
+    keep_q, keep_kv, same = attn_masks(B, T, docs, dev, mutant)
+    kq, kkv = keep_q[:, None, None], keep_kv[:, None, None]
+    tr = lambda t: t.transpose(-1, -2)
+    zero = torch.zeros((), dtype=dtype, device=dev)
+
+    # ---- forward
+    S = _rb((q @ tr(k)) * scale, rg)                      # [B, Hkv, G, Tq, Tk]
+    if mutant == "scores_x102":
+        S[..., T // 2:, :] *= 1.02
+    Sm = torch.where(kq, S, torch.full_like(S, -math.inf))
+    m = Sm.amax(-1, keepdim=True)
+    e = _rb(torch.exp(Sm - m), rq)
+    l = e.sum(-1, keepdim=True)
+    if mutant == "l_low":
+        l[..., T - 64:, :] *= 1.0 - 2.0 ** -6
+    if gemm:
+        Pf = _rb(e / l, rg)                               # the stored bf16 P, which the backward re-reads
+        O = _rb(Pf @ v, rg)
+    else:
+        O = _rb((e @ v) / l, rq)
+    lse = m + torch.log(l)
+
+    # ---- backward
+    dob = do
+    if mutant == "dout_dropped":
+        dob = do.clone()
+        dob[:, -1, -1, T - 16:] = 0
+    dP = dob @ tr(v)
+    if gemm:
+        dP = _rb(dP, rg)
+        Praw = Pf
+        delta = torch.where(kq, Pf * dP, zero).sum(-1, keepdim=True)   # softmax_bwd's row term
+    else:
+        Praw = torch.exp(S - lse)
+        delta = (dob * O).sum(-1, keepdim=True)
+    if mutant == "bwd_p_x102":
+        Praw = Praw.clone()
+        Praw[..., 64:, :] *= 1.02
+    P = torch.where(kq, Praw, zero)
+    dS = _rb(P * (torch.where(kq, dP, zero) - delta), twin)
+    if same:
+        Pk, dSk = P, dS
+    else:
+        Pk = torch.where(kkv, Praw, zero)
+        dSk = _rb(Pk * (torch.where(kkv, dP, zero) - delta), twin)
+    dQ = _rb((dS @ k) * scale, twin)
+    dVg, dKg = tr(_rb(Pk, rq)) @ dob, (tr(dSk) @ q) * scale    # per q-head [B, Hkv, G, Tk, Dh]
+    if mutant == "group_first_only":
+        dVg[:, :, 1:, T - 64:] = 0
+        dKg[:, :, 1:, T - 64:] = 0
+    if rg:   # beta = 1 GEMMs: every q-head of the group is added to the stored bf16 rows
+        dV, dK = _rb(dVg[:, :, 0], True), _rb(dKg[:, :, 0], True)
+        for g in range(1, G):
+            dV, dK = _rb(dV + dVg[:, :, g], True), _rb(dK + dKg[:, :, g], True)
+    else:
+        dV, dK = _rb(dVg.sum(2), twin), _rb(dKg.sum(2), twin)
+
+    rows = lambda t: t.permute(0, 3, 1, 2, 4).reshape(B, T, -1)      # [B, n, g, T, Dh] -> [B, T, n g Dh]
+    kvrows = lambda t: t.permute(0, 2, 1, 3).reshape(B, T, -1)       # [B, Hkv, T, Dh]
+    vec = lambda t: t[..., 0].reshape(B * H, T)
+    res = {"out": rows(O), "lse": vec(lse) * LOG2E, "delta": vec(delta), "dq": rows(dQ), "dk": kvrows(dK),
+           "dv": kvrows(dV)}
+    if dtype != F64 or twin or mutant:
+        return res
+
+    # ---- the allowance (u = U_BF16; F(n) = _f32_terms(n) of the sum of |terms| at the leaves)
+    u, Fk, Fg, Fd = U_BF16, _f32_terms(T), _f32_terms(G * T), _f32_terms(Dh)
+    av, ak, aq, ado = v.abs(), k.abs(), q.abs(), do.abs()
+    pv, pk = P @ av, P @ ak
+    dterms = (do * O).abs().sum(-1, keepdim=True)             # the leaves of delta
+    dpl = torch.where(kq, ado @ tr(av), zero) + dterms        # the leaves of dP - delta
+    Wt = P * (torch.where(kq, dP, zero) - delta).abs()        # |dS|
+    if not gemm:
+        # out: e rounded (numerator) and l the sum of rounded e (denominator): U2; O stored as bf16
+        A_o = _stored(O, (U2 + Fk) * pv)
+        # delta = sum_d dO * O(stored)
+        E_d = (ado * A_o).sum(-1, keepdim=True) + Fd * dterms
+        # lse = m + log2 l, l within u (sum of rounded e); the lazy rescale keeps the kernel's m
+        # within 8 below the row maximum, so |m| + |log2 l| is up to 16 above the reference's
+        A_lse = LOG2E * u + Fk * (LOG2E * (m.abs() + torch.log(l).abs()) + 16.0)
+        # dV: P = 2^(s c - lse) inherits u from lse and is rounded by pack_pair: U2; dV stored as bf16
+        A_dv = _stored(dV, (U2 + Fg) * (tr(P) @ ado).sum(2))
+        # dQ: u from lse in P, dS rounded by pack_pair: U2; P x (error of delta); dQ stored as bf16
+        A_dq = _stored(dQ, scale * (U2 * (Wt @ ak) + Fk * ((P * dpl) @ ak) + E_d * pk))
+        # dK: the mirror image, summed over the group in fp32 and stored once
+        A_dk = _stored(dK, scale * (U2 * (tr(Wt) @ aq) + Fg * (tr(P * dpl) @ aq) + tr(P * E_d) @ aq).sum(2))
+    else:
+        # gemm_bf16 stores S = bf16(alpha Q K^T): e carries u |s|, and so does l, p-weighted; the
+        # softmax stores P = bf16(e / l): relative error of p_ij
+        sabs = torch.where(kq, S, zero).abs()
+        r = u * (1.0 + sabs + (P * sabs).sum(-1, keepdim=True)) + Fk
+        A_o = (P * r) @ av + (u + Fk) * pv                      # + O rounded when stored
+        # dP = bf16(dO V^T); the row term sum_j P dP is formed from the stored P and dP
+        adp = torch.where(kq, dP, zero).abs()
+        E_d = (P * (r + u) * adp).sum(-1, keepdim=True) + Fk * (P * adp).sum(-1, keepdim=True)
+        A_lse = torch.zeros_like(lse)                           # the composed path keeps no lse
+        # dS = bf16(P (dP - row term)): error of P, of dP, of the row term, its own rounding
+        E_s = P * (r * (adp + delta.abs()) + u * adp + E_d) + u * Wt + Fd * P * dpl
+        A_dq = scale * (E_s @ ak + (u + Fk) * (Wt @ ak))        # + dQ rounded when stored
+        # dK / dV: one bf16 rounding per q-head added (beta = 1 re-reads the stored rows)
+        gV, gK = tr(P) @ ado, scale * (tr(Wt) @ aq)             # per q-head sums of |terms|
+        cum = lambda t: sum(t[:, :, : g + 1].sum(2) for g in range(G))   # |partial sum| after each add
+        A_dv = (tr(P * r) @ ado).sum(2) + u * cum(gV) + Fk * gV.sum(2)
+        A_dk = scale * (tr(E_s) @ aq).sum(2) + u * cum(gK) + Fk * gK.sum(2)
+    res.update(allow_out=rows(A_o), allow_lse=vec(A_lse), allow_delta=vec(E_d), allow_dq=rows(A_dq),
+               allow_dk=kvrows(A_dk), allow_dv=kvrows(A_dv))
+    return res
+
+
+def allow_err(out, ref64, allow) -> float:
+    """max |out - ref| / allowance, elementwise (an exact match scores 0 whatever the allowance)."""
+    d = (out.double() - ref64.double()).abs()
+    e = torch.where(d == 0, torch.zeros_like(d), d / allow.double())
+    return float("nan") if bool(torch.isnan(e).any()) else e.max().item()
+
+
+def old_yardstick(out, ref64, rel) -> bool:
+    """`_close` of tests/test_kernels_gpu.py and tests/test_attn_docmask_gpu.py: the largest error of the
+    tensor against rel x the largest magnitude of the tensor"""
+    return (out.double() - ref64).abs().max().item() <= rel * (ref64.abs().max().item() + 1e-6)
+
+
+# -- inputs
+ATTN_GENS = ("randn", "peaky", "spikes", "offset")
+SPIKE_A, SPIKE_B = 8.25, 22.0   # log2-domain scores of the two planted keys (tile 1, tile 2)
+
+
+def attn_inputs(gen, B, T, H, Hkv, Dh, seed=0, dev="cpu"):
+    """qkv [B, T, (H + 2 Hkv) Dh] and dout [B, T, H Dh], bf16.
+    randn: plain.  peaky: q and k x 3 (rows near one-hot).
+    spikes (T >= 256): the rows of the last 64-row block are one +-1 direction w plus a little
+    noise, and two keys are multiples of w - one in key tile 1 scoring SPIKE_A, one in tile 2
+    scoring SPIKE_B in the log2 domain - so every row's running maximum rises by clearly less than
+    8 at tile 1 (no rescale, e up to 2^7) and by clearly more at tile 2 (rescale): the
+    `mx * c > m + 8` test of the forward kernels (attn_spike_rises measures it).
+    offset: dimension 0 of every key is 16; q-head 0 has the matching value that puts all its
+    scores near +60 in the log2 domain, the last q-head (H > 1) near -40."""
+    gen_ = torch.Generator().manual_seed(7919 * T + 131 * Dh + 17 * H + 3 * Hkv + B + seed)
+    C, KV = H * Dh, Hkv * Dh
+    x = torch.randn(B, T, C + 2 * KV, generator=gen_)
+    dout = torch.randn(B, T, C, generator=gen_)
+    qv, kv_ = x[..., :C].view(B, T, H, Dh), x[..., C:C + KV].view(B, T, Hkv, Dh)
+    if gen == "peaky":
+        qv *= 3
+        kv_ *= 3
+    elif gen == "spikes":
+        assert T >= 256
+        w = torch.where(torch.rand(Dh, generator=gen_) < 0.5, -1.0, 1.0)
+        qv[:, T - 64:] = w + 0.125 * qv[:, T - 64:]
+        # scale * (w . gamma w) = gamma sqrt(Dh) in natural units
+        kv_[:, 64 + 5] = w * (SPIKE_A / LOG2E / math.sqrt(Dh))
+        kv_[:, 128 + 37] = w * (SPIKE_B / LOG2E / math.sqrt(Dh))
+    elif gen == "offset":
+        kv_[..., 0] = 16.0
+        qv[:, :, 0, 0] = 60.0 / LOG2E * math.sqrt(Dh) / 16.0
+        if H > 1:
+            qv[:, :, H - 1, 0] = -40.0 / LOG2E * math.sqrt(Dh) / 16.0
+    else:
+        assert gen == "randn"
+    return {"qkv": x.to(BF16).to(dev), "dout": dout.to(BF16).to(dev)}
+
+
+def attn_spike_rises(qkv, B, T, H, Hkv, Dh):
+    """per row of the last 64-row block (plain causal): the rise of the running maximum over the
+    tile-0 maximum at key tile 1 and at key tile 2, log2 domain - what the lazy rescale tests"""
+    C, G = H * Dh, H // Hkv
+    x = qkv.double()
+    q = x[..., :C].reshape(B, T, Hkv, G, Dh).permute(0, 2, 3, 1, 4)[..., T - 64:, :]
+    k = x[..., C:C + Hkv * Dh].reshape(B, T, Hkv, 1, Dh).permute(0, 2, 3, 1, 4)
+    s = (q @ k.transpose(-1, -2)) * (LOG2E / math.sqrt(Dh))
+    m0, m1, m2 = (s[..., 64 * t:64 * t + 64].amax(-1) for t in range(3))
+    return m1 - m0, m2 - torch.maximum(m0, m1), m2 - m0
+
+
+# -- document layouts (lengths per batch row).  A: a boundary inside the first wave (5), one
+# mid-wave, two documents of length 1, later blocks that continue a document from an earlier key
+# tile; batch row 1 a single document, row 2 the reverse of row 0.  T = 192 and 256 are LAYOUT_A
+# of tests/test_attn_docmask_gpu.py.
+_LAYOUT_A = {64: [5, 35, 1, 1, 22], 128: [5, 65, 1, 1, 56], 192: [5, 65, 1, 1, 58, 62],
+             256: [5, 65, 1, 1, 58, 126], 384: [5, 65, 1, 1, 58, 126, 70, 58]}
+_ALIGNED = {64: [64], 128: [64, 64], 192: [64, 128], 256: [64, 128, 64], 384: [64, 128, 64, 128]}
+ATTN_LAYOUTS = ("A", "aligned", "ones")
+
+
+def attn_layout(name, T, B):
+    if name == "ones":
+        return [[1] * T for _ in range(B)]
+    if name == "aligned":
+        a = _ALIGNED[T]
+        return [a, a[::-1], [64] * (T // 64)][:B]
+    a = _LAYOUT_A[T]
+    return [a, [T], a[::-1]][:B]
+
+
+# -- the case table: (B, T, H, Hkv, Dh, generator).  T = 64 one tile; 128 the first size of the
+# 32-row kernels; 192 forces the 64-row kernels and wraps the NS = 2 ring; 256 two 128-row blocks
+# and four key tiles; 384 three 128-row blocks.  Group sizes 1, 2, 4, 8; B chosen so that every
+# launch grid meets every branch of xcd_grid (test_attn_grids_meet_every_xcd_branch).
+ATTN_CASES = [
+    (1, 64, 1, 1, 64, "randn"),
+    (3, 64, 4, 2, 128, "peaky"),
+    (2, 128, 4, 4, 64, "randn"),
+    (1, 128, 8, 2, 128, "offset"),
+    (3, 128, 8, 1, 64, "offset"),
+    (2, 192, 4, 2, 64, "randn"),
+    (1, 192, 8, 1, 128, "peaky"),
+    (2, 256, 4, 2, 64, "spikes"),
+    (1, 256, 4, 4, 128, "randn"),
+    (1, 384, 1, 1, 64, "randn"),
+    (2, 384, 4, 2, 128, "peaky"),
+]
+ATTN_VARIANTS = [(1, 1, 1), (2, 2, 2), (1, 2, 1), (2, 1, 2)]   # (RTDC_FA_FWD, RTDC_FA_DQ, RTDC_FA_DKDV)
+ATTN_DIRECT = [ATTN_CASES[7], ATTN_CASES[3]]                   # the cases the GPU test also launches directly
+ATTN_GEMM = [(2, 100, 4, 2, 64, "randn"), (1, 128, 8, 2, 128, "peaky")]   # RTDC_ATTN=gemm
+
+
+def attn_case_id(c):
+    return "B%d-T%d-H%d-Hkv%d-Dh%d-%s" % c
+
+
+def attn_head_splits(H, Hkv):
+    """the RTDC_FA_QS values ops/attention.py honours for this group size"""
+    return [qs for qs in (1, 2, 4) if (H // Hkv) % qs == 0]
+
+
+def attn_launches(B, T, H, Hkv, Dh, v, qs):
+    """(kernel, gridDim.x, gridDim.y) of the three launches, from flash_fwd_launch / flash_bwd_launch
+    with all three variant knobs set (so Dh = 128 takes bwd_dkdv2 when asked)."""
+    two = T % 128 == 0
+    f, d, kv = (x == 2 and two for x in v)
+    return [("fwd2" if f else "fwd", T // (128 if f else 64), B * H),
+            ("dq2" if d else "dq", T // (128 if d else 64), B * H),
+            ("dkdv2" if kv else "dkdv", T // (128 if kv else 64), B * Hkv * qs)]
+
+
+def xcd_branch(gx, gy):
+    """the branch of xcd_grid (common.h, x_major) a grid takes"""
+    n = gx * gy
+    return "rows" if gy % 8 == 0 else ("even" if n % 8 == 0 else ("ragged<8" if n < 8 else "ragged"))
+
+
+def judge_attn(J, fams, shape, ref, twin, outs, names=("out", "dq", "dk", "dv")):
+    """fams: the kernel that wrote each output, by output name (the WORST lines go by it)"""
+    for n in names:
+        J.within(fams[n], shape, n, outs.get(n), ref[n], twin[n], ref["allow_" + n])

@@ -50,6 +50,14 @@ int rtdc_adamw_bf16state(const void* chunks, int nchunks, float* p, const float*
 int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow, float lr,
              float momentum, float dampening, float wd, int nesterov, int first, float grad_scale,
              const int* skip, const float* clip, hipStream_t st);
+int rtdc_adamw_dev(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v, int m_bf16,
+                   void* shadow, const long long* count, const float* lr_row, int L, const float* bc, int Lbc,
+                   int step_off, float b1, float b2, float eps, float wd, float grad_scale, const int* skip,
+                   const float* clip, unsigned long long seed, hipStream_t st);
+int rtdc_sgd_dev(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow,
+                 const long long* count, const float* lr_row, int L, float momentum, float dampening, float wd,
+                 int nesterov, int first, float grad_scale, const int* skip, const float* clip, hipStream_t st);
+int rtdc_optim_step_advance(long long* count, hipStream_t st);
 int rtdc_f32_to_bf16(const float* x, void* y, long long n, hipStream_t st);
 int rtdc_f32_to_bf16_t(const float* x, void* y, int R, int C, hipStream_t st);
 int rtdc_bf16_transpose_multi(const void* const* src, void* const* dst, const int* R, const int* C, int n,
@@ -434,6 +442,59 @@ static void sgd(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, c10::optiona
                     (float)wd, nesterov, first, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
                     (const float*)(uintptr_t)clip_ptr, cur_stream()),
            "sgd");
+}
+// capturable variants (FusedAdamW / FusedSGD capturable=True): lr, the bias corrections and the step
+// number come from device tables indexed by the device step counter `count` (kernels/optim.hip
+// DevStep) instead of host scalars, so a replayed hipGraph does not freeze them
+static const float* check_lr_table(const Tensor& count, const Tensor& lr_tab, int64_t group, const char* op) {
+  TORCH_CHECK(count.is_cuda() && count.scalar_type() == at::kLong && count.numel() >= 1, op,
+              ": count must be an int64 GPU tensor");
+  TORCH_CHECK(lr_tab.is_cuda() && lr_tab.scalar_type() == at::kFloat && lr_tab.is_contiguous() && lr_tab.dim() == 2 &&
+                  lr_tab.size(1) >= 1 && group >= 0 && group < lr_tab.size(0) && lr_tab.size(1) <= INT32_MAX,
+              op, ": lr table must be a contiguous fp32 [n_groups, L] GPU tensor holding row `group`");
+  return lr_tab.data_ptr<float>() + group * lr_tab.size(1);
+}
+static void adamw_dev(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, Tensor m, Tensor v,
+                      c10::optional<Tensor> shadow, Tensor count, Tensor lr_tab, int64_t group, Tensor bc,
+                      int64_t step_off, double b1, double b2, double eps, double wd, double grad_scale,
+                      int64_t skip_ptr, int64_t clip_ptr, uint64_t seed) {
+  check_chunks(chunks, nchunks, "adamw_dev");
+  TORCH_CHECK(m.scalar_type() == v.scalar_type(), "adamw_dev: exp_avg is ", m.scalar_type(), " but exp_avg_sq is ",
+              v.scalar_type());
+  TORCH_CHECK(m.scalar_type() == at::kFloat || m.scalar_type() == at::kBFloat16,
+              "adamw_dev: optimizer state must be float32 or bfloat16, got ", m.scalar_type());
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat,
+              "adamw_dev: fp32 parameters and gradients");
+  const float* lr_row = check_lr_table(count, lr_tab, group, "adamw_dev");
+  TORCH_CHECK(bc.is_cuda() && bc.scalar_type() == at::kFloat && bc.is_contiguous() && bc.dim() == 2 &&
+                  bc.size(1) == 2 && bc.size(0) >= 1 && bc.size(0) <= INT32_MAX,
+              "adamw_dev: bias-correction table must be a contiguous fp32 [Lbc, 2] GPU tensor");
+  TORCH_CHECK(step_off <= 0 && step_off > INT32_MIN, "adamw_dev: step_off must be <= 0");
+  check_rc(rtdc_adamw_dev(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr(),
+                          v.data_ptr(), m.scalar_type() == at::kBFloat16, ptr_or_null(shadow),
+                          (const long long*)count.data_ptr<int64_t>(), lr_row, (int)lr_tab.size(1),
+                          bc.data_ptr<float>(), (int)bc.size(0), (int)step_off, (float)b1, (float)b2, (float)eps,
+                          (float)wd, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
+                          (const float*)(uintptr_t)clip_ptr, (unsigned long long)seed, cur_stream()),
+           "adamw_dev");
+}
+static void sgd_dev(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, c10::optional<Tensor> buf,
+                    c10::optional<Tensor> shadow, Tensor count, Tensor lr_tab, int64_t group, double momentum,
+                    double dampening, double wd, bool nesterov, bool first, double grad_scale, int64_t skip_ptr,
+                    int64_t clip_ptr) {
+  check_chunks(chunks, nchunks, "sgd_dev");
+  const float* lr_row = check_lr_table(count, lr_tab, group, "sgd_dev");
+  check_rc(rtdc_sgd_dev(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(),
+                        (float*)ptr_or_null(buf), ptr_or_null(shadow), (const long long*)count.data_ptr<int64_t>(),
+                        lr_row, (int)lr_tab.size(1), (float)momentum, (float)dampening, (float)wd, nesterov, first,
+                        (float)grad_scale, (const int*)(uintptr_t)skip_ptr, (const float*)(uintptr_t)clip_ptr,
+                        cur_stream()),
+           "sgd_dev");
+}
+static void optim_step_advance(Tensor count) {
+  TORCH_CHECK(count.is_cuda() && count.scalar_type() == at::kLong && count.numel() >= 1,
+              "optim_step_advance: count must be an int64 GPU tensor");
+  check_rc(rtdc_optim_step_advance((long long*)count.data_ptr<int64_t>(), cur_stream()), "optim_step_advance");
 }
 static void f32_to_bf16(Tensor x, Tensor y) {
   check_rc(rtdc_f32_to_bf16(x.data_ptr<float>(), y.data_ptr(), (long long)x.numel(), cur_stream()), "f32_to_bf16");
@@ -1171,6 +1232,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("shadow"), py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("wd"),
         py::arg("nesterov"), py::arg("first"), py::arg("grad_scale"), py::arg("skip_ptr") = 0,
         py::arg("clip_ptr") = 0);
+  m.def("adamw_dev", &adamw_dev, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("m"),
+        py::arg("v"), py::arg("shadow"), py::arg("count"), py::arg("lr_tab"), py::arg("group"), py::arg("bc"),
+        py::arg("step_off"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"),
+        py::arg("skip_ptr") = 0, py::arg("clip_ptr") = 0, py::arg("seed") = 0);
+  m.def("sgd_dev", &sgd_dev, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("buf"),
+        py::arg("shadow"), py::arg("count"), py::arg("lr_tab"), py::arg("group"), py::arg("momentum"),
+        py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("first"), py::arg("grad_scale"),
+        py::arg("skip_ptr") = 0, py::arg("clip_ptr") = 0);
+  m.def("optim_step_advance", &optim_step_advance);
   m.def("f32_to_bf16", &f32_to_bf16);
   m.def("f32_to_bf16_t", &f32_to_bf16_t);
   m.def("bf16_transpose_multi", &bf16_transpose_multi);

@@ -36,14 +36,50 @@ struct Chunk {
 };
 static_assert(sizeof(Chunk) == 24, "chunk table rows are 3 x int64");
 
+// ---- device-resident step state (FusedAdamW / FusedSGD capturable=True) ----------------------
+// The per-step hyper-parameters of the kernels below - lr, and AdamW's 1 - b1^t and
+// sqrt(1 - b2^t) - are host scalars passed by value: a replayed hipGraph would freeze them.  The
+// DEV = true instantiations read them from tables instead, indexed by a device step counter that
+// optim_step_advance_kernel increments at the end of every step (eager or replayed).  The tables
+// are built on the host from the very doubles the host path converts to fp32 (optim/schedule.py),
+// and the per-element arithmetic is the DEV = false code, so both paths give the same bits.  No
+// device pow / cos: those are not correctly rounded.
+struct DevStep {
+  const long long* count;  // completed optimizer steps
+  const float* lr;         // this param group's row of the lr table: lr[k] is the (k + 1)-th step's, k < L
+  const float* bc;         // rows t = 1 .. Lbc of {1 - b1^t, sqrt(1 - b2^t)} (both 1.0f from row Lbc on); SGD: null
+  int L, Lbc;
+  int step_off;  // (step number of this launch's parameters) - (optimizer step number): <= 0, replay-invariant
+};
+
+// Read once per block, before the chunk loop (wave-uniform addresses: scalar loads).  Both indices
+// are clamped into their tables whatever the counter holds.
+__device__ __forceinline__ long long dev_step(const DevStep& ds, float& lr) {
+  const long long n = *ds.count;
+  const long long k = n < 0 ? 0 : (n < ds.L ? n : ds.L - 1);
+  lr = ds.lr[k];
+  return n + 1 + ds.step_off;  // the Adam step number t of this launch's parameters
+}
+__device__ __forceinline__ void dev_bias(const DevStep& ds, long long t, float& bc1, float& bc2_sqrt) {
+  const long long r = (t < 1 ? 1 : (t < ds.Lbc ? t : ds.Lbc)) - 1;
+  bc1 = ds.bc[2 * r];
+  bc2_sqrt = ds.bc[2 * r + 1];
+}
+
+__global__ void optim_step_advance_kernel(long long* count) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *count += 1;
+}
+
+template <bool DEV>
 __global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ chunks, int nchunks,
                                                    float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    bf16_t* __restrict__ shadow, float lr, float b1,
                                                    float b2, float eps, float wd, float bc1,
                                                    float bc2_sqrt, float grad_scale, const int* skip,
-                                                   const float* __restrict__ clip) {
+                                                   const float* __restrict__ clip, const DevStep ds) {
   if (comm_poisoned(skip)) return;
+  if constexpr (DEV) dev_bias(ds, dev_step(ds, lr), bc1, bc2_sqrt);
   // clip (optional): {total_norm, coef} of gradnorm_finalize_kernel - the clip coefficient folds
   // into the gradient multiply
   const float gs = clip ? grad_scale * clip[1] : grad_scale;
@@ -107,12 +143,18 @@ __device__ __forceinline__ uint32_t philox_word(const uint4 r, int w) {
   return w == 0 ? r.x : (w == 1 ? r.y : (w == 2 ? r.z : r.w));
 }
 
+template <bool DEV>
 __global__ __launch_bounds__(256) void adamw_bf16state_kernel(
     const Chunk* __restrict__ chunks, int nchunks, float* __restrict__ p, const float* __restrict__ g,
     bf16_t* __restrict__ m, bf16_t* __restrict__ v, bf16_t* __restrict__ shadow, float lr, float b1, float b2,
     float eps, float wd, float bc1, float bc2_sqrt, float grad_scale, const int* skip,
-    const float* __restrict__ clip, uint64_t seed, uint64_t step) {
+    const float* __restrict__ clip, uint64_t seed, uint64_t step, const DevStep ds) {
   if (comm_poisoned(skip)) return;
+  if constexpr (DEV) {
+    const long long t = dev_step(ds, lr);
+    dev_bias(ds, t, bc1, bc2_sqrt);
+    step = (uint64_t)t;  // the Philox step word: the same number the host path passes
+  }
   const float gs = clip ? grad_scale * clip[1] : grad_scale;
   const float step_size = lr / bc1;
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
@@ -183,13 +225,15 @@ __global__ __launch_bounds__(256) void adamw_bf16state_kernel(
 
 // torch SGD: d = g*s + wd*p ; buf = first ? d : mom*buf + (1-damp)*d ; d = nesterov ? d + mom*buf : buf
 // p -= lr*d
+template <bool DEV>
 __global__ __launch_bounds__(256) void sgd_kernel(const Chunk* __restrict__ chunks, int nchunks,
                                                  float* __restrict__ p, const float* __restrict__ g,
                                                  float* __restrict__ buf, bf16_t* __restrict__ shadow,
                                                  float lr, float momentum, float dampening, float wd,
                                                  int nesterov, int first, float grad_scale, const int* skip,
-                                                 const float* __restrict__ clip) {
+                                                 const float* __restrict__ clip, const DevStep ds) {
   if (comm_poisoned(skip)) return;
+  if constexpr (DEV) dev_step(ds, lr);
   const float gs = clip ? grad_scale * clip[1] : grad_scale;
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const Chunk c = chunks[ci];
@@ -428,8 +472,9 @@ extern "C" int rtdc_adamw(const void* chunks, int nchunks, float* p, const float
                           float bc1, float bc2_sqrt, float grad_scale, const int* skip, const float* clip,
                           hipStream_t st) {
   if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
-                     nchunks, p, g, m, v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, skip, clip);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
+                     nchunks, p, g, m, v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, skip, clip,
+                     DevStep{});
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -438,9 +483,9 @@ extern "C" int rtdc_adamw_bf16state(const void* chunks, int nchunks, float* p, c
                                     float bc2_sqrt, float grad_scale, const int* skip, const float* clip,
                                     unsigned long long seed, unsigned long long step, hipStream_t st) {
   if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(adamw_bf16state_kernel, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
+  hipLaunchKernelGGL(adamw_bf16state_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
                      nchunks, p, g, (bf16_t*)m, (bf16_t*)v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt,
-                     grad_scale, skip, clip, (uint64_t)seed, (uint64_t)step);
+                     grad_scale, skip, clip, (uint64_t)seed, (uint64_t)step, DevStep{});
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -449,9 +494,50 @@ extern "C" int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* 
                         int nesterov, int first, float grad_scale, const int* skip, const float* clip,
                         hipStream_t st) {
   if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
+  hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
                      nchunks, p, g, buf, (bf16_t*)shadow, lr, momentum, dampening, wd, nesterov, first,
-                     grad_scale, skip, clip);
+                     grad_scale, skip, clip, DevStep{});
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// ---- capturable variants: lr / bias corrections / step number from the device tables (DevStep) ----
+// lr_row: this param group's row of the [n_groups, L] lr table; bc: [Lbc, 2] (AdamW).  m_bf16: the
+// moments are bf16 (adamw_bf16state_kernel; its Philox step word is the device step number).
+extern "C" int rtdc_adamw_dev(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v,
+                              int m_bf16, void* shadow, const long long* count, const float* lr_row, int L,
+                              const float* bc, int Lbc, int step_off, float b1, float b2, float eps, float wd,
+                              float grad_scale, const int* skip, const float* clip, unsigned long long seed,
+                              hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  if (count == nullptr || lr_row == nullptr || bc == nullptr || L < 1 || Lbc < 1) return 1;
+  const DevStep ds{count, lr_row, bc, L, Lbc, step_off};
+  if (m_bf16)
+    hipLaunchKernelGGL(adamw_bf16state_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, st,
+                       (const Chunk*)chunks, nchunks, p, g, (bf16_t*)m, (bf16_t*)v, (bf16_t*)shadow, 0.f, b1, b2, eps,
+                       wd, 1.f, 1.f, grad_scale, skip, clip, (uint64_t)seed, (uint64_t)0, ds);
+  else
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks, nchunks,
+                       p, g, (float*)m, (float*)v, (bf16_t*)shadow, 0.f, b1, b2, eps, wd, 1.f, 1.f, grad_scale, skip,
+                       clip, ds);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_sgd_dev(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow,
+                            const long long* count, const float* lr_row, int L, float momentum, float dampening,
+                            float wd, int nesterov, int first, float grad_scale, const int* skip, const float* clip,
+                            hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  if (count == nullptr || lr_row == nullptr || L < 1) return 1;
+  const DevStep ds{count, lr_row, nullptr, L, 0, 0};
+  hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks, nchunks, p, g,
+                     buf, (bf16_t*)shadow, 0.f, momentum, dampening, wd, nesterov, first, grad_scale, skip, clip, ds);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// count += 1 on stream st: the last launch of a capturable optimizer step
+extern "C" int rtdc_optim_step_advance(long long* count, hipStream_t st) {
+  if (count == nullptr) return 1;
+  hipLaunchKernelGGL(optim_step_advance_kernel, dim3(1), dim3(64), 0, st, count);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -36,6 +36,13 @@ bf16 moment state (`FusedAdamW(state_dtype=torch.bfloat16)`, off by default): `e
 Philox bits that are a pure function of (rounding_seed, step, flat element index) - the rule and
 its NumPy twin are in ops/random.py, the kernel is `adamw_bf16state_kernel`.  With bf16 state the
 CPU also steps over the flat buffers (every element needs its flat index).
+
+Learning-rate schedules (`lr_schedule=`, optim/schedule.py; off by default): `step()` first writes
+`group["lr"] = base_lr * f(step_count)` and then runs the code above unchanged.  `capturable=True`
+(off by default) replaces the per-step host scalars of the native launches - lr, AdamW's two bias
+corrections, the bf16-state kernel's step word - by device tables indexed with a device step
+counter that a one-thread kernel increments after the last update launch of every step, so a
+step captured into a hipGraph keeps stepping them; the results are the host path's bit for bit.
 """
 from __future__ import annotations
 
@@ -51,9 +58,25 @@ from .flat import FlatParamSpace, space_of
 
 class _FlatOptimizer(torch.optim.Optimizer):
     _state_keys: tuple = ()
+    _counts_steps = False  # the state carries a per-parameter `step` (AdamW)
 
-    def __init__(self, params, defaults, max_grad_norm=None):
+    def __init__(self, params, defaults, max_grad_norm=None, lr_schedule=None, capturable=False):
         super().__init__(params, defaults)
+        # number of step() calls (host int; AdamW's load_state_dict restores it from the loaded
+        # per-parameter steps, FusedSGD's state has none: set `opt.step_count` after a load)
+        self._step_count = 0
+        # learning-rate schedule (optim/schedule.py): `group["lr"]` is rewritten from it at the
+        # start of every step.  Attributes, not param-group options: state_dict() and checkpoints
+        # keep their keys.
+        self._sched = None
+        # capturable=True (GPU): lr, bias corrections and the step number are read by the kernels
+        # from device tables indexed by a device step counter, so a step captured into a hipGraph
+        # keeps stepping them on replay.  `_dev` holds that state, `_captured` the parameters of
+        # captured launches (None: never captured - then nothing is ever read back).
+        self.capturable = bool(capturable)
+        self._dev = None
+        self._captured = None
+        self.lr_schedule = lr_schedule
         # clip the global gradient norm to this value inside the step (None / 0: off).  An
         # attribute, not a param-group option: state_dict() and checkpoints do not change.
         # Unlike torch.nn.utils.clip_grad_norm_, `p.grad` is left UNSCALED - the coefficient is
@@ -220,9 +243,127 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _init_extra(self, p, st) -> None:
         pass
 
+    # -- learning-rate schedule, step count, device-resident step state --------------------------
+    @property
+    def lr_schedule(self):
+        return None if self._sched is None else self._sched.schedule
+
+    @lr_schedule.setter
+    def lr_schedule(self, schedule) -> None:
+        """Attach (or with None detach) an `LRSchedule`; the groups' current `lr` become its base
+        learning rates."""
+        if schedule is None:
+            self._sched = None
+            return
+        from .schedule import LRSchedule, ScheduleBinding
+
+        if not isinstance(schedule, LRSchedule):
+            raise TypeError(f"lr_schedule must be an optim.schedule.LRSchedule, got {type(schedule).__name__}")
+        self._sched = ScheduleBinding(schedule, [g["lr"] for g in self.param_groups])
+
+    @property
+    def step_count(self) -> int:
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, n: int) -> None:
+        self._step_count = int(n)
+        if self._dev is not None:
+            self._dev["count"].fill_(self._step_count)
+
+    def get_last_lr(self) -> list:
+        return [g["lr"] for g in self.param_groups]
+
+    def _apply_schedule(self, n: int) -> None:
+        """group["lr"] of the n-th optimizer step."""
+        for g, lr in zip(self.param_groups, self._sched.lrs(n)):
+            g["lr"] = lr
+
+    def _begin_step(self, capturing: bool = False) -> None:
+        """Before the first launch of a step (`step()`; BackwardOverlap's first early update):
+        bring the host counters up to date with captured replays, write the scheduled `lr`, and
+        keep the device tables of a capturable optimizer current.  Idempotent within a step."""
+        if self._captured is not None and not capturing:
+            self._reconcile()
+        if self._sched is not None:
+            self._apply_schedule(self._step_count + 1)
+        if self.capturable and self._use_native():
+            self._ensure_dev(capturing)
+
+    def _ensure_dev(self, capturing: bool = False) -> dict:
+        """The device step state: `count` (int64, completed optimizer steps), `lr` (fp32
+        [n_groups, L]) and per (b1, b2) the bias-correction table.  Uploaded outside capture only;
+        a table a captured graph reads is updated in place or kept alive, never freed."""
+        from .schedule import bias_correction_table, lr_table
+
+        dev = self._dev
+        b = self._sched
+        # without a schedule the (one-column) table follows `group["lr"]`, which the caller may edit
+        key = (b.schedule, tuple(b.base_lrs)) if b is not None else (None, tuple(g["lr"] for g in self.param_groups))
+        if dev is not None and dev["lr_key"] == key:
+            return dev
+        if capturing:
+            raise RuntimeError("capturable optimizer: the device lr / bias-correction tables must be uploaded "
+                               "before capture - run an eager step first (utils.graphs.CapturedStep(warmup >= 1))")
+        device = self._all_params()[0].device
+        if dev is None:
+            dev = self._dev = {"count": torch.full((1,), self._step_count, dtype=torch.int64, device=device),
+                               "lr": None, "lr_key": None, "bc": {}, "retired": []}
+            for g in self.param_groups:
+                if "betas" in g and tuple(g["betas"]) not in dev["bc"]:
+                    b1, b2 = g["betas"]
+                    dev["bc"][(b1, b2)] = torch.from_numpy(bias_correction_table(b1, b2).copy()).to(device)
+        tab = torch.from_numpy(lr_table(key[1], key[0]))
+        if dev["lr"] is not None and dev["lr"].shape == tab.shape:
+            dev["lr"].copy_(tab)
+        else:
+            if dev["lr"] is not None:
+                dev["retired"].append(dev["lr"])
+            dev["lr"] = tab.to(device)
+        dev["lr_key"] = key
+        return dev
+
+    def _group_index(self, group) -> int:
+        for i, g in enumerate(self.param_groups):
+            if g is group:
+                return i
+        raise ValueError("param group does not belong to this optimizer")
+
+    def _end_step(self, capturing: bool, steps_before) -> None:
+        """After the last launch of `step()`.  A captured step ran nothing: the host counters go
+        back to what the device holds, and the replays are added by `_reconcile`."""
+        if not capturing:
+            self._step_count += 1
+            return
+        cap = self._captured if self._captured is not None else set()
+        if steps_before is not None:
+            for p, n in list(self._steps.items()):
+                if n != steps_before.get(p, 0):
+                    cap.add(p)
+                    self._steps[p] = steps_before.get(p, 0)
+        self._captured = cap
+
+    def _reconcile(self) -> None:
+        """Replays of a captured step advance only the device counter: read it back (8 bytes) and
+        add the difference to `step_count` and to the steps of the parameters in the captured
+        launches; `group["lr"]` becomes the last step's."""
+        if self._dev is None or torch.cuda.is_current_stream_capturing():
+            return
+        n = int(self._dev["count"].item())
+        d = n - self._step_count
+        if d:
+            self._step_count = n
+            for p in self._captured:
+                if p in self._steps:
+                    self._steps[p] += d
+        if self._sched is not None and n > 0:
+            self._apply_schedule(n)
+
     # -- torch-compatible state dict -------------------------------------------------------
     def _materialize_steps(self) -> None:
         """Write the host step counters into the per-parameter `step` tensors torch keeps."""
+        if self._captured is not None:
+            self._reconcile()
         for p, n in self._steps.items():
             st = self.state.get(p)
             if st is not None:
@@ -310,6 +451,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
             st = self.state.get(p)
             if st and "step" in st:
                 self._steps[p] = int(float(st["step"]))
+        if self._counts_steps:  # (also rewrites the device counter of a capturable optimizer)
+            self.step_count = max(self._steps.values(), default=0)
         if self._space is not None:
             for p in self._all_params():
                 st = self.state.get(p)
@@ -345,6 +488,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._launch_split(sp, launches)
         if ov is not None:
             ov.end_step()  # the compute stream waits for the updates that ran during backward
+        if native and self.capturable:
+            gpu_ext().optim_step_advance(self._dev["count"])  # behind every launch that read the counter
         sp.after_step()  # ZeRO-1: gather the updated shards
         bump_generation()  # masters / shadows changed in place: K-major weight images are stale
 
@@ -526,12 +671,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
 class FusedAdamW(_FlatOptimizer):
     _state_keys = ("exp_avg", "exp_avg_sq")
+    _counts_steps = True
 
     def _init_extra(self, p, st) -> None:
         self._steps.setdefault(p, 0)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 maximize=False, max_grad_norm=None, state_dtype=torch.float32, rounding_seed=0):
+                 maximize=False, max_grad_norm=None, state_dtype=torch.float32, rounding_seed=0,
+                 lr_schedule=None, capturable=False):
         """`max_grad_norm`: clip the global gradient norm inside the step (None / 0: off; settable
         later as `opt.max_grad_norm`).  `opt.grad_norm` then holds the pre-clip norm of the last
         step.  `p.grad` is left unscaled - the one visible difference from
@@ -546,14 +693,34 @@ class FusedAdamW(_FlatOptimizer):
         resumes are bit-identical, and the bits do not depend on how the chunk tables are cut.
         They do depend on the flat layout, so a replicated and a ZeRO-1 run (whose buckets are
         padded) are not promised equal bits.  Both are attributes, not param-group options:
-        `state_dict()` keeps torch's keys; a checkpoint resumes into the same `state_dtype`."""
+        `state_dict()` keeps torch's keys; a checkpoint resumes into the same `state_dtype`.
+
+        `lr_schedule`: an `optim.schedule.LRSchedule` (settable later as `opt.lr_schedule`): the
+        n-th step runs with `group["lr"] = base_lr * f(n - 1)`, written at the start of `step()` -
+        bit for bit a run whose caller set `group["lr"]` by hand.  The base rates are the groups'
+        `lr` when the schedule is attached; nothing is added to `param_groups` or the state.
+
+        `capturable=True` (GPU; the CPU accepts it and runs the host path): the kernels read lr,
+        `1 - b1**t`, `sqrt(1 - b2**t)` and the step number from device tables indexed by a device
+        step counter instead of host scalars (optim/schedule.py builds the tables from the same
+        doubles, so the results are the same bits), and the step may be captured into a hipGraph
+        (`utils.graphs.CapturedStep`) with the schedule and the bias corrections advancing on every
+        replay.  Replays advance only the device counter; `state_dict()`, `load_state_dict()` and the
+        next eager step read it back (8 bytes) and bring `step_count`, the per-parameter steps and
+        `group["lr"]` up to date.  Betas whose bias corrections need more than 2^22 table rows to
+        reach 1.0f raise ValueError."""
         if amsgrad or maximize:
             raise NotImplementedError("amsgrad/maximize are not supported by the fused kernel")
         if state_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"FusedAdamW state_dtype must be torch.float32 or torch.bfloat16, got {state_dtype!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
-                                      fused=None), max_grad_norm)
+                                      fused=None), max_grad_norm, lr_schedule, capturable)
+        if capturable:  # (host tables, cached per betas: refuses betas that need too many rows)
+            from .schedule import bias_correction_table
+
+            for g in self.param_groups:
+                bias_correction_table(*g["betas"])
         self.state_dtype = state_dtype
         self.rounding_seed = int(rounding_seed) & ((1 << 64) - 1)
 
@@ -566,6 +733,21 @@ class FusedAdamW(_FlatOptimizer):
         b1, b2 = group["betas"]
         wd = group["weight_decay"]
         out = []
+        if self.capturable:
+            # device path: lr = table[group][count], bias corrections = row t, t = count + 1 + off
+            dev, gi = self._dev, self._group_index(group)
+            bc = dev["bc"].get((b1, b2))
+            if bc is None:
+                raise RuntimeError(f"capturable FusedAdamW: betas {(b1, b2)} changed after construction")
+            now = self._step_count + 1  # the optimizer step these launches belong to
+            for step, sub in self._count(ps).items():
+                def fn(chunks, n, clip=0, group=group, gi=gi, bc=bc, b1=b1, b2=b2, wd=wd, off=step - now):
+                    ext.adamw_dev(chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"],
+                                  sp.shadow, dev["count"], dev["lr"], gi, bc, off, b1, b2, group["eps"], wd,
+                                  sp.grad_scale, sp.skip_ptr, clip, self.rounding_seed)
+
+                out.append((sub, [wd != 0.0] * len(sub), fn))
+            return out
         for step, sub in self._count(ps).items():
             def fn(chunks, n, clip=0, group=group, b1=b1, b2=b2, wd=wd, step=step):
                 ext.adamw(chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"],
@@ -653,11 +835,18 @@ class FusedAdamW(_FlatOptimizer):
                 loss = closure()
         flush_wgrads()  # weight gradients deferred into a grouped launch (normally flushed by backward's end)
         if self._flat_mode():
-            if self._use_native() and torch.cuda.is_current_stream_capturing():
+            capturing = self._use_native() and torch.cuda.is_current_stream_capturing()
+            if capturing and not self.capturable:
                 raise RuntimeError("FusedAdamW computes bias corrections on the host per step: not graph-capturable "
-                                   "(use eager steps, or FusedSGD inside utils.graphs.CapturedStep)")
+                                   "(construct it with capturable=True, use eager steps, or FusedSGD inside "
+                                   "utils.graphs.CapturedStep)")
+            self._begin_step(capturing)
+            before = dict(self._steps) if capturing else None
             self._flat_step()
+            self._end_step(capturing, before)
             return loss
+        self._begin_step()
+        self._step_count += 1
         coef = self._plain_prelude()
         for group in self.param_groups:
             b1, b2 = group["betas"]
@@ -685,14 +874,17 @@ class FusedSGD(_FlatOptimizer):
             super().init_state()
 
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 maximize=False, max_grad_norm=None):
+                 maximize=False, max_grad_norm=None, lr_schedule=None, capturable=False):
         """`max_grad_norm`: as in `FusedAdamW` (clipping inside the step, `p.grad` left unscaled);
-        a clipped FusedSGD step stays capturable in `utils.graphs.CapturedStep`."""
+        a clipped FusedSGD step stays capturable in `utils.graphs.CapturedStep`.  `lr_schedule`,
+        `capturable`: as in `FusedAdamW`.  A constant-lr step captures either way; with a
+        non-constant schedule only `capturable=True` does (a host `lr` would freeze in the graph).
+        SGD's state has no step number: after `load_state_dict` set `opt.step_count` yourself."""
         if maximize:
             raise NotImplementedError("maximize is not supported by the fused kernel")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, maximize=False, foreach=None, differentiable=False,
-                                      fused=None), max_grad_norm)
+                                      fused=None), max_grad_norm, lr_schedule, capturable)
 
     def _native_launches(self, group, ps) -> list:
         sp, ext = self._space, gpu_ext()
@@ -709,6 +901,16 @@ class FusedSGD(_FlatOptimizer):
             for p in fresh:
                 self._bind_state(p)
         out = []
+        if self.capturable:  # device path: lr = table[group][count]
+            dev, gi = self._dev, self._group_index(group)
+            for sub, first in parts:
+                def fn(chunks, n, clip=0, group=group, gi=gi, mom=mom, wd=wd, first=first):
+                    ext.sgd_dev(chunks, n, sp.data, sp.grad, self._bufs["momentum_buffer"] if mom != 0.0 else None,
+                                sp.shadow, dev["count"], dev["lr"], gi, mom, group["dampening"], wd,
+                                group["nesterov"], first, sp.grad_scale, sp.skip_ptr, clip)
+
+                out.append((sub, [wd != 0.0] * len(sub), fn))
+            return out
         for sub, first in parts:
             def fn(chunks, n, clip=0, group=group, mom=mom, wd=wd, first=first):
                 ext.sgd(chunks, n, sp.data, sp.grad, self._bufs["momentum_buffer"] if mom != 0.0 else None,
@@ -765,8 +967,17 @@ class FusedSGD(_FlatOptimizer):
                 loss = closure()
         flush_wgrads()  # weight gradients deferred into a grouped launch (normally flushed by backward's end)
         if self._flat_mode():
+            native = self._use_native()
+            capturing = native and torch.cuda.is_current_stream_capturing()
+            if capturing and not self.capturable and self._sched is not None and not self._sched.schedule.is_constant:
+                raise RuntimeError("FusedSGD with a learning-rate schedule: a captured step would freeze lr "
+                                   "(construct it with capturable=True)")
+            self._begin_step(capturing)
             self._flat_step()
+            self._end_step(capturing and native and self.capturable, None)
             return loss
+        self._begin_step()
+        self._step_count += 1
         coef = self._plain_prelude()
         for group in self.param_groups:
             mom = group["momentum"]

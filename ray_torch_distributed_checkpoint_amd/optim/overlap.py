@@ -130,6 +130,8 @@ class BackwardOverlap:
         if not ps:
             return
         dev = self.sp.device
+        # this step's scheduled lr / device tables, before its first launch (step() runs later)
+        self.opt._begin_step()
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))  # behind the kernels that wrote these gradients
         self.stream.wait_event(ev)

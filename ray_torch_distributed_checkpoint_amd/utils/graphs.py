@@ -12,8 +12,14 @@ state a replay would otherwise freeze are made device-resident:
   mode) and the captured step ends with `base += consumed`, so each replay draws new masks
   that are bit-identical to the eager sequence;
 * gradients: the flat buffer is overwritten in place every step (ops/gradbuf), no memset;
-* optimizer: FusedSGD (constant lr) is graph-safe; FusedAdamW's bias correction is a host
-  scalar per step, so it refuses capture.
+* optimizer: the step count moves to a device int64 and the values derived from it to host-built
+  device tables (`FusedAdamW(capturable=True)` / `FusedSGD(capturable=True)`, optim/schedule.py):
+  the kernels read lr and AdamW's bias corrections by the counter, and the captured step ends
+  with `count += 1`, so a replay follows the learning-rate schedule and the bias corrections
+  bit for bit like the eager sequence; the host counters are read back (8 bytes) by
+  `state_dict()` or the next eager step.  Without `capturable=True`, FusedSGD with a constant lr
+  is graph-safe as before, FusedAdamW (host bias corrections) and a scheduled FusedSGD refuse
+  capture.
 
 Inputs must be static tensors: copy each new batch into `step.inputs[...]` before `replay()`.
 

@@ -76,6 +76,19 @@ class WorkloadConfig:
     # micro-batches per optimizer step (optim.GradAccumulator): each step draws this many batches,
     # adds their gradients in place in the flat buffer and applies their mean
     grad_accum_steps: int = 1
+    # learning-rate schedule over the optimizer steps (optim/schedule.py): "constant" | "cosine" |
+    # "linear", with `warmup_steps` of linear warmup and a decay to min_lr_ratio x lr that ends at step
+    # `lr_total_steps` (None: `steps`).  "constant" without warmup attaches no schedule at all.
+    lr_schedule: str = "constant"
+    warmup_steps: int = 0
+    min_lr_ratio: float = 0.0
+    lr_total_steps: Optional[int] = None
+    # GPU: build the fused optimizer with capturable=True (lr, bias corrections and the step number read
+    # from device tables by a device step counter: the same bits, and the step may be captured into a
+    # hipGraph).  Off by default: the device-table kernels measured 0.5 us (about 1 %) behind the
+    # host-scalar ones at ResNet-18 size, and a step ends with one more tiny launch
+    # (profiles/adamw_capturable_ab.md).
+    opt_capturable: bool = False
 
     @classmethod
     def from_dict(cls, d: dict) -> "WorkloadConfig":
@@ -84,6 +97,27 @@ class WorkloadConfig:
 
 
 _OPT_STATE_DTYPES = {"fp32": "float32", "bf16": "bfloat16"}  # option value -> torch dtype name
+
+_LR_SCHEDULES = ("constant", "cosine", "linear")
+
+
+def make_schedule(cfg: WorkloadConfig):
+    """The `LRSchedule` of a config; None for the default (constant, no warmup): then no schedule
+    object exists and the optimizer runs exactly as before."""
+    from .optim import LRSchedule
+
+    if cfg.lr_schedule not in _LR_SCHEDULES:
+        raise ValueError(f"lr_schedule must be one of {list(_LR_SCHEDULES)}, got {cfg.lr_schedule!r}")
+    w = int(cfg.warmup_steps or 0)
+    if cfg.lr_schedule == "constant" and w == 0:
+        return None
+    total = int(cfg.lr_total_steps or cfg.steps)
+    if cfg.lr_schedule == "cosine":
+        return LRSchedule.warmup_cosine(w, total, cfg.min_lr_ratio)
+    if cfg.lr_schedule == "linear":
+        return LRSchedule.warmup_linear(w, total, cfg.min_lr_ratio)
+    return LRSchedule.warmup_linear(w, total, 1.0)  # constant after the warmup
+
 
 _DEFAULTS = {
     # name prefix: (batch/worker, seq_len or image side, lr)
@@ -242,6 +276,12 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     S = cfg.seq_len or S0
     lr = cfg.lr or lr0
     clip = cfg.max_grad_norm or None
+    # the schedule rewrites group["lr"] on the host before every step (host-scalar kernels);
+    # opt_capturable moves lr, the bias corrections and the step number into device tables (GPU only)
+    sched = make_schedule(cfg)
+    sched_kw = {} if sched is None else {"lr_schedule": sched}
+    if cfg.opt_capturable and torch.device(device).type == "cuda":
+        sched_kw["capturable"] = True
     torch.manual_seed(cfg.seed)
     name = cfg.model
     if name.startswith("resnet18"):
@@ -249,7 +289,7 @@ def build(cfg: WorkloadConfig, device) -> Workload:
 
         # "-tiny" = the full network on 32x32 images (the GEMM tiles need >= 64 channels)
         model = ResNet18(num_classes=cfg.num_classes).to(device)
-        opt = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=5e-5, max_grad_norm=clip)
+        opt = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=5e-5, max_grad_norm=clip, **sched_kw)
         data = SyntheticImages(cfg.dataset_size, S, cfg.num_classes, device, seed=cfg.seed)
         return Workload(model, opt, data, B, S, 0, model.flops_per_sample(S),
                         lambda net, x, y: ops.cross_entropy(net(x), y))
@@ -268,7 +308,7 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     else:
         raise ValueError(f"unknown workload model {name!r}")
     opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=clip,
-                     state_dtype=getattr(torch, _OPT_STATE_DTYPES[cfg.opt_state_dtype]), rounding_seed=cfg.seed)
+                     state_dtype=getattr(torch, _OPT_STATE_DTYPES[cfg.opt_state_dtype]), rounding_seed=cfg.seed, **sched_kw)
     data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed, doc_len=cfg.doc_len or None)
     # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle)
     return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S,
@@ -398,6 +438,8 @@ def restore(core, opt, stream, checkpoint, mode: str, device, rank: int) -> int:
             if not _set_rng(tr["rng"], rank, device):
                 torch.manual_seed(int(tr["step"]) * 1000003 + rank)
             step = int(tr["step"])
+            if not getattr(opt, "_counts_steps", True):
+                opt.step_count = step  # (SGD's state carries no step number: the schedule resumes from the trainer's)
     sp = getattr(opt, "flat_space", None) or getattr(core.parameters().__next__(), "_rtdc_space", None)
     if sp is not None:
         sp.refresh_shadows()  # bf16 compute copies of the restored fp32 masters
@@ -434,6 +476,7 @@ def train_loop_per_worker(config: dict):
     pending = None  # this rank's in-flight async save (at most one: bounded snapshot memory)
     losses = []
     clipping = bool(cfg.max_grad_norm)
+    scheduled = getattr(opt, "lr_schedule", None) is not None
     norms = []  # per-step pre-clip gradient norms (device scalars, read with the losses)
     t_last, n_last = time.perf_counter(), 0
     k = int(cfg.grad_accum_steps or 1)
@@ -484,6 +527,8 @@ def train_loop_per_worker(config: dict):
             metrics["tokens_per_s"] = round(metrics["samples_per_s"] * wl.tokens_per_sample, 1)
         if clipping:
             metrics["grad_norm"], metrics["grad_norms"] = gnorms[-1], gnorms
+        if scheduled:
+            metrics["lr"] = opt.get_last_lr()[0]  # the last step's, group 0
         losses, norms, n_last = [], [], 0
         ck = None
         if do_ckpt:
@@ -524,7 +569,9 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    bucket_cap_mb: float = 32.0, zero_stage: int = -1, progress_timeout_s: float | None = 300.0,
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
                    report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
-                   doc_len: int | None = None, opt_state_dtype: str = "fp32", grad_accum_steps: int = 1):
+                   doc_len: int | None = None, opt_state_dtype: str = "fp32", grad_accum_steps: int = 1,
+                   lr_schedule: str = "constant", warmup_steps: int = 0, min_lr_ratio: float = 0.0,
+                   lr_total_steps: int | None = None, opt_capturable: bool = False):
     """`train_fashion_mnist`'s counterpart for the bf16 workloads (R/my_ray_module.py:216-251).
     zero_stage -1: `default_zero_stage(model, num_workers)`.  max_grad_norm: clip the global
     gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
@@ -535,7 +582,15 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     stochastic rounding keyed by `seed`; the report rows are unchanged).  grad_accum_steps = k:
     every optimizer step accumulates k micro-batches in place (optim.GradAccumulator) and applies
     their mean; `steps` stays optimizer steps, a row's loss is the mean over its k micro-batches
-    and samples_per_s / tokens_per_s count k x the batch."""
+    and samples_per_s / tokens_per_s count k x the batch.  lr_schedule "constant" | "cosine" |
+    "linear" with `warmup_steps` of linear warmup and a decay to `min_lr_ratio` x lr that ends at
+    optimizer step `lr_total_steps` (None: `steps`): the report rows then carry `lr` (the row's last
+    step, group 0).  The schedule is a function of the step count that comes back with the optimizer
+    state, so an exact resume needs the same arguments and nothing else - resuming into a longer
+    `steps` needs the original `lr_total_steps` given explicitly.  The default (constant, no warmup)
+    attaches nothing: rows, checkpoints and bits are unchanged.  opt_capturable (GPU): the fused
+    optimizer reads lr, the bias corrections and the step number from device tables
+    (`capturable=True`): the same bits as the host path, and a step that may be captured."""
     if int(grad_accum_steps) < 1:
         raise ValueError(f"grad_accum_steps must be >= 1, got {grad_accum_steps}")
     if opt_state_dtype not in _OPT_STATE_DTYPES:
@@ -546,7 +601,11 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                          lr=lr, ckpt_every_n_steps=ckpt_every_n_steps, seed=seed, resume_mode=resume_mode,
                          checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
                          max_grad_norm=max_grad_norm or None, doc_len=doc_len or None,
-                         opt_state_dtype=opt_state_dtype, grad_accum_steps=int(grad_accum_steps))
+                         opt_state_dtype=opt_state_dtype, grad_accum_steps=int(grad_accum_steps),
+                         lr_schedule=lr_schedule, warmup_steps=int(warmup_steps or 0),
+                         min_lr_ratio=float(min_lr_ratio or 0.0), lr_total_steps=lr_total_steps or None,
+                         opt_capturable=bool(opt_capturable))
+    make_schedule(cfg)  # (argument errors here, not in the workers)
     run_config = train.RunConfig(
         name=name, storage_path=checkpoint_storage_path, verbose=verbose,
         checkpoint_config=train.CheckpointConfig(num_to_keep=num_checkpoints_to_keep,
@@ -585,13 +644,26 @@ def main(argv=None):
                     help="LMs: dtype of the fused AdamW's stored moments (bf16: stochastically rounded)")
     ap.add_argument("--grad-accum-steps", type=int, default=1,
                     help="micro-batches accumulated in place per optimizer step (default 1: off)")
+    ap.add_argument("--lr-schedule", default="constant", choices=list(_LR_SCHEDULES),
+                    help="learning-rate schedule over the optimizer steps (default: constant)")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="linear warmup steps of the schedule")
+    ap.add_argument("--min-lr-ratio", type=float, default=0.0,
+                    help="the schedule decays to this fraction of the learning rate")
+    ap.add_argument("--lr-total-steps", type=int, default=None,
+                    help="step at which the decay ends (default: --steps; give it explicitly when resuming into a "
+                         "longer --steps)")
+    ap.add_argument("--opt-capturable", action="store_true",
+                    help="GPU: fused optimizer with device-resident step count, lr and bias-correction tables "
+                         "(capturable=True; same bits as the default host path)")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
     use_gpu = torch.cuda.is_available() and not a.cpu
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
                          zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len,
-                         opt_state_dtype=a.opt_state_dtype, grad_accum_steps=a.grad_accum_steps)
+                         opt_state_dtype=a.opt_state_dtype, grad_accum_steps=a.grad_accum_steps,
+                         lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, min_lr_ratio=a.min_lr_ratio,
+                         lr_total_steps=a.lr_total_steps, opt_capturable=a.opt_capturable)
     print(res)
 
 

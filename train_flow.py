@@ -63,6 +63,18 @@ class RayTorchTrain(FlowSpec):
     grad_accum_steps = Parameter("grad_accum_steps", default=1,
                                  help="bf16 workloads: micro-batches accumulated in place per optimizer step; "
                                       "--steps stays optimizer steps (1: off)")
+    lr_schedule = Parameter("lr_schedule", default="constant",
+                            help="bf16 workloads: constant | cosine | linear learning-rate schedule over the optimizer "
+                                 "steps (optim/schedule.py)")
+    warmup_steps = Parameter("warmup_steps", default=0, help="bf16 workloads: linear warmup steps of the schedule")
+    min_lr_ratio = Parameter("min_lr_ratio", default=0.0,
+                             help="bf16 workloads: the schedule decays to this fraction of the learning rate")
+    lr_total_steps = Parameter("lr_total_steps", default=0,
+                               help="bf16 workloads: step at which the decay ends (0: --steps; give it explicitly "
+                                    "when resuming into a longer --steps)")
+    opt_capturable = Parameter("opt_capturable", default=0,
+                               help="bf16 workloads on the GPU: 1 = fused optimizer with device-resident step count, "
+                                    "lr and bias-correction tables (capturable=True; same bits as the host path)")
     batch_size_per_worker = Parameter("batch_size_per_worker", default=0,
                                       help="bf16 workloads: samples per worker per step (0: the model's default). "
                                            "--batch_size is the reference MLP's global batch")
@@ -120,7 +132,10 @@ class RayTorchTrain(FlowSpec):
                 zero_stage=int(self.zero_stage),
                 report_every_n_steps=int(self.report_every_n_steps) or None,
                 max_grad_norm=float(self.max_grad_norm) or None, doc_len=int(self.doc_len) or None,
-                opt_state_dtype=str(self.opt_state_dtype), grad_accum_steps=int(self.grad_accum_steps))
+                opt_state_dtype=str(self.opt_state_dtype), grad_accum_steps=int(self.grad_accum_steps),
+                lr_schedule=str(self.lr_schedule), warmup_steps=int(self.warmup_steps),
+                min_lr_ratio=float(self.min_lr_ratio), lr_total_steps=int(self.lr_total_steps) or None,
+                opt_capturable=bool(int(self.opt_capturable)))
         self.next(self.join)
 
     @step

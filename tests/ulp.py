@@ -24,6 +24,23 @@ The last section does the same for the attention kernels (attn_flash.hip and the
 with one difference said there: those kernels round to bf16 inside the computation, so their
 allowance is a per-element tensor derived from those roundings (`attn_ref`, `Judge.within`), not
 a multiple of an unrounded twin's error.  tests/test_attn_ulp_gpu.py runs the kernels against it.
+
+The GEMM section (at the end) puts the bf16 MFMA GEMMs and their fused epilogues (gemm_bf16.hip,
+gemm_8ph.h/.hip, gemm4b.hip, gemm8b.hip, gemm_f32.hip) under the first yardstick again - they
+accumulate in fp32 and round every output to bf16 once, split-K included (its slabs are fp32):
+* `gemm_ref` in float64 is the reference, in float32 (nothing rounded to bf16) the twin; the
+  epilogue is written in the kernels' order - bias, then beta * Cin, then the activation - with the
+  GELU of common.h (`gelu_sigmoid_arg`); it returns every output of the call (C, the saved
+  pre-activation or gelu', the column sums) and S, the sum of |terms| at the leaves;
+* bf16 outputs: `Judge.ulp`, k = 1, floor = FLOOR_GEMM x S (an element is a sum of K signed
+  products: |ref| / S has a median of a few percent and no lower bound); fp32 outputs:
+  `Judge.rel`, scale = S, R = K;
+* column sums: the fused arm (8-wave / one-barrier kernels, act 3 / 6, bf16 C) adds the fp32 values
+  before they are packed and is judged against the fp64 column sum of the unrounded product with
+  R = the rows a lane adds serially (GEMM_CS_ROWS, counted from tile_epilogue_bf16); every other
+  arm reduces the stored C and is judged against the fp64 column sum of the kernel's own C;
+* the case table (GEMM_*) is data shared by tests/test_ulp_cpu.py (twin condition, mutants) and
+  tests/test_gemm_ulp_gpu.py (the kernels).
 """
 from __future__ import annotations
 
@@ -895,3 +912,322 @@ def judge_attn(J, fams, shape, ref, twin, outs, names=("out", "dq", "dk", "dv"))
     """fams: the kernel that wrote each output, by output name (the WORST lines go by it)"""
     for n in names:
         J.within(fams[n], shape, n, outs.get(n), ref[n], twin[n], ref["allow_" + n])
+
+
+# ------------------------------------------------------------------------------- GEMM
+# C = act(alpha A.B + bias + beta Cin): an element is a sum of K signed products (plus the bias and
+# the residual), so it can be arbitrarily small against S = sum |terms|: what cancels is the K-term
+# sum itself.  Below FLOOR_GEMM x S an element is judged in ulps of that floor.  Measured on the
+# whole case table (tests/test_ulp_cpu.py::test_twin_gemm): the twin's worst error is 0.0107 ulp
+# at 2^-10, 0.0426 at 2^-12 and 0.164 at 2^-14, so 2^-12 is the smallest power of two under 2^-4.
+FLOOR_GEMM = 2.0 ** -12
+
+GEMM_MUTANTS = ("truncate", "drop_k_last", "cols_scaled", "bias_shift", "slab_bf16", "res_after_act",
+                "gelu_of_rounded", "colsum_rounded")
+GELU_ROOT = -0.75     # the bf16 number nearest the root of gelu' (-0.7518); its neighbours are +-2^-8
+GEMM_AUX_PLANTED = (GELU_ROOT, GELU_ROOT - 2.0 ** -8, GELU_ROOT + 2.0 ** -8, 0.0, 6.0, -6.0, 20.0, -20.0)
+
+
+def gelu_parts(x):
+    """(sigmoid, gelu') of the tanh-form GELU as common.h writes it: gelu_sigmoid_arg, gelu_tanh_grad"""
+    k0, k1 = _f32(0.7978845608028654), _f32(0.044715)
+    u = k0 * (k1 * x * x * x + x)
+    s = 1.0 / (1.0 + torch.exp(-2.0 * u))
+    return s, 2.0 * x * s * (1.0 - s) * k0 * (3.0 * k1 * x * x + 1.0) + s
+
+
+def gemm_alpha(alpha, alpha_dev=None) -> float:
+    """alpha as the kernels form it: a float, times the device scalar in fp32"""
+    a = _f32(alpha)
+    return a if alpha_dev is None else _f32(a * float(alpha_dev.float().reshape(-1)[0]))
+
+
+def _truncate_bf16(x):
+    return (x.float().contiguous().view(torch.int32) & -65536).view(torch.float32).to(x.dtype)
+
+
+def gemm_ref(dtype, A, B, a_kmajor=True, b_kmajor=True, *, alpha=1.0, alpha_dev=None, bias=None, Cin=None, beta=0.0,
+             act=0, aux_in=None, mutant="", slabs=4):
+    """gemm_bf16 / gemm_f32 with the fused epilogue.  A, B as stored: K-major [M, K] / [N, K] or
+    MN-major [K, M] / [K, N], leading batch dimensions allowed.  The order is epilogue4's and
+    tile_epilogue_bf16's: alpha x the sum, + bias, + beta Cin, then the activation (1 relu, 2 gelu
+    with the pre-activation as aux_out, 5 gelu with gelu' as aux_out, 3 / 6 / 4 x gelu'(aux_in) /
+    aux_in / [aux_in > 0]).  act 2 stores the rounded pre-activation but applies GELU to the
+    unrounded one (gemm_common.h epilogue4: store4 of v, then gelu_tanh(v)).
+    Returns C, aux_out, the column sums of C, and S = |alpha| |A| |B| + |bias| + |beta Cin| (x the
+    activation factor of act 3 / 6 / 4), with S_aux for aux_out, colsum_scale = colsum(S) and
+    S_rel, the scale of an fp32 C (S, but for act 3: see there).
+    `mutant`: a deliberate error (GEMM_MUTANTS), used only by tests/test_ulp_cpu.py."""
+    assert mutant == "" or mutant in GEMM_MUTANTS
+    tr = lambda t: t.transpose(-1, -2)
+    a = A.to(dtype) if a_kmajor else tr(A.to(dtype))   # [.., M, K]
+    b = tr(B.to(dtype)) if b_kmajor else B.to(dtype)   # [.., K, N]
+    K = a.shape[-1]
+    al = gemm_alpha(alpha, alpha_dev)
+    S = abs(al) * (a.abs() @ b.abs())
+    if mutant == "drop_k_last":
+        a = a.clone()
+        a[..., -8:, K - 1] = 0
+    if mutant == "slab_bf16":
+        per = -(-(K // 64) // slabs) * 64
+        v = sum(_rb(al * (a[..., k0:k0 + per] @ b[..., k0:k0 + per, :]), True) for k0 in range(0, K, per))
+    else:
+        v = al * (a @ b)
+    if bias is not None:
+        bb = bias.to(dtype)
+        S = S + bb.abs()
+        if mutant == "bias_shift":
+            bb = bb.clone()
+            bb[-8:] = bb[-16:-8]
+        v = v + bb
+    res = None
+    if Cin is not None and beta != 0.0:
+        res = _f32(beta) * Cin.to(dtype)
+        S = S + res.abs()
+        if mutant != "res_after_act":
+            v = v + res
+    aux_out = S_aux = S_rel = None
+    if act == 1:
+        C, aux_out, S_aux = v.clamp_min(0), v, S          # (gemm_f32 stores the pre-activation)
+    elif act == 2:
+        x = _rb(v, True) if mutant == "gelu_of_rounded" else v
+        C, aux_out, S_aux = x * gelu_parts(x)[0], v, S
+    elif act == 5:
+        s, g = gelu_parts(v)
+        # gelu' = s + x (...): terms of size <= 1 next to what v's own error moves (|gelu''| < 1.2)
+        C, aux_out, S_aux = v * s, g, S + 1.0
+    elif act in (3, 4, 6):
+        h = aux_in.to(dtype)
+        if act == 3:
+            s, f = gelu_parts(h)
+            # gelu' = s + x (...) is itself a sum of two terms that cancel at its root (-0.7518):
+            # next to it the fp32 twin is 1.3e-5 of S |gelu'| - above TWIN_REL_CEIL - so an fp32
+            # output is judged against S x the two terms' magnitudes (S_rel).  A bf16 output keeps
+            # S |gelu'| under its floor: the twin stays below 2^-4 ulp there.
+            S_rel = S * (s.abs() + (f - s).abs())
+        else:
+            f = h if act == 6 else (h > 0).to(dtype)
+        C, S = v * f, S * f.abs()
+    else:
+        assert act == 0
+        C = v
+    if mutant == "res_after_act" and res is not None:
+        C = C + res
+    if mutant == "cols_scaled":
+        C = C.clone()
+        C[..., -8:] *= 1.0 + 2.0 ** -7
+    if mutant == "truncate":
+        C = _truncate_bf16(C)
+    cs = (_rb(C, True) if mutant == "colsum_rounded" else C).sum(-2)
+    return {"C": C, "S": S, "S_rel": S if S_rel is None else S_rel, "aux_out": aux_out, "S_aux": S_aux, "colsum": cs,
+            "colsum_scale": S.sum(-2)}
+
+
+# -- inputs
+GEMM_GENS = ("randn", "range")
+
+
+def gemm_inputs(gen, M, N, K, seed=0, dev="cpu", bscale=1.0, batch=(), dtype=BF16):
+    """the logical operands a [.., M, K] and b [.., K, N] (`gemm_store` lays them out).
+    randn: plain (b x bscale).  range: row M // 3 of a x 2^-20, column 2 N // 3 of b x 2^10, and
+    (from two K-tiles on) one K-tile of a all zero - rows and columns that a whole-tensor
+    criterion does not see."""
+    g = torch.Generator().manual_seed(1009 * M + 31 * N + K + 7 * len(gen) + seed)
+    a = torch.randn(*batch, M, K, generator=g)
+    b = torch.randn(*batch, K, N, generator=g) * bscale
+    if gen == "range":
+        a[..., M // 3, :] *= 2.0 ** -20
+        b[..., :, 2 * N // 3] *= 2.0 ** 10
+        if K >= 128:
+            kt = (K // 64) // 2
+            a[..., :, 64 * kt:64 * kt + 64] = 0
+    else:
+        assert gen == "randn"
+    return a.to(dtype).to(dev), b.to(dtype).to(dev)
+
+
+def gemm_store(a, b, a_kmajor, b_kmajor):
+    """(A, B) as the kernel reads them: K-major [M, K] / [N, K] or MN-major [K, M] / [K, N]"""
+    tr = lambda t: t.transpose(-1, -2).contiguous()
+    return (a if a_kmajor else tr(a)), (tr(b) if b_kmajor else b)
+
+
+def gemm_aux_in(M, N, seed=0, dev="cpu"):
+    """randn with the bf16 numbers around the root of gelu' and 0, +-6, +-20 planted (twice each)"""
+    g = torch.Generator().manual_seed(977 * M + N + seed)
+    h = torch.randn(M, N, generator=g)
+    for j, v in enumerate(GEMM_AUX_PLANTED):
+        h[(7 * j) % M, (13 * j + 1) % N] = v
+        h[M - 1 - (5 * j) % M, N - 1 - (11 * j) % N] = v
+    return h.to(BF16).to(dev)
+
+
+# -- the epilogue variants: name -> what the call gets.  bias "bf16" / "f32"; cin "alias" (Cin is
+# C) / "sep"; colsum: also colsum_out.  "mul" (act 6) takes as aux_in the gelu' that the act-5
+# call of the same kernel stored (the saved-derivative round trip; on the CPU the twin's, rounded).
+GEMM_EPILOGUES = {
+    "plain": {},
+    "bias_bf16": {"bias": "bf16"},
+    "bias_f32": {"bias": "f32"},
+    "alpha": {"alpha": 0.5},
+    "alpha_dev": {"alpha": 0.5, "alpha_dev": 0.75},
+    "cin_alias": {"cin": "alias", "beta": 0.5},
+    "accumulate": {"cin": "alias", "beta": 1.0},
+    "cin_sep": {"cin": "sep", "beta": 0.5, "bias": "bf16"},
+    "relu": {"bias": "f32", "act": 1},
+    "gelu": {"bias": "bf16", "act": 2},
+    "gelu_save_grad": {"bias": "bf16", "act": 5},
+    "mul": {"act": 6, "colsum": True},
+    "gelu_bwd": {"act": 3, "colsum": True},
+    "relu_bwd": {"act": 4},
+    "gelu_bwd_res": {"act": 3, "cin": "sep", "beta": 1.0},   # the launcher sends it to cfg 0
+}
+GEMM_BWD_ACTS = (3, 4, 6)
+
+
+def gemm_case(gen, M, N, K, epi="plain", out_fp32=False, dev="cpu", bscale=None, aux_in=None, dtype=BF16):
+    """operands and epilogue inputs of one case, and the keyword arguments of gemm_ref for it.
+    With an activation b is scaled by K^-1/2 so that the pre-activations are O(1)."""
+    e = GEMM_EPILOGUES[epi]
+    act = e.get("act", 0)
+    if bscale is None:
+        bscale = K ** -0.5 if act else 1.0
+    a, b = gemm_inputs(gen, M, N, K, dev=dev, bscale=bscale, dtype=dtype)
+    g = torch.Generator().manual_seed(M + 3 * N + 5 * K + len(epi))
+    odt = F32 if out_fp32 else BF16
+    c = {"a": a, "b": b, "M": M, "N": N, "K": K, "epi": epi, "out_fp32": out_fp32, "act": act,
+         "colsum": bool(e.get("colsum")), "cin": e.get("cin"),
+         "alpha": e.get("alpha", 1.0), "beta": e.get("beta", 0.0), "bias": None, "Cin": None, "alpha_dev": None,
+         "aux_in": None}
+    if e.get("bias"):
+        bias = torch.randn(N, generator=g)
+        c["bias"] = (bias if e["bias"] == "f32" else bias.to(BF16)).to(dev)
+    if e.get("cin"):
+        c["Cin"] = torch.randn(M, N, generator=g).to(odt).to(dev)
+    if e.get("alpha_dev") is not None:
+        c["alpha_dev"] = torch.tensor([e["alpha_dev"]], dtype=F32, device=dev)
+    if act in GEMM_BWD_ACTS:
+        c["aux_in"] = gemm_aux_in(M, N, dev=dev).to(BF16 if dtype == BF16 else F32) if aux_in is None else aux_in
+    return c
+
+
+def gemm_ref_of(dtype, c, mutant=""):
+    return gemm_ref(dtype, c["a"], c["b"], True, False, alpha=c["alpha"], alpha_dev=c["alpha_dev"], bias=c["bias"],
+                    Cin=c["Cin"], beta=c["beta"], act=c["act"], aux_in=c["aux_in"], mutant=mutant)
+
+
+# -- the kernels' shapes (gemm_bf16.hip header, rtdc_gemm_bf16)
+GEMM_TILES = {0: (128, 128), 1: (256, 128), 2: (128, 256), 3: (256, 256), 4: (256, 64), 5: (64, 256),
+              6: (256, 256), 7: (256, 192), 8: (256, 256), 9: (256, 192), 10: (256, 256), 11: (256, 128),
+              12: (256, 256), 13: (256, 256)}
+GEMM_LAYOUTS = ((True, True), (True, False), (False, False), (False, True))   # (a_kmajor, b_kmajor)
+GEMM_KS = (64, 128, 192, 320)   # one K-tile, two, the peeled tails of cfg 12 / 13, five
+# rows a lane adds serially into the fused column sums: 2 (qa) x TMQ pairs per column run in
+# tile_epilogue_bf16; TMQ = SA / 16 with SA = 128 / WA and WA = the partial rows per row tile that
+# rtdc_gemm_bf16 reduces (2 at 256 columns, 4 at 192 / 128)
+GEMM_CS_ROWS = {6: 8, 8: 8, 10: 8, 12: 8, 13: 8, 7: 4, 9: 4, 11: 4}
+
+
+def gemm_tile_shapes(cfg):
+    """one axis ends in a tile of 8, the other in a tile that is 8 short"""
+    BM, BN = GEMM_TILES[cfg]
+    return [(BM + 8, 2 * BN - 8), (2 * BM - 8, BN + 8)]
+
+
+def gemm_cfg_runs_as(cfg, a_k, b_k, out_fp32, K=128):
+    """the configuration a forced tile_cfg runs as (the documented fall-backs of rtdc_gemm_bf16:
+    cfg 13 is forward only, cfg 11 needs a K-major A and a bf16 output - both then run as cfg 6),
+    or None where the launcher refuses (the persistent form needs two K-tiles)."""
+    if cfg == 13 and not (a_k and b_k):
+        cfg = 6
+    if cfg == 11 and (out_fp32 or not a_k):
+        cfg = 6
+    if cfg in (8, 9) and K < 128:
+        return None
+    return cfg
+
+
+def gemm_colsum_fallback_rows(M):
+    """rows a wave of colsum_partial_kernel (norm.hip) adds serially: M / 64 blocks (1..256), 4 waves"""
+    nblk = min(256, max(1, M // 64))
+    return -(-(-(-M // nblk)) // 4)
+
+
+GEMM_SPLITK_SHAPES = ((264, 264), (520, 392))
+GEMM_SPLITK_KS = (2048, 1984)                    # 32 K-tiles: split; 31: never
+GEMM_SPLITK_CFGS = (-1, 0, 6, 7, 10, 11, 12, 13)
+GEMM_PERSIST_MN = (4392, 4160)                   # 18 x 17 (22) tiles, the last row and column partial
+GEMM_PERSIST_KS = (128, 320)
+GEMM_EPI_SHAPE = (520, 392, 192)
+GEMM_EPI_CFGS = (0, 6, 7, 8, 10, 11, 12, 13)
+# automatic routes under the default knobs: (name, M, N, K, layout, epilogue, fp32 out, the forced
+# configuration it must equal bit for bit), worked out from pick_cfg / pick_cfg_few_rows
+GEMM_ROUTES = [
+    ("tail_split", 2048, 19200, 1024, (True, True), "plain", False, 12),       # 600 tiles: 2 rounds + 88 tiles
+    ("tail_split_bias", 2048, 19200, 1024, (True, True), "bias_bf16", False, 12),
+    ("few_rows_13", 2048, 4352, 512, (True, True), "plain", False, 13),        # 136 tiles: one partial round
+    ("few_rows_0", 512, 512, 512, (True, True), "plain", False, 0),            # at most half a round, K <= 4096
+    ("few_rows_7", 2048, 8448, 1024, (True, True), "plain", False, 7),         # 352 x 192-wide tiles
+    ("few_rows_6", 2048, 6400, 512, (True, False), "plain", False, 6),         # dgrad layout, 200 tiles
+    ("few_rows_11", 256, 384, 4160, (True, False), "plain", False, 11),        # K > 4096: 256x128 tiles
+    ("long_k_12", 512, 512, 2048, (True, True), "plain", True, 12),            # K >= 2048 forward
+]
+GEMM_BATCH = (3, 2, 136, 136, 128)               # outer, inner, M, N, K on cfg 0
+# grouped weight gradients dW[N, K] = dY[T, N]^T X[T, K]: (N, K) of each product
+GEMM_GROUP_SMALL = ((1000, 2736), (512, 768), (264, 520))     # 56 tiles: under one round
+GEMM_GROUP_BIG = ((4096, 4096), (1000, 2736), (2048, 1024))   # 332 tiles: the persistent grouped kernel
+GEMM_GROUP_TOKENS = (192, 2048)
+GEMM_F32_SHAPES = ((16, 512, 784), (16, 10, 512), (37, 70, 100), (37, 130, 100))   # (M, N, K)
+GEMM_F32_EPIS = ("plain", "relu", "relu_bwd", "accumulate")
+
+
+def gemm_cpu_cases():
+    """(label, gen, M, N, K, epilogue, fp32 out) of every case of the table, for the twin condition.
+    The multi-tile cases - persistent, automatic routes, grouped - are cut down to one 256x256
+    tile (the twin's error depends on K, the epilogue and the generator, not on the tile count)."""
+    out = []
+    tiles = sorted({s for cfg in GEMM_TILES for s in gemm_tile_shapes(cfg)})
+    for gen in GEMM_GENS:
+        for f32 in (False, True):
+            out += [("tile", gen, M, N, K, "plain", f32) for M, N in tiles for K in GEMM_KS]
+            out += [("splitk", gen, M, N, K, e, f32) for M, N in GEMM_SPLITK_SHAPES for K in GEMM_SPLITK_KS
+                    for e in ("plain", "accumulate")]
+            out += [("persist", gen, 256, 256, K, "plain", f32) for K in GEMM_PERSIST_KS]
+            out += [("epilogue", gen, *GEMM_EPI_SHAPE, e, f32) for e in GEMM_EPILOGUES]
+        out += [("route", gen, 256, 256, K, e, f32) for _, _, _, K, _, e, f32, _ in GEMM_ROUTES]
+        out += [("batch", gen, *GEMM_BATCH[2:], "plain", f32) for f32 in (False, True)]
+        out += [("group", gen, 256, 256, T, e, True) for T in GEMM_GROUP_TOKENS for e in ("plain", "accumulate")]
+        out += [("f32", gen, M, N, K, e, True) for M, N, K in GEMM_F32_SHAPES for e in GEMM_F32_EPIS]   # fp32 operands
+    return out
+
+
+def gemm_cpu_case(label, gen, M, N, K, epi, f32, dev="cpu"):
+    """the case of one row of gemm_cpu_cases; act 6 reads the gelu' its act-5 twin stored"""
+    aux = None
+    if epi == "mul":
+        aux = gemm_ref_of(F32, gemm_case(gen, M, N, K, "gelu_save_grad", f32, dev))["aux_out"].to(BF16)
+    return gemm_case(gen, M, N, K, epi, f32, dev, aux_in=aux, dtype=F32 if label == "f32" else BF16)
+
+
+def judge_gemm(J, op, shape, c, r, t, outs, cs_rows=None, aux_fp32=False):
+    """C, aux_out and (where the call asks for them) the column sums of one call.  cs_rows: the
+    fused arm's serial rows; None: the arm that reduces the stored C (judged against the kernel's
+    own C - on the CPU against the twin's, rounded)."""
+    K, C = c["K"], outs.get("C")
+    if c["out_fp32"]:
+        # (the clamp as in ulp_err: gelu'(-20) is 1e-258 in fp64 and 0 in fp32)
+        J.rel(op, shape, "C", C, r["C"], t["C"], r["S_rel"].clamp_min(TINY), K)
+    else:
+        J.ulp(op, shape, "C", C, r["C"], t["C"], FLOOR_GEMM * r["S"])
+    if r["aux_out"] is not None and (not outs or "aux_out" in outs):
+        if aux_fp32:
+            J.rel(op, shape, "aux", outs.get("aux_out"), r["aux_out"], t["aux_out"], r["S_aux"], K)
+        else:
+            J.ulp(op, shape, "aux", outs.get("aux_out"), r["aux_out"], t["aux_out"], FLOOR_GEMM * r["S_aux"])
+    if c["colsum"]:
+        if cs_rows is not None:
+            J.rel(op, shape, "colsum", outs.get("colsum"), r["colsum"], t["colsum"], r["colsum_scale"], cs_rows)
+        else:
+            st = (C if C is not None else t["C"].to(F32 if c["out_fp32"] else BF16))
+            J.rel(op, shape, "colsum*", outs.get("colsum"), st.double().sum(-2), st.float().sum(-2),
+                  st.double().abs().sum(-2), gemm_colsum_fallback_rows(c["M"]))

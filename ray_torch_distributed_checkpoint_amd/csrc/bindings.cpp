@@ -40,23 +40,7 @@ int rtdc_colsum_multi(const float* const* ws, float* const* out, const int* W, c
 int rtdc_xent(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
               int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index, int is_bf16,
               hipStream_t st);
-int rtdc_adamw(const void* chunks, int nchunks, float* p, const float* g, float* m, float* v, void* shadow,
-               float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-               float grad_scale, const int* skip, const float* clip, hipStream_t st);
-int rtdc_adamw_bf16state(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v, void* shadow,
-                        float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                        float grad_scale, const int* skip, const float* clip, unsigned long long seed,
-                        unsigned long long step, hipStream_t st);
-int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow, float lr,
-             float momentum, float dampening, float wd, int nesterov, int first, float grad_scale,
-             const int* skip, const float* clip, hipStream_t st);
-int rtdc_adamw_dev(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v, int m_bf16,
-                   void* shadow, const long long* count, const float* lr_row, int L, const float* bc, int Lbc,
-                   int step_off, float b1, float b2, float eps, float wd, float grad_scale, const int* skip,
-                   const float* clip, unsigned long long seed, hipStream_t st);
-int rtdc_sgd_dev(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow,
-                 const long long* count, const float* lr_row, int L, float momentum, float dampening, float wd,
-                 int nesterov, int first, float grad_scale, const int* skip, const float* clip, hipStream_t st);
+// (rtdc_adamw, rtdc_sgd: declared with their argument structs in kernels/args.h)
 int rtdc_optim_step_advance(long long* count, hipStream_t st);
 int rtdc_f32_to_bf16(const float* x, void* y, long long n, hipStream_t st);
 int rtdc_f32_to_bf16_t(const float* x, void* y, int R, int C, hipStream_t st);
@@ -405,91 +389,116 @@ static void check_chunks(const Tensor& chunks, int64_t nchunks, const char* op) 
                   chunks.size(1) == 3 && chunks.size(0) >= nchunks,
               op, ": chunk table must be a contiguous int64 [n, 3] GPU tensor");
 }
-// dispatches on the state dtype: fp32 m / v -> adamw_kernel; bf16 m / v -> adamw_bf16state_kernel
-// (stored state rounded stochastically with Philox bits keyed by (seed, step, flat index))
-static void adamw(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, Tensor m, Tensor v,
-                  c10::optional<Tensor> shadow, double lr, double b1, double b2, double eps, double wd, double bc1,
-                  double bc2_sqrt, double grad_scale, int64_t skip_ptr, int64_t clip_ptr, uint64_t seed,
-                  int64_t step) {
-  check_chunks(chunks, nchunks, "adamw");
-  TORCH_CHECK(m.scalar_type() == v.scalar_type(), "adamw: exp_avg is ", m.scalar_type(), " but exp_avg_sq is ",
-              v.scalar_type());
-  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "adamw: fp32 parameters and gradients");
-  if (m.scalar_type() == at::kBFloat16) {
-    TORCH_CHECK(step > 0, "adamw: bf16 state needs the step number (>= 1) that keys the rounding bits");
-    check_rc(rtdc_adamw_bf16state(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(),
-                                  m.data_ptr(), v.data_ptr(), ptr_or_null(shadow), (float)lr, (float)b1, (float)b2,
-                                  (float)eps, (float)wd, (float)bc1, (float)bc2_sqrt, (float)grad_scale,
-                                  (const int*)(uintptr_t)skip_ptr, (const float*)(uintptr_t)clip_ptr,
-                                  (unsigned long long)seed, (unsigned long long)step, cur_stream()),
-             "adamw");
-    return;
-  }
-  TORCH_CHECK(m.scalar_type() == at::kFloat, "adamw: optimizer state must be float32 or bfloat16, got ",
-              m.scalar_type());
-  check_rc(rtdc_adamw(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
-                      v.data_ptr<float>(), ptr_or_null(shadow), (float)lr, (float)b1, (float)b2, (float)eps,
-                      (float)wd, (float)bc1, (float)bc2_sqrt, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
-                      (const float*)(uintptr_t)clip_ptr, cur_stream()),
-           "adamw");
-}
-static void sgd(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, c10::optional<Tensor> buf,
-                c10::optional<Tensor> shadow, double lr, double momentum, double dampening, double wd,
-                bool nesterov, bool first, double grad_scale, int64_t skip_ptr, int64_t clip_ptr) {
-  check_chunks(chunks, nchunks, "sgd");
-  check_rc(rtdc_sgd(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(),
-                    (float*)ptr_or_null(buf), ptr_or_null(shadow), (float)lr, (float)momentum, (float)dampening,
-                    (float)wd, nesterov, first, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
-                    (const float*)(uintptr_t)clip_ptr, cur_stream()),
-           "sgd");
+// The operands every update launch shares (rtdc::OptimArgs, kernels/args.h), checked and filled in.
+static void optim_args(rtdc::OptimArgs& a, const char* op, const Tensor& chunks, int64_t nchunks, const Tensor& p,
+                       const Tensor& g, const c10::optional<Tensor>& shadow, double wd, double grad_scale,
+                       int64_t skip_ptr, int64_t clip_ptr) {
+  check_chunks(chunks, nchunks, op);
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, op, ": fp32 parameters and gradients");
+  a.chunks = chunks.data_ptr();
+  a.nchunks = (int)nchunks;
+  a.p = p.data_ptr<float>();
+  a.g = g.data_ptr<float>();
+  a.shadow = ptr_or_null(shadow);
+  a.wd = (float)wd;
+  a.grad_scale = (float)grad_scale;
+  a.skip = (const int*)(uintptr_t)skip_ptr;
+  a.clip = (const float*)(uintptr_t)clip_ptr;
 }
 // capturable variants (FusedAdamW / FusedSGD capturable=True): lr, the bias corrections and the step
-// number come from device tables indexed by the device step counter `count` (kernels/optim.hip
+// number come from device tables indexed by the device step counter `count` (kernels/args.h
 // DevStep) instead of host scalars, so a replayed hipGraph does not freeze them
-static const float* check_lr_table(const Tensor& count, const Tensor& lr_tab, int64_t group, const char* op) {
+static void optim_dev_args(rtdc::OptimArgs& a, const char* op, const Tensor& count, const Tensor& lr_tab,
+                           int64_t group) {
   TORCH_CHECK(count.is_cuda() && count.scalar_type() == at::kLong && count.numel() >= 1, op,
               ": count must be an int64 GPU tensor");
   TORCH_CHECK(lr_tab.is_cuda() && lr_tab.scalar_type() == at::kFloat && lr_tab.is_contiguous() && lr_tab.dim() == 2 &&
                   lr_tab.size(1) >= 1 && group >= 0 && group < lr_tab.size(0) && lr_tab.size(1) <= INT32_MAX,
               op, ": lr table must be a contiguous fp32 [n_groups, L] GPU tensor holding row `group`");
-  return lr_tab.data_ptr<float>() + group * lr_tab.size(1);
+  a.ds.count = (const long long*)count.data_ptr<int64_t>();
+  a.ds.lr = lr_tab.data_ptr<float>() + group * lr_tab.size(1);
+  a.ds.L = (int)lr_tab.size(1);
+}
+// the state dtype selects the kernel: fp32 m / v -> adamw_kernel; bf16 m / v -> adamw_bf16state_kernel
+// (stored state rounded stochastically with Philox bits keyed by (seed, step, flat index))
+static rtdc::AdamwArgs adamw_args(const char* op, const Tensor& chunks, int64_t nchunks, const Tensor& p,
+                                  const Tensor& g, const Tensor& m, const Tensor& v,
+                                  const c10::optional<Tensor>& shadow, double b1, double b2, double eps, double wd,
+                                  double grad_scale, int64_t skip_ptr, int64_t clip_ptr, uint64_t seed) {
+  rtdc::AdamwArgs a{};
+  optim_args(a, op, chunks, nchunks, p, g, shadow, wd, grad_scale, skip_ptr, clip_ptr);
+  TORCH_CHECK(m.scalar_type() == v.scalar_type(), op, ": exp_avg is ", m.scalar_type(), " but exp_avg_sq is ",
+              v.scalar_type());
+  TORCH_CHECK(m.scalar_type() == at::kFloat || m.scalar_type() == at::kBFloat16, op,
+              ": optimizer state must be float32 or bfloat16, got ", m.scalar_type());
+  a.m = m.data_ptr();
+  a.v = v.data_ptr();
+  a.state_bf16 = m.scalar_type() == at::kBFloat16;
+  a.b1 = (float)b1;
+  a.b2 = (float)b2;
+  a.eps = (float)eps;
+  a.bc1 = a.bc2_sqrt = 1.f;
+  a.seed = (unsigned long long)seed;
+  return a;
+}
+static void adamw(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, Tensor m, Tensor v,
+                  c10::optional<Tensor> shadow, double lr, double b1, double b2, double eps, double wd, double bc1,
+                  double bc2_sqrt, double grad_scale, int64_t skip_ptr, int64_t clip_ptr, uint64_t seed,
+                  int64_t step) {
+  rtdc::AdamwArgs a = adamw_args("adamw", chunks, nchunks, p, g, m, v, shadow, b1, b2, eps, wd, grad_scale, skip_ptr,
+                                 clip_ptr, seed);
+  TORCH_CHECK(!a.state_bf16 || step > 0, "adamw: bf16 state needs the step number (>= 1) that keys the rounding bits");
+  a.lr = (float)lr;
+  a.bc1 = (float)bc1;
+  a.bc2_sqrt = (float)bc2_sqrt;
+  a.step = (unsigned long long)step;
+  check_rc(rtdc_adamw(&a, cur_stream()), "adamw");
 }
 static void adamw_dev(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, Tensor m, Tensor v,
                       c10::optional<Tensor> shadow, Tensor count, Tensor lr_tab, int64_t group, Tensor bc,
                       int64_t step_off, double b1, double b2, double eps, double wd, double grad_scale,
                       int64_t skip_ptr, int64_t clip_ptr, uint64_t seed) {
-  check_chunks(chunks, nchunks, "adamw_dev");
-  TORCH_CHECK(m.scalar_type() == v.scalar_type(), "adamw_dev: exp_avg is ", m.scalar_type(), " but exp_avg_sq is ",
-              v.scalar_type());
-  TORCH_CHECK(m.scalar_type() == at::kFloat || m.scalar_type() == at::kBFloat16,
-              "adamw_dev: optimizer state must be float32 or bfloat16, got ", m.scalar_type());
-  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat,
-              "adamw_dev: fp32 parameters and gradients");
-  const float* lr_row = check_lr_table(count, lr_tab, group, "adamw_dev");
+  rtdc::AdamwArgs a = adamw_args("adamw_dev", chunks, nchunks, p, g, m, v, shadow, b1, b2, eps, wd, grad_scale,
+                                 skip_ptr, clip_ptr, seed);
+  optim_dev_args(a, "adamw_dev", count, lr_tab, group);
   TORCH_CHECK(bc.is_cuda() && bc.scalar_type() == at::kFloat && bc.is_contiguous() && bc.dim() == 2 &&
                   bc.size(1) == 2 && bc.size(0) >= 1 && bc.size(0) <= INT32_MAX,
               "adamw_dev: bias-correction table must be a contiguous fp32 [Lbc, 2] GPU tensor");
   TORCH_CHECK(step_off <= 0 && step_off > INT32_MIN, "adamw_dev: step_off must be <= 0");
-  check_rc(rtdc_adamw_dev(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr(),
-                          v.data_ptr(), m.scalar_type() == at::kBFloat16, ptr_or_null(shadow),
-                          (const long long*)count.data_ptr<int64_t>(), lr_row, (int)lr_tab.size(1),
-                          bc.data_ptr<float>(), (int)bc.size(0), (int)step_off, (float)b1, (float)b2, (float)eps,
-                          (float)wd, (float)grad_scale, (const int*)(uintptr_t)skip_ptr,
-                          (const float*)(uintptr_t)clip_ptr, (unsigned long long)seed, cur_stream()),
-           "adamw_dev");
+  a.ds.bc = bc.data_ptr<float>();
+  a.ds.Lbc = (int)bc.size(0);
+  a.ds.step_off = (int)step_off;
+  check_rc(rtdc_adamw(&a, cur_stream()), "adamw_dev");
+}
+static rtdc::SgdArgs sgd_args(const char* op, const Tensor& chunks, int64_t nchunks, const Tensor& p, const Tensor& g,
+                              const c10::optional<Tensor>& buf, const c10::optional<Tensor>& shadow, double momentum,
+                              double dampening, double wd, bool nesterov, bool first, double grad_scale,
+                              int64_t skip_ptr, int64_t clip_ptr) {
+  rtdc::SgdArgs a{};
+  optim_args(a, op, chunks, nchunks, p, g, shadow, wd, grad_scale, skip_ptr, clip_ptr);
+  a.buf = (float*)ptr_or_null(buf);
+  a.momentum = (float)momentum;
+  a.dampening = (float)dampening;
+  a.nesterov = nesterov;
+  a.first = first;
+  return a;
+}
+static void sgd(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, c10::optional<Tensor> buf,
+                c10::optional<Tensor> shadow, double lr, double momentum, double dampening, double wd,
+                bool nesterov, bool first, double grad_scale, int64_t skip_ptr, int64_t clip_ptr) {
+  rtdc::SgdArgs a = sgd_args("sgd", chunks, nchunks, p, g, buf, shadow, momentum, dampening, wd, nesterov, first,
+                             grad_scale, skip_ptr, clip_ptr);
+  a.lr = (float)lr;
+  check_rc(rtdc_sgd(&a, cur_stream()), "sgd");
 }
 static void sgd_dev(Tensor chunks, int64_t nchunks, Tensor p, Tensor g, c10::optional<Tensor> buf,
                     c10::optional<Tensor> shadow, Tensor count, Tensor lr_tab, int64_t group, double momentum,
                     double dampening, double wd, bool nesterov, bool first, double grad_scale, int64_t skip_ptr,
                     int64_t clip_ptr) {
-  check_chunks(chunks, nchunks, "sgd_dev");
-  const float* lr_row = check_lr_table(count, lr_tab, group, "sgd_dev");
-  check_rc(rtdc_sgd_dev(chunks.data_ptr(), (int)nchunks, p.data_ptr<float>(), g.data_ptr<float>(),
-                        (float*)ptr_or_null(buf), ptr_or_null(shadow), (const long long*)count.data_ptr<int64_t>(),
-                        lr_row, (int)lr_tab.size(1), (float)momentum, (float)dampening, (float)wd, nesterov, first,
-                        (float)grad_scale, (const int*)(uintptr_t)skip_ptr, (const float*)(uintptr_t)clip_ptr,
-                        cur_stream()),
-           "sgd_dev");
+  rtdc::SgdArgs a = sgd_args("sgd_dev", chunks, nchunks, p, g, buf, shadow, momentum, dampening, wd, nesterov, first,
+                             grad_scale, skip_ptr, clip_ptr);
+  optim_dev_args(a, "sgd_dev", count, lr_tab, group);
+  check_rc(rtdc_sgd(&a, cur_stream()), "sgd_dev");
 }
 static void optim_step_advance(Tensor count) {
   TORCH_CHECK(count.is_cuda() && count.scalar_type() == at::kLong && count.numel() >= 1,

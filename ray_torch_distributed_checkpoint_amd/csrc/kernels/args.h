@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <hip/hip_runtime_api.h>  // hipStream_t
+
 namespace rtdc {
 
 // bf16 MFMA GEMM (gemm_bf16.hip)
@@ -76,4 +78,55 @@ struct GemmF32Args {
   const long long* drop_base;
 };
 
+// ---- fused optimizers over flat buffers (optim.hip) -------------------------------------------
+// Device-resident step state (FusedAdamW / FusedSGD capturable=True).
+// The per-step hyper-parameters of the update kernels - lr, and AdamW's 1 - b1^t and
+// sqrt(1 - b2^t) - are host scalars passed by value: a replayed hipGraph would freeze them.  The
+// DEV = true instantiations read them from tables instead, indexed by a device step counter that
+// optim_step_advance_kernel increments at the end of every step (eager or replayed).  The tables
+// are built on the host from the very doubles the host path converts to fp32 (optim/schedule.py),
+// and the per-element arithmetic is the DEV = false code, so both paths give the same bits.  No
+// device pow / cos: those are not correctly rounded.
+struct DevStep {
+  const long long* count;  // completed optimizer steps
+  const float* lr;         // this param group's row of the lr table: lr[k] is the (k + 1)-th step's, k < L
+  const float* bc;         // rows t = 1 .. Lbc of {1 - b1^t, sqrt(1 - b2^t)} (both 1.0f from row Lbc on); SGD: null
+  int L, Lbc;
+  int step_off;  // (step number of this launch's parameters) - (optimizer step number): <= 0, replay-invariant
+};
+
+// What every update launch takes.  ds.count == nullptr: the host scalars (lr; AdamW's bc1,
+// bc2_sqrt, step) are used and ds is ignored; otherwise the device tables are and those are.
+struct OptimArgs {
+  const void* chunks;  // int64 [nchunks, 3] rows (start, len | decay << 32, state start)
+  int nchunks;
+  float* p;
+  const float* g;
+  void* shadow;     // optional bf16 image of p, written in the same pass
+  float lr, wd, grad_scale;
+  const int* skip;    // optional communicator health word: nonzero -> the update is a no-op
+  const float* clip;  // optional {total_norm, coef} of the gradient-norm kernels
+  DevStep ds;
+};
+
+struct AdamwArgs : OptimArgs {
+  void* m;  // exp_avg / exp_avg_sq: fp32, or bf16 rounded stochastically (state_bf16)
+  void* v;
+  int state_bf16;
+  float b1, b2, eps, bc1, bc2_sqrt;
+  unsigned long long seed, step;  // bf16 state: the Philox key words (step: host path only)
+};
+
+struct SgdArgs : OptimArgs {
+  float* buf;  // momentum buffer (null without momentum)
+  float momentum, dampening;
+  int nesterov, first;
+};
+
 }  // namespace rtdc
+
+// Launchers (0 = ok, 1 = unsupported arguments, 2 = launch error), on stream st.
+extern "C" {
+int rtdc_adamw(const rtdc::AdamwArgs* args, hipStream_t st);
+int rtdc_sgd(const rtdc::SgdArgs* args, hipStream_t st);
+}

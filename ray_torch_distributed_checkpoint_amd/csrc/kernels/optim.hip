@@ -20,6 +20,9 @@
 // timed out it poisoned its bucket with NaN and set the word; the update then becomes a no-op,
 // so a NaN gradient can never reach the parameters or the optimizer state - also inside a
 // replayed hipGraph, where no host code runs between the collective and the step.
+//
+// Host side: two launchers, rtdc_adamw and rtdc_sgd, each taking one argument struct (args.h).
+#include "args.h"
 #include "common.h"
 
 namespace rtdc {
@@ -36,22 +39,7 @@ struct Chunk {
 };
 static_assert(sizeof(Chunk) == 24, "chunk table rows are 3 x int64");
 
-// ---- device-resident step state (FusedAdamW / FusedSGD capturable=True) ----------------------
-// The per-step hyper-parameters of the kernels below - lr, and AdamW's 1 - b1^t and
-// sqrt(1 - b2^t) - are host scalars passed by value: a replayed hipGraph would freeze them.  The
-// DEV = true instantiations read them from tables instead, indexed by a device step counter that
-// optim_step_advance_kernel increments at the end of every step (eager or replayed).  The tables
-// are built on the host from the very doubles the host path converts to fp32 (optim/schedule.py),
-// and the per-element arithmetic is the DEV = false code, so both paths give the same bits.  No
-// device pow / cos: those are not correctly rounded.
-struct DevStep {
-  const long long* count;  // completed optimizer steps
-  const float* lr;         // this param group's row of the lr table: lr[k] is the (k + 1)-th step's, k < L
-  const float* bc;         // rows t = 1 .. Lbc of {1 - b1^t, sqrt(1 - b2^t)} (both 1.0f from row Lbc on); SGD: null
-  int L, Lbc;
-  int step_off;  // (step number of this launch's parameters) - (optimizer step number): <= 0, replay-invariant
-};
-
+// ---- device-resident step state (DevStep, args.h) ---------------------------------------------
 // Read once per block, before the chunk loop (wave-uniform addresses: scalar loads).  Both indices
 // are clamped into their tables whatever the counter holds.
 __device__ __forceinline__ long long dev_step(const DevStep& ds, float& lr) {
@@ -467,71 +455,35 @@ using namespace rtdc;
 
 static inline int grid_for(int nchunks) { return nchunks < 4096 ? nchunks : 4096; }
 
-extern "C" int rtdc_adamw(const void* chunks, int nchunks, float* p, const float* g, float* m,
-                          float* v, void* shadow, float lr, float b1, float b2, float eps, float wd,
-                          float bc1, float bc2_sqrt, float grad_scale, const int* skip, const float* clip,
-                          hipStream_t st) {
-  if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
-                     nchunks, p, g, m, v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, skip, clip,
-                     DevStep{});
+// One update launch over a chunk table: `rest` are the kernel's parameters after (chunks, nchunks,
+// p, g).  An empty table launches nothing; device tables that cannot be indexed are refused (1).
+template <typename... KP, typename... A>
+static int launch_update(void (*kernel)(KP...), const OptimArgs& o, bool bc_table, hipStream_t st, A... rest) {
+  if (o.nchunks <= 0) return 0;
+  const DevStep& ds = o.ds;
+  if (ds.count != nullptr && (ds.lr == nullptr || ds.L < 1 || (bc_table && (ds.bc == nullptr || ds.Lbc < 1)))) return 1;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(o.nchunks)), dim3(256), 0, st, (const Chunk*)o.chunks, o.nchunks, o.p, o.g,
+                     rest...);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-extern "C" int rtdc_adamw_bf16state(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v,
-                                    void* shadow, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                    float bc2_sqrt, float grad_scale, const int* skip, const float* clip,
-                                    unsigned long long seed, unsigned long long step, hipStream_t st) {
-  if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(adamw_bf16state_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
-                     nchunks, p, g, (bf16_t*)m, (bf16_t*)v, (bf16_t*)shadow, lr, b1, b2, eps, wd, bc1, bc2_sqrt,
-                     grad_scale, skip, clip, (uint64_t)seed, (uint64_t)step, DevStep{});
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+// a->ds.count != nullptr (capturable): lr, the bias corrections and the step number - also the
+// bf16-state kernel's Philox step word - come from the device tables, not from a->lr / bc1 / bc2_sqrt / step
+extern "C" int rtdc_adamw(const AdamwArgs* a, hipStream_t st) {
+  const bool dev = a->ds.count != nullptr;
+  bf16_t* shadow = (bf16_t*)a->shadow;
+  if (a->state_bf16)
+    return launch_update(dev ? adamw_bf16state_kernel<true> : adamw_bf16state_kernel<false>, *a, true, st,
+                         (bf16_t*)a->m, (bf16_t*)a->v, shadow, a->lr, a->b1, a->b2, a->eps, a->wd, a->bc1, a->bc2_sqrt,
+                         a->grad_scale, a->skip, a->clip, (uint64_t)a->seed, (uint64_t)a->step, a->ds);
+  return launch_update(dev ? adamw_kernel<true> : adamw_kernel<false>, *a, true, st, (float*)a->m, (float*)a->v, shadow,
+                       a->lr, a->b1, a->b2, a->eps, a->wd, a->bc1, a->bc2_sqrt, a->grad_scale, a->skip, a->clip, a->ds);
 }
 
-extern "C" int rtdc_sgd(const void* chunks, int nchunks, float* p, const float* g, float* buf,
-                        void* shadow, float lr, float momentum, float dampening, float wd,
-                        int nesterov, int first, float grad_scale, const int* skip, const float* clip,
-                        hipStream_t st) {
-  if (nchunks <= 0) return 0;
-  hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks,
-                     nchunks, p, g, buf, (bf16_t*)shadow, lr, momentum, dampening, wd, nesterov, first,
-                     grad_scale, skip, clip, DevStep{});
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-// ---- capturable variants: lr / bias corrections / step number from the device tables (DevStep) ----
-// lr_row: this param group's row of the [n_groups, L] lr table; bc: [Lbc, 2] (AdamW).  m_bf16: the
-// moments are bf16 (adamw_bf16state_kernel; its Philox step word is the device step number).
-extern "C" int rtdc_adamw_dev(const void* chunks, int nchunks, float* p, const float* g, void* m, void* v,
-                              int m_bf16, void* shadow, const long long* count, const float* lr_row, int L,
-                              const float* bc, int Lbc, int step_off, float b1, float b2, float eps, float wd,
-                              float grad_scale, const int* skip, const float* clip, unsigned long long seed,
-                              hipStream_t st) {
-  if (nchunks <= 0) return 0;
-  if (count == nullptr || lr_row == nullptr || bc == nullptr || L < 1 || Lbc < 1) return 1;
-  const DevStep ds{count, lr_row, bc, L, Lbc, step_off};
-  if (m_bf16)
-    hipLaunchKernelGGL(adamw_bf16state_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, st,
-                       (const Chunk*)chunks, nchunks, p, g, (bf16_t*)m, (bf16_t*)v, (bf16_t*)shadow, 0.f, b1, b2, eps,
-                       wd, 1.f, 1.f, grad_scale, skip, clip, (uint64_t)seed, (uint64_t)0, ds);
-  else
-    hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks, nchunks,
-                       p, g, (float*)m, (float*)v, (bf16_t*)shadow, 0.f, b1, b2, eps, wd, 1.f, 1.f, grad_scale, skip,
-                       clip, ds);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-extern "C" int rtdc_sgd_dev(const void* chunks, int nchunks, float* p, const float* g, float* buf, void* shadow,
-                            const long long* count, const float* lr_row, int L, float momentum, float dampening,
-                            float wd, int nesterov, int first, float grad_scale, const int* skip, const float* clip,
-                            hipStream_t st) {
-  if (nchunks <= 0) return 0;
-  if (count == nullptr || lr_row == nullptr || L < 1) return 1;
-  const DevStep ds{count, lr_row, nullptr, L, 0, 0};
-  hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(nchunks)), dim3(256), 0, st, (const Chunk*)chunks, nchunks, p, g,
-                     buf, (bf16_t*)shadow, 0.f, momentum, dampening, wd, nesterov, first, grad_scale, skip, clip, ds);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+extern "C" int rtdc_sgd(const SgdArgs* a, hipStream_t st) {
+  return launch_update(a->ds.count != nullptr ? sgd_kernel<true> : sgd_kernel<false>, *a, false, st, a->buf,
+                       (bf16_t*)a->shadow, a->lr, a->momentum, a->dampening, a->wd, a->nesterov, a->first,
+                       a->grad_scale, a->skip, a->clip, a->ds);
 }
 
 // count += 1 on stream st: the last launch of a capturable optimizer step

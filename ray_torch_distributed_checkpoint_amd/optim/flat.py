@@ -92,9 +92,6 @@ class ZeroLayout:
         for (a, b), (oa, ob), c in zip(self.buckets, self.owned, self.compact_starts):
             dist.all_gather_into_tensor(full[a:b], compact[c:c + (ob - oa)], group=self.group)
 
-    def owned_elements(self) -> int:
-        return self.compact_numel
-
 
 class FlatParamSpace:
     def __init__(self, params, device=None, shadow_dtype=torch.bfloat16, grads=True, align_after=None):
@@ -371,18 +368,29 @@ class FlatParamSpace:
         ZeRO).  The fused optimizers' per-parameter state is these slices of the state buffers."""
         return [(a, b, self.state_offset(a)) for a, b in self._ranges(s)]
 
-    def chunk_table_split(self, params_subset, decay_flags, split: int):
-        """Two chunk tables: segments below flat offset `split`, and the rest."""
-        key = ("split", tuple(id(p) for p in params_subset), tuple(decay_flags), split)
+    def _tables(self, key, params_subset, decay_flags, splits=None):
+        """Build and cache the chunk tables cut at `splits`: len(splits) + 1 pairs (int64 [n, 3]
+        device tensor, n), an empty table being one zero row with n = 0.  splits=None: the one
+        uncut table, as a bare pair."""
         hit = self._chunk_cache.get(key)
         if hit is not None:
             return hit
-        lo, hi = [], []
+        import bisect
+
+        cuts = splits or ()
+        parts = [[] for _ in range(len(cuts) + 1)]
         for p, d in zip(params_subset, decay_flags):
-            s = self.segment_of(p)
-            (lo if s.offset < split else hi).extend(self._chunks(s, d))
-        out = tuple((torch.tensor(r if r else [(0, 0, 0)], dtype=torch.int64).to(self.device), len(r))
-                    for r in (lo, hi))
+            for start, lend, so in self._chunks(self.segment_of(p), d):
+                n, flag = lend & 0xFFFFFFFF, lend & ~0xFFFFFFFF
+                a, e = start, start + n
+                while a < e:
+                    k = bisect.bisect_right(cuts, a)
+                    cut = min(e, cuts[k]) if k < len(cuts) else e
+                    parts[k].append((a, (cut - a) | flag, so + (a - start)))
+                    a = cut
+        out = tuple((torch.tensor(r if r else [(0, 0, 0)], dtype=torch.int64).to(self.device), len(r)) for r in parts)
+        if splits is None:
+            out = out[0]
         self._chunk_cache[key] = out
         return out
 
@@ -392,40 +400,14 @@ class FlatParamSpace:
         split is cut there (pieces of a deferred collective need not align to chunks)."""
         splits = tuple(int(x) for x in splits)
         key = ("splits", tuple(id(p) for p in params_subset), tuple(decay_flags), splits)
-        hit = self._chunk_cache.get(key)
-        if hit is not None:
-            return hit
-        import bisect
-
-        parts = [[] for _ in range(len(splits) + 1)]
-        for p, d in zip(params_subset, decay_flags):
-            for start, lend, so in self._chunks(self.segment_of(p), d):
-                n, flag = lend & 0xFFFFFFFF, lend & ~0xFFFFFFFF
-                a, e = start, start + n
-                while a < e:
-                    k = bisect.bisect_right(splits, a)
-                    cut = min(e, splits[k]) if k < len(splits) else e
-                    parts[k].append((a, (cut - a) | flag, so + (a - start)))
-                    a = cut
-        out = tuple((torch.tensor(r if r else [(0, 0, 0)], dtype=torch.int64).to(self.device), len(r)) for r in parts)
-        self._chunk_cache[key] = out
-        return out
+        return self._tables(key, params_subset, decay_flags, splits)
 
     def chunk_table(self, params_subset, decay_flags) -> tuple[torch.Tensor, int]:
         """int64 [nchunks, 3] rows of (start, len | decay<<32, state start) for the native
         optimizer kernels (only this rank's owned elements under ZeRO-1, whose state lives in
         compact buffers)."""
         key = (tuple(id(p) for p in params_subset), tuple(decay_flags))
-        hit = self._chunk_cache.get(key)
-        if hit is not None:
-            return hit
-        rows = []
-        for p, d in zip(params_subset, decay_flags):
-            rows.extend(self._chunks(self.segment_of(p), d))
-        t = torch.tensor(rows if rows else [(0, 0, 0)], dtype=torch.int64).to(self.device)
-        out = (t, len(rows))
-        self._chunk_cache[key] = out
-        return out
+        return self._tables(key, params_subset, decay_flags)
 
     def after_step(self) -> None:
         """End of an optimizer step: under ZeRO-1 every rank updated only its shards; gather

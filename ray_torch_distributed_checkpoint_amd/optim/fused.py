@@ -134,10 +134,6 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return sp
 
     # -- per-parameter state views -------------------------------------------------------------
-    def _zero(self):
-        sp = self._space
-        return None if sp is None else sp.zero
-
     def _state_value(self, p, k):
         """What `self.state[p][k]` holds: a view of the flat state buffer, or under ZeRO-1 a
         `FlatShardedTensor` over this rank's compact slices (checkpoint/sharded.py) - the value
@@ -330,8 +326,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         raise ValueError("param group does not belong to this optimizer")
 
     def _end_step(self, capturing: bool, steps_before) -> None:
-        """After the last launch of `step()`.  A captured step ran nothing: the host counters go
-        back to what the device holds, and the replays are added by `_reconcile`."""
+        """After the last launch of `step()`.  `capturing`: the step was captured by a capturable
+        optimizer.  It ran nothing: the host counters go back to what the device holds, and the
+        replays are added by `_reconcile`."""
         if not capturing:
             self._step_count += 1
             return
@@ -463,6 +460,40 @@ class _FlatOptimizer(torch.optim.Optimizer):
                         self._adopt(p, k, st[k])
                         st[k] = self._state_value(p, k)
 
+    @torch.no_grad()
+    def step(self, closure=None):
+        from ..ops.gemm import flush_wgrads
+
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        flush_wgrads()  # weight gradients deferred into a grouped launch (normally flushed by backward's end)
+        if self._flat_mode():
+            capturing = self._use_native() and torch.cuda.is_current_stream_capturing()
+            if capturing:
+                self._check_capture()
+            self._begin_step(capturing)
+            # Only a capturable optimizer counts its replays (on the device, read back by
+            # `_reconcile`).  Any other captured step - a constant-lr FusedSGD - counts like an
+            # eager one: once, when it is captured.
+            replayed = capturing and self.capturable
+            before = dict(self._steps) if replayed else None
+            self._flat_step()
+            self._end_step(replayed, before)
+            return loss
+        self._begin_step()
+        self._step_count += 1
+        coef = self._plain_prelude()
+        for group in self.param_groups:
+            self._plain_update(group, self._with_grad(group), coef)
+        return loss
+
+    # What a subclass supplies: `_check_capture()` raises if its step must not be captured into a
+    # hipGraph; `_plain_update(group, ps, coef)` is the per-tensor CPU step of one param group (`coef`:
+    # the factor on every gradient, None: 1); `_native_launches` / `_cpu_launches(group, ps)` give the
+    # flat step's [(params, decay_flags, fn(chunks, n[, clip]))].
+
     def _flat_step(self) -> None:
         """One step over the flat buffers: native chunk-table kernels on the GPU, the same
         chunk walk with torch ops on the CPU (ZeRO-1 reference path); then, under ZeRO-1, the
@@ -498,33 +529,42 @@ class _FlatOptimizer(torch.optim.Optimizer):
         for start, lend, so in chunks[:n].tolist():
             yield start, lend & 0xFFFFFFFF, bool(lend >> 32), so
 
-    def _cpu_launches(self, group, ps) -> list:
-        raise NotImplementedError
+    @staticmethod
+    def _tail_plan(sp, launches):
+        """launches: [(params, decay_flags, fn)] -> (parts, waits): per launch `(tables, fn)` with
+        one chunk table per entry of `waits` plus one.  Without a pending last-bucket all-reduce
+        (DDP defer_tail_to_optimizer; `sp.pending_tail`, cleared here) that is the whole chunk
+        table and no wait; with one, table 0 holds everything below the first in-flight piece and
+        table i + 1 the piece that `waits[i]` makes the stream wait for."""
+        tail, sp.pending_tail = sp.pending_tail, None
+        if tail is None:
+            return [((sp.chunk_table(ps, flags),), fn) for ps, flags, fn in launches], []
+        starts = [off for off, _ in tail]
+        return ([(sp.chunk_table_splits(ps, flags, starts), fn) for ps, flags, fn in launches],
+                [wait for _, wait in tail])
+
+    @staticmethod
+    def _walk(parts, waits, wait: bool = True):
+        """(chunks, n, fn) of every non-empty table, piece-major; before piece i + 1 its collective
+        is waited for (also when nothing is launched), unless `wait` is off."""
+        for i in range(len(waits) + 1):
+            if i and wait:
+                waits[i - 1]()
+            for tables, fn in parts:
+                chunks, n = tables[i]
+                if n:
+                    yield chunks, n, fn
 
     def _launch_split(self, sp, launches) -> None:
         """launches: [(params, decay_flags, fn(chunks, n))].  With a pending last-bucket
-        all-reduce (DDP defer_tail_to_optimizer), update everything below its slice first,
-        stream-wait for the collective, then the slice itself.
+        all-reduce, update everything below its slice first, stream-wait for the collective,
+        then the slice itself.
 
         Gradient clipping (`_launch_clipped`) gives up this tail/update overlap: every update
         needs the clip coefficient, which needs the whole gradient, so only the norm pass of the
         early part overlaps the tail's transfer."""
-        tail = sp.pending_tail
-        if tail is None:
-            for ps, flags, fn in launches:
-                fn(*sp.chunk_table(ps, flags))
-            return
-        sp.pending_tail = None
-        starts = [off for off, _ in tail]
-        parts = [(sp.chunk_table_splits(ps, flags, starts), fn) for ps, flags, fn in launches]
-        for tables, fn in parts:  # everything below the first in-flight piece
-            if tables[0][1]:
-                fn(*tables[0])
-        for i, (_, wait) in enumerate(tail):  # piece i: wait for its collective, then update it
-            wait()
-            for tables, fn in parts:
-                if tables[i + 1][1]:
-                    fn(*tables[i + 1])
+        for chunks, n, fn in self._walk(*self._tail_plan(sp, launches)):
+            fn(chunks, n)
 
     # -- global gradient-norm clipping ---------------------------------------------------------
     def _clip_on(self) -> bool:
@@ -562,64 +602,68 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def _launch_clipped(self, sp, launches, native: bool) -> None:
         """`_launch_split` with clipping: the per-chunk sums of squares of every launch's chunk
-        table (each its own slice of the partials buffer, in launch order), finalize, then the
-        updates with the clip coefficient.  With a pending DDP tail: the sums of everything
-        below the first in-flight piece, then per piece wait + its sums, finalize, all updates."""
-        tail = sp.pending_tail
-        sp.pending_tail = None
-        if tail is None:
-            parts = [((sp.chunk_table(ps, flags),), fn) for ps, flags, fn in launches]
-            waits = []
-        else:
-            starts = [off for off, _ in tail]
-            parts = [(sp.chunk_table_splits(ps, flags, starts), fn) for ps, flags, fn in launches]
-            waits = [wait for _, wait in tail]
-        z = sp.zero
+        table (each its own slice of the partials buffer, in launch order), the norm and the clip
+        coefficient, then the updates with it.  With a pending DDP tail: the sums of everything
+        below the first in-flight piece, then per piece wait + its sums, the norm, all updates."""
+        parts, waits = self._tail_plan(sp, launches)
         ws = self._clip_buffers(sp.device, sum(n for tables, _ in parts for _, n in tables), sp.max_chunks(),
-                                1 if z is None else z.world)
-        ext = gpu_ext() if native else None
-        max_norm = float(self.max_grad_norm)
-        if not native:
-            ws["local"].zero_()
-        total = 0
-        for i in range(len(waits) + 1):
-            if i:
-                waits[i - 1]()
-            for tables, _ in parts:
-                chunks, n = tables[i]
-                if not n:
-                    continue
-                if native:
-                    ext.gradnorm_partial(chunks, n, sp.grad, ws["partial"], total)
-                else:  # CPU reference: per-chunk sum(g * g) in fp32, added in table order
-                    for start, ln, _, _ in self._rows(chunks, n):
-                        g = sp.grad[start:start + ln]
-                        ws["local"] += (g * g).sum()
-                total += n
+                                1 if sp.zero is None else sp.zero.world)
+        pieces = self._walk(parts, waits)
         if native:
-            ext.gradnorm_finalize(ws["partial"], total, sp.grad_scale, max_norm, ws["out"],
-                                  None if z is None else ws["local"])
-        if z is not None:
-            import torch.distributed as dist
-
-            # all-gather (not all-reduce) + a rank-order sum: the same bits on every rank
-            dist.all_gather_into_tensor(ws["gather"], ws["local"], group=z.group)
-            if native:
-                ext.gradnorm_combine(ws["gather"], z.world, sp.grad_scale, max_norm, ws["out"])
-        if native:
-            clip = ws["out"].data_ptr()
+            clip = self._norm_native(sp, ws, self._sums_native(sp, ws, pieces))
         else:
-            s = ws["local"][0]
-            if z is not None:
-                s = ws["gather"][0]
-                for r in range(1, z.world):
-                    s = s + ws["gather"][r]
-            clip = self._write_clip(ws["out"], s, sp.grad_scale, max_norm)
-        for i in range(len(waits) + 1):
-            for tables, fn in parts:
-                chunks, n = tables[i]
-                if n:
-                    fn(chunks, n, clip)
+            self._add_sumsq(ws, (sp.grad[start:start + ln] for chunks, n, _ in pieces
+                                 for start, ln, _, _ in self._rows(chunks, n)))
+            clip = self._norm_cpu(sp, ws)
+        for chunks, n, fn in self._walk(parts, waits, wait=False):
+            fn(chunks, n, clip)
+
+    @staticmethod
+    def _sums_native(sp, ws, pieces) -> int:
+        """partial[k] = sum of squares of the k-th chunk, in fp64; returns the number of chunks."""
+        ext, total = gpu_ext(), 0
+        for chunks, n, _ in pieces:
+            ext.gradnorm_partial(chunks, n, sp.grad, ws["partial"], total)
+            total += n
+        return total
+
+    def _norm_native(self, sp, ws, total: int) -> int:
+        """out = {norm, coef} from the per-chunk sums, on the device; the address the update
+        kernels read the coefficient from."""
+        ext, z, max_norm = gpu_ext(), sp.zero, float(self.max_grad_norm)
+        ext.gradnorm_finalize(ws["partial"], total, sp.grad_scale, max_norm, ws["out"],
+                              None if z is None else ws["local"])
+        if z is not None:
+            self._gather_sums(z, ws)
+            ext.gradnorm_combine(ws["gather"], z.world, sp.grad_scale, max_norm, ws["out"])
+        return ws["out"].data_ptr()
+
+    @staticmethod
+    def _add_sumsq(ws, grads) -> None:
+        """CPU reference: local = sum over `grads` of sum(g * g), in fp32, added in the order given
+        (the chunk tables' / the parameters')."""
+        ws["local"].zero_()
+        for g in grads:
+            ws["local"] += (g * g).sum()
+
+    def _norm_cpu(self, sp, ws) -> float:
+        """`_norm_native` with torch ops; returns the coefficient as a host float."""
+        z = sp.zero
+        s = ws["local"][0]
+        if z is not None:
+            self._gather_sums(z, ws)
+            s = ws["gather"][0]
+            for r in range(1, z.world):
+                s = s + ws["gather"][r]
+        return self._write_clip(ws["out"], s, sp.grad_scale, float(self.max_grad_norm))
+
+    @staticmethod
+    def _gather_sums(z, ws) -> None:
+        """ZeRO-1: every rank's local sum -> `gather` on every rank."""
+        import torch.distributed as dist
+
+        # all-gather (not all-reduce) + a rank-order sum: the same bits on every rank
+        dist.all_gather_into_tensor(ws["gather"], ws["local"], group=z.group)
 
     def _plain_clip(self):
         """Clip coefficient of the per-tensor CPU step (None: clipping off): the same
@@ -629,10 +673,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         ps = [p for group in self.param_groups for p in self._with_grad(group)]
         dev = ps[0].device if ps else self._all_params()[0].device
         ws = self._clip_buffers(dev)
-        ws["local"].zero_()
-        for p in ps:
-            g = p.grad.float()
-            ws["local"] += (g * g).sum()
+        self._add_sumsq(ws, (p.grad.float() for p in ps))
         sp = space_of(self._all_params())
         return self._write_clip(ws["out"], ws["local"][0], 1.0 if sp is None else sp.grad_scale,
                                 float(self.max_grad_norm))
@@ -732,35 +773,43 @@ class FusedAdamW(_FlatOptimizer):
             self._bind_state(p)
         b1, b2 = group["betas"]
         wd = group["weight_decay"]
-        out = []
-        if self.capturable:
+        cap = self.capturable
+        if cap:
             # device path: lr = table[group][count], bias corrections = row t, t = count + 1 + off
             dev, gi = self._dev, self._group_index(group)
             bc = dev["bc"].get((b1, b2))
             if bc is None:
                 raise RuntimeError(f"capturable FusedAdamW: betas {(b1, b2)} changed after construction")
             now = self._step_count + 1  # the optimizer step these launches belong to
-            for step, sub in self._count(ps).items():
-                def fn(chunks, n, clip=0, group=group, gi=gi, bc=bc, b1=b1, b2=b2, wd=wd, off=step - now):
-                    ext.adamw_dev(chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"],
-                                  sp.shadow, dev["count"], dev["lr"], gi, bc, off, b1, b2, group["eps"], wd,
-                                  sp.grad_scale, sp.skip_ptr, clip, self.rounding_seed)
-
-                out.append((sub, [wd != 0.0] * len(sub), fn))
-            return out
+        out = []
         for step, sub in self._count(ps).items():
-            def fn(chunks, n, clip=0, group=group, b1=b1, b2=b2, wd=wd, step=step):
-                ext.adamw(chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"],
-                          sp.shadow, group["lr"], b1, b2, group["eps"], wd, 1 - b1 ** step,
-                          math.sqrt(1 - b2 ** step), sp.grad_scale, sp.skip_ptr, clip, self.rounding_seed, step)
+            def fn(chunks, n, clip=0, step=step):
+                bufs = (chunks, n, sp.data, sp.grad, self._bufs["exp_avg"], self._bufs["exp_avg_sq"], sp.shadow)
+                if cap:
+                    ext.adamw_dev(*bufs, dev["count"], dev["lr"], gi, bc, step - now, b1, b2, group["eps"], wd,
+                                  sp.grad_scale, sp.skip_ptr, clip, self.rounding_seed)
+                else:
+                    ext.adamw(*bufs, group["lr"], b1, b2, group["eps"], wd, 1 - b1 ** step,
+                              math.sqrt(1 - b2 ** step), sp.grad_scale, sp.skip_ptr, clip, self.rounding_seed, step)
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out
 
+    @staticmethod
+    def _torch_update(p, g, m, v, step: int, lr, b1, b2, eps, wd, decay: bool) -> None:
+        """torch.optim.AdamW's update of one tensor - a whole parameter or a slice of the flat
+        buffers - in place; `g` is the gradient with every factor applied."""
+        if decay:
+            p.mul_(1 - lr * wd)
+        m.lerp_(g, 1 - b1)
+        v.mul_(b2).addcmul_(g, g, value=1 - b2)
+        denom = (v.sqrt() / math.sqrt(1 - b2 ** step)).add_(eps)
+        p.addcdiv_(m, denom, value=-lr / (1 - b1 ** step))
+
     def _cpu_launches(self, group, ps) -> list:
         """CPU twin of `_native_launches` (ZeRO-1 on gloo): the per-tensor reference math of
-        `step`, applied chunk by chunk to the owned flat slices and the compact state.  With bf16
-        state the parameter update is that same math on the widened moments (so step 1 equals the
+        `_torch_update`, applied chunk by chunk to the owned flat slices and the compact state.  With
+        bf16 state the parameter update is that same math on the widened moments (so step 1 equals the
         fp32-state optimizer bit for bit), while the moments that are rounded and stored are
         computed with the kernel's own operation order: a few fp32 ulps from the former, and the
         same bits as the GPU keeps."""
@@ -801,12 +850,7 @@ class FusedAdamW(_FlatOptimizer):
                         v_st = (b2f.double() * v.double() + ((c2f * gr) * gr).double()).float()
                     if gs != 1.0:
                         g = g * gs
-                    if decay:
-                        p.mul_(1 - lr * wd)
-                    m.lerp_(g, 1 - b1)
-                    v.mul_(b2).addcmul_(g, g, value=1 - b2)
-                    denom = (v.sqrt() / math.sqrt(1 - b2 ** step)).add_(eps)
-                    p.addcdiv_(m, denom, value=-lr / (1 - b1 ** step))
+                    self._torch_update(p, g, m, v, step, lr, b1, b2, eps, wd, decay)
                     if bf16_state:  # the kernel's rounding: bits keyed by (seed, step, flat index)
                         w = sr_words(self.rounding_seed, step, start, ln)
                         ms.copy_(sr_bf16(m_st, w & 0xFFFF))
@@ -825,45 +869,24 @@ class FusedAdamW(_FlatOptimizer):
             by.setdefault(n, []).append(p)
         return by
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        from ..ops.gemm import flush_wgrads
+    def _check_capture(self) -> None:
+        if not self.capturable:
+            raise RuntimeError("FusedAdamW computes bias corrections on the host per step: not graph-capturable "
+                               "(construct it with capturable=True, use eager steps, or FusedSGD inside "
+                               "utils.graphs.CapturedStep)")
 
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        flush_wgrads()  # weight gradients deferred into a grouped launch (normally flushed by backward's end)
-        if self._flat_mode():
-            capturing = self._use_native() and torch.cuda.is_current_stream_capturing()
-            if capturing and not self.capturable:
-                raise RuntimeError("FusedAdamW computes bias corrections on the host per step: not graph-capturable "
-                                   "(construct it with capturable=True, use eager steps, or FusedSGD inside "
-                                   "utils.graphs.CapturedStep)")
-            self._begin_step(capturing)
-            before = dict(self._steps) if capturing else None
-            self._flat_step()
-            self._end_step(capturing, before)
-            return loss
-        self._begin_step()
-        self._step_count += 1
-        coef = self._plain_prelude()
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            ps = self._with_grad(group)
-            for step, sub in self._count(ps).items():
-                for p in sub:
-                    st = self.state[p]
-                    if "exp_avg" not in st:
-                        st["exp_avg"] = torch.zeros_like(p)
-                        st["exp_avg_sq"] = torch.zeros_like(p)
-                    g = p.grad if coef is None else p.grad * coef
-                    p.mul_(1 - group["lr"] * group["weight_decay"])
-                    st["exp_avg"].lerp_(g, 1 - b1)
-                    st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
-                    denom = (st["exp_avg_sq"].sqrt() / math.sqrt(1 - b2 ** step)).add_(group["eps"])
-                    p.addcdiv_(st["exp_avg"], denom, value=-group["lr"] / (1 - b1 ** step))
-        return loss
+    def _plain_update(self, group, ps, coef) -> None:
+        b1, b2 = group["betas"]
+        for step, sub in self._count(ps).items():
+            for p in sub:
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    st["exp_avg"] = torch.zeros_like(p)
+                    st["exp_avg_sq"] = torch.zeros_like(p)
+                g = p.grad if coef is None else p.grad * coef
+                # (decays unconditionally: with weight_decay = 0 a multiply by 1.0)
+                self._torch_update(p, g, st["exp_avg"], st["exp_avg_sq"], step, group["lr"], b1, b2, group["eps"],
+                                   group["weight_decay"], True)
 
 
 class FusedSGD(_FlatOptimizer):
@@ -886,113 +909,89 @@ class FusedSGD(_FlatOptimizer):
                                       nesterov=nesterov, maximize=False, foreach=None, differentiable=False,
                                       fused=None), max_grad_norm, lr_schedule, capturable)
 
+    def _first_parts(self, group, ps) -> list:
+        """[(params, first)]: torch's first momentum step is `buf = d` (a clone), so parameters
+        without a buffer yet form their own launch with first=True (and get their buffer here)."""
+        if group["momentum"] == 0.0:
+            return [(ps, False)]
+        fresh = [p for p in ps if "momentum_buffer" not in self.state[p]]
+        if not fresh:
+            return [(ps, False)]
+        old = [p for p in ps if "momentum_buffer" in self.state[p]]
+        for p in fresh:
+            self._bind_state(p)
+        return [(fresh, True)] + ([(old, False)] if old else [])
+
     def _native_launches(self, group, ps) -> list:
         sp, ext = self._space, gpu_ext()
         mom = group["momentum"]
         wd = group["weight_decay"]
-        # torch's first momentum step is `buf = d` (a clone): parameters without a buffer yet
-        # form their own launch with first=True
-        parts = [(ps, False)]
-        if mom != 0.0:
-            fresh = [p for p in ps if "momentum_buffer" not in self.state[p]]
-            if fresh:
-                old = [p for p in ps if "momentum_buffer" in self.state[p]]
-                parts = [(fresh, True)] + ([(old, False)] if old else [])
-            for p in fresh:
-                self._bind_state(p)
-        out = []
-        if self.capturable:  # device path: lr = table[group][count]
+        cap = self.capturable
+        if cap:  # device path: lr = table[group][count]
             dev, gi = self._dev, self._group_index(group)
-            for sub, first in parts:
-                def fn(chunks, n, clip=0, group=group, gi=gi, mom=mom, wd=wd, first=first):
-                    ext.sgd_dev(chunks, n, sp.data, sp.grad, self._bufs["momentum_buffer"] if mom != 0.0 else None,
-                                sp.shadow, dev["count"], dev["lr"], gi, mom, group["dampening"], wd,
-                                group["nesterov"], first, sp.grad_scale, sp.skip_ptr, clip)
-
-                out.append((sub, [wd != 0.0] * len(sub), fn))
-            return out
-        for sub, first in parts:
-            def fn(chunks, n, clip=0, group=group, mom=mom, wd=wd, first=first):
-                ext.sgd(chunks, n, sp.data, sp.grad, self._bufs["momentum_buffer"] if mom != 0.0 else None,
-                        sp.shadow, group["lr"], mom, group["dampening"], wd, group["nesterov"], first,
-                        sp.grad_scale, sp.skip_ptr, clip)
+        out = []
+        for sub, first in self._first_parts(group, ps):
+            def fn(chunks, n, clip=0, first=first):
+                bufs = (chunks, n, sp.data, sp.grad, self._bufs["momentum_buffer"] if mom != 0.0 else None, sp.shadow)
+                rest = (mom, group["dampening"], wd, group["nesterov"], first, sp.grad_scale, sp.skip_ptr, clip)
+                if cap:
+                    ext.sgd_dev(*bufs, dev["count"], dev["lr"], gi, *rest)
+                else:
+                    ext.sgd(*bufs, group["lr"], *rest)
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out
+
+    @staticmethod
+    def _torch_update(p, d, buf, first: bool, lr, mom, damp, wd, nest):
+        """torch.optim.SGD's update of one tensor - a whole parameter or a slice of the flat
+        buffers - in place; `d` is the gradient with every factor applied.  `buf`: the momentum
+        buffer (None: torch's first step clones one; `first`: an existing one takes `d`).  Returns
+        the buffer."""
+        if wd != 0:
+            d = d.add(p, alpha=wd)
+        if mom != 0:
+            if buf is None:
+                buf = torch.clone(d).detach()
+            elif first:
+                buf.copy_(d)
+            else:
+                buf.mul_(mom).add_(d, alpha=1 - damp)
+            d = d.add(buf, alpha=mom) if nest else buf
+        p.add_(d, alpha=-lr)
+        return buf
 
     def _cpu_launches(self, group, ps) -> list:
         """CPU twin of `_native_launches` (ZeRO-1 on gloo), torch.optim.SGD's math per chunk."""
         sp = self._space
         mom, wd, lr, damp, nest = (group["momentum"], group["weight_decay"], group["lr"], group["dampening"],
                                    group["nesterov"])
-        parts = [(ps, False)]
-        if mom != 0.0:
-            fresh = [p for p in ps if "momentum_buffer" not in self.state[p]]
-            if fresh:
-                old = [p for p in ps if "momentum_buffer" in self.state[p]]
-                parts = [(fresh, True)] + ([(old, False)] if old else [])
-            for p in fresh:
-                self._bind_state(p)
+        parts = self._first_parts(group, ps)
         buf_all = self._bufs.get("momentum_buffer")
         out = []
         for sub, first in parts:
             def fn(chunks, n, clip=None, first=first):
                 gs = sp.grad_scale if clip is None else sp.grad_scale * clip
                 for start, ln, decay, so in self._rows(chunks, n):
-                    p = sp.data[start:start + ln]
                     d = sp.grad[start:start + ln]
                     if gs != 1.0:
                         d = d * gs
-                    if wd != 0 and decay:
-                        d = d.add(p, alpha=wd)
-                    if mom != 0:
-                        b = buf_all[so:so + ln]
-                        if first:
-                            b.copy_(d)
-                        else:
-                            b.mul_(mom).add_(d, alpha=1 - damp)
-                        d = d.add(b, alpha=mom) if nest else b
-                    p.add_(d, alpha=-lr)
+                    self._torch_update(sp.data[start:start + ln], d, buf_all[so:so + ln] if mom != 0 else None, first,
+                                       lr, mom, damp, wd if decay else 0, nest)
 
             out.append((sub, [wd != 0.0] * len(sub), fn))
         return out
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        from ..ops.gemm import flush_wgrads
+    def _check_capture(self) -> None:
+        if not self.capturable and self._sched is not None and not self._sched.schedule.is_constant:
+            raise RuntimeError("FusedSGD with a learning-rate schedule: a captured step would freeze lr "
+                               "(construct it with capturable=True)")
 
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        flush_wgrads()  # weight gradients deferred into a grouped launch (normally flushed by backward's end)
-        if self._flat_mode():
-            native = self._use_native()
-            capturing = native and torch.cuda.is_current_stream_capturing()
-            if capturing and not self.capturable and self._sched is not None and not self._sched.schedule.is_constant:
-                raise RuntimeError("FusedSGD with a learning-rate schedule: a captured step would freeze lr "
-                                   "(construct it with capturable=True)")
-            self._begin_step(capturing)
-            self._flat_step()
-            self._end_step(capturing and native and self.capturable, None)
-            return loss
-        self._begin_step()
-        self._step_count += 1
-        coef = self._plain_prelude()
-        for group in self.param_groups:
-            mom = group["momentum"]
-            for p in self._with_grad(group):
-                d = p.grad if coef is None else p.grad * coef
-                if group["weight_decay"] != 0:
-                    d = d.add(p, alpha=group["weight_decay"])
-                if mom != 0:
-                    st = self.state[p]
-                    buf = st.get("momentum_buffer")
-                    if buf is None:
-                        buf = torch.clone(d).detach()
-                        st["momentum_buffer"] = buf
-                    else:
-                        buf.mul_(mom).add_(d, alpha=1 - group["dampening"])
-                    d = d.add(buf, alpha=mom) if group["nesterov"] else buf
-                p.add_(d, alpha=-group["lr"])
-        return loss
+    def _plain_update(self, group, ps, coef) -> None:
+        mom = group["momentum"]
+        for p in ps:
+            d = p.grad if coef is None else p.grad * coef
+            buf = self._torch_update(p, d, self.state[p].get("momentum_buffer") if mom != 0 else None, False,
+                                     group["lr"], mom, group["dampening"], group["weight_decay"], group["nesterov"])
+            if mom != 0:
+                self.state[p]["momentum_buffer"] = buf

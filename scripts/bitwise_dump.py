@@ -4,6 +4,13 @@ in profiles/.
 
     python scripts/bitwise_dump.py attn|norm|resnet|gemm OUT.pt
     python -c "import torch; a, b = torch.load('A.pt'), torch.load('B.pt'); ..."   (compare)
+
+The `optim` family compares two COMMITS, not two builds: it covers the Python side of the fused
+optimizers' step as well, so drop this file into a checkout of the other commit, build the
+extension there and run it in both (profiles/optim_step_refactor_bitwise.md).
+
+    python scripts/bitwise_dump.py optim OUT.pt cpu|cuda
+    python scripts/bitwise_dump.py compare A.pt B.pt
 """
 import os
 import sys
@@ -79,5 +86,158 @@ def gemm():
     return out
 
 
+def optim(device="cpu"):
+    """The fused optimizers, every step path: {case: {step: {name: tensor | scalar | list}}}.  Uses the
+    public API and the private attributes the tests read, so it runs in older trees too."""
+    from ray_torch_distributed_checkpoint_amd.optim import BackwardOverlap, FusedAdamW, FusedSGD, LRSchedule
+    from ray_torch_distributed_checkpoint_amd.optim.flat import FlatParamSpace
+
+    dev = torch.device(device)
+    cuda = dev.type == "cuda"
+    # more than one 16384-element chunk, a sub-64 segment, tails that are no multiples of 4; the last
+    # parameter has no gradient in steps 1-2 (its Adam step number trails the optimizer's)
+    shapes = [(1027,), (64,), (5,), (40000,), (63,), (33, 7), (129,)]
+    late, steps = len(shapes) - 1, 6
+    gen = torch.Generator().manual_seed(11)
+    init = [torch.randn(s, generator=gen) for s in shapes]
+    grads = [[torch.randn(s, generator=gen).to(dev) for s in shapes] for _ in range(steps)]
+    kinds = {
+        "adamw": lambda g, kw: FusedAdamW(g, lr=1e-2, betas=(0.9, 0.95), **kw),
+        "adamw_bf16": lambda g, kw: FusedAdamW(g, lr=1e-2, betas=(0.9, 0.95), state_dtype=torch.bfloat16,
+                                               rounding_seed=5, **kw),
+        "sgd_nesterov": lambda g, kw: FusedSGD(g, lr=0.05, momentum=0.9, nesterov=True, **kw),
+        "sgd_plain": lambda g, kw: FusedSGD(g, lr=0.05, **kw),
+    }
+    variants = {
+        "base": {}, "clip": {"max_grad_norm": 0.5}, "gscale": {"grad_scale": 0.25},
+        "sched": {"lr_schedule": LRSchedule.warmup_cosine(2, 6)}, "tail": {"tail": True},
+        "tail_clip": {"tail": True, "max_grad_norm": 0.5},
+    }
+
+    def make(kind, kw, zero=False):
+        ps = [torch.nn.Parameter(t.clone().to(dev)) for t in init]
+        if zero:  # ZeRO-1 with one rank that owns everything: the chunk walk with torch ops, compact state
+            sp = FlatParamSpace(ps)
+            sp.set_zero(ZeroLayout([(0, sp.numel)], 0, 1))
+        groups = [{"params": ps[0::2], "weight_decay": 0.0}, {"params": ps[1::2], "weight_decay": 0.1}]
+        opt = kinds[kind](groups, kw)
+        return ps, opt, opt._ensure_space()
+
+    def snap(opt, sp, full=True):
+        if cuda:
+            torch.cuda.synchronize()
+        d = {}
+        if full:  # (reads the device counter of a captured optimizer back: only where that is meant)
+            for i, st in opt.state_dict()["state"].items():
+                for k, v in st.items():
+                    if not opt._bufs or k == "step":  # (the other values are views of the flat buffers below)
+                        d[f"state.{i}.{k}"] = v.clone() if torch.is_tensor(v) else v
+        d.update(data=sp.data.clone(), step_count=opt.step_count, lr=opt.get_last_lr())
+        if sp.shadow is not None:
+            d["shadow"] = sp.shadow.clone()
+        for k, b in opt._bufs.items():
+            d["buf." + k] = b.clone()
+        if opt._clip_ws is not None:
+            d["clip_out"], d["grad_norm"] = opt._clip_ws["out"].clone(), opt.grad_norm.clone()
+        return {k: v.cpu() if torch.is_tensor(v) else v for k, v in d.items()}
+
+    def set_grads(ps, sp, n, in_place):
+        for i, (p, g) in enumerate(zip(ps, grads[n])):
+            if i == late and n < 2:
+                p.grad = None
+            elif not in_place:
+                p.grad = g.clone()
+            else:  # into the flat slice: a gradient outside it would make the step wait for the tail first
+                if p.grad is None:
+                    p.grad = FlatParamSpace.view(sp.grad, sp.segment_of(p))
+                p.grad.copy_(g)
+
+    if not cuda:
+        import tempfile
+
+        import torch.distributed as dist
+        from ray_torch_distributed_checkpoint_amd.optim.flat import ZeroLayout
+
+        dist.init_process_group("gloo", init_method="file://" + tempfile.mktemp(), rank=0, world_size=1)
+    out = {}
+    for kind in kinds:
+        for vname, v in variants.items():
+            for mode in ("", ".capturable") if cuda else ("", ".zero1"):
+                kw = {k: x for k, x in v.items() if k in ("max_grad_norm", "lr_schedule")}
+                ps, opt, sp = make(kind, dict(kw, capturable=mode == ".capturable"), zero=mode == ".zero1")
+                sp.grad_scale = v.get("grad_scale", 1.0)
+                case = out[f"{kind}.{vname}{mode}"] = {}
+                for n in range(steps):
+                    set_grads(ps, sp, n, "tail" in v)
+                    if "tail" in v:  # a deferred last-bucket all-reduce in four pieces, odd offsets included
+                        sp.pending_tail = [(off, lambda: None) for off in (7, 1090, 1091, 20001)]
+                    opt.step()
+                    case[n + 1] = snap(opt, sp)
+    if not cuda:
+        dist.destroy_process_group()
+        return out
+
+    from ray_torch_distributed_checkpoint_amd.models import GPT2, GPT2Config
+    from ray_torch_distributed_checkpoint_amd.utils.graphs import CapturedStep
+
+    # captured steps: one eager warm-up step, three replays, then state_dict() (the read-back)
+    for kind, kw in (("adamw", {"capturable": True}), ("adamw_bf16", {"capturable": True}),
+                     ("sgd_nesterov", {"max_grad_norm": 0.5})):
+        ps, opt, sp = make(kind, kw)
+        for p, g in zip(ps, grads[0]):
+            p.grad = g.clone()
+        cs = CapturedStep(opt.step, warmup=1)
+        case = out[f"{kind}.graph"] = {0: snap(opt, sp, full=False)}
+        for n in (1, 2, 3):
+            for p, g in zip(ps, grads[n]):
+                p.grad.copy_(g)
+            cs.replay()
+            case[n] = snap(opt, sp, full=False)
+        cs.close()
+        case["end"] = snap(opt, sp)
+
+    for overlap in (False, True):
+        torch.manual_seed(0)
+        model = GPT2(GPT2Config.named("gpt2-tiny")).to(dev)
+        opt = FusedAdamW(model.parameters(), lr=1e-3, weight_decay=0.1)
+        if overlap:
+            BackwardOverlap(opt, bucket_mb=0.05)
+        g = torch.Generator(device=dev).manual_seed(1)
+        case = out["gpt2_tiny" + (".overlap" if overlap else "")] = {}
+        for n in range(3):
+            data = torch.randint(0, 1000, (4, 65), device=dev, generator=g)
+            loss = model(data[:, :-1], data[:, 1:])
+            loss.backward()
+            opt.step()
+            opt.zero_grad()
+            case[n + 1] = dict(snap(opt, opt.flat_space), loss=loss.item())
+    return out
+
+
+def compare(a, b, path=""):
+    """(values compared, paths that differ) of two dumps: tensors by torch.equal, the rest by ==."""
+    if isinstance(a, dict) and isinstance(b, dict) and a.keys() == b.keys():
+        n, bad = 0, []
+        for k in a:
+            dn, db = compare(a[k], b[k], f"{path}/{k}")
+            n, bad = n + dn, bad + db
+        return n, bad
+    if isinstance(a, (tuple, list)) and isinstance(b, (tuple, list)) and len(a) == len(b) and any(map(torch.is_tensor, a)):
+        return compare(dict(enumerate(a)), dict(enumerate(b)), path)
+    if torch.is_tensor(a) and torch.is_tensor(b):
+        same = a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
+    else:
+        same = type(a) is type(b) and a == b
+    return 1, [] if same else [path]
+
+
 if __name__ == "__main__":
-    torch.save({"attn": attn, "norm": norm, "resnet": resnet, "gemm": gemm}[sys.argv[1]](), sys.argv[2])
+    if sys.argv[1] == "compare":  # compare A.pt B.pt: the paths that differ, the totals; exit 1 on a mismatch
+        a, b = torch.load(sys.argv[2]), torch.load(sys.argv[3])
+        n, bad = compare(a, b)
+        for k in bad:
+            print("MISMATCH", k)
+        print(f"{len(a)} cases, {n} values compared, {len(bad)} mismatches")
+        sys.exit(1 if bad else 0)
+    family = {"attn": attn, "norm": norm, "resnet": resnet, "gemm": gemm, "optim": optim}[sys.argv[1]]
+    torch.save(family(*sys.argv[3:]), sys.argv[2])

@@ -106,6 +106,8 @@ def train_func_per_worker(config: Dict):
     if restart_ckpt is not None and (checkpoint is None or restart_ckpt.path != checkpoint.path):
         checkpoint, resume_mode = restart_ckpt, "exact"
     seed = config.get("seed")
+    # optional loss terms of ops.cross_entropy (both off: the call is the one it was)
+    xkw = {k: float(config[k]) for k in ("label_smoothing", "z_loss") if config.get(k)}
     device = train.torch.get_device()
     ctx = train.get_context()
     world, rank = ctx.get_world_size(), ctx.get_world_rank()
@@ -162,7 +164,7 @@ def train_func_per_worker(config: Dict):
 
         def graph_step():
             optimizer.zero_grad()
-            loss_ = ops.cross_entropy(model(sx), sy)
+            loss_ = ops.cross_entropy(model(sx), sy, **xkw)
             loss_.backward()
             optimizer.step()
             return loss_
@@ -200,7 +202,7 @@ def train_func_per_worker(config: Dict):
             with torch.cuda.stream(side) if warm else contextlib.nullcontext():
                 with phase("fwd"):
                     pred = model(X)
-                    loss = ops.cross_entropy(pred, y)
+                    loss = ops.cross_entropy(pred, y, **xkw)
                 optimizer.zero_grad()
                 with phase("bwd"):
                     loss.backward()
@@ -285,7 +287,11 @@ def train_fashion_mnist(
     max_failures=0,
     seed=None,
     hipgraph=True,
+    label_smoothing=0.0,
+    z_loss=0.0,
 ):
+    """label_smoothing / z_loss: the optional terms of `ops.cross_entropy` in the training loss
+    (0: off; the validation loss stays the plain cross-entropy)."""
     train_config = {
         "lr": learning_rate,
         "epochs": epochs,
@@ -297,6 +303,10 @@ def train_fashion_mnist(
         train_config["seed"] = seed
     if checkpoint is not None:
         train_config["checkpoint"] = checkpoint
+    if label_smoothing:
+        train_config["label_smoothing"] = float(label_smoothing)
+    if z_loss:
+        train_config["z_loss"] = float(z_loss)
     run_config = RunConfig(
         checkpoint_config=CheckpointConfig(num_to_keep=num_checkpoints_to_keep),
         storage_path=checkpoint_storage_path,

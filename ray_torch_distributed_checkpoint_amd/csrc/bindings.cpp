@@ -79,6 +79,14 @@ int rtdc_im2col(const void* x, void* cols, int B, int H, int W, int C, int Ho, i
 int rtdc_xent_finalize(const float* loss, const int64_t* target, int M, float fixed_n, int ignore, float* out,
                        hipStream_t st);
 int rtdc_xent_alpha(const float* g, const float* den, float* out, hipStream_t st);
+int rtdc_xent_aux(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse, int64_t* argmax,
+                  int M, int V, int ld, float grad_scale, int ignore_index, float eps, float z, float* ce, int is_bf16,
+                  hipStream_t st);
+int rtdc_xent_finalize_ce(const float* loss, const float* ce, const int64_t* target, int M, float fixed_n, int ignore,
+                          float* out, hipStream_t st);
+int rtdc_xent_bwd_aux(const void* logits, void* dlogits, const int64_t* target, const float* lse, const float* g,
+                      const float* den, int M, int V, int ignore_index, float eps, float z, int is_bf16,
+                      hipStream_t st);
 int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* target, const float* lse, const float* g,
                   const float* den, int M, int V, int ignore_index, int is_bf16, hipStream_t st);
 int rtdc_nchw_to_nhwc_bf16(const float* x, void* y, int B, int C, long long HW, hipStream_t st);
@@ -355,9 +363,21 @@ static void colsum(Tensor X, int64_t M, int64_t N, int64_t ld, Tensor ws, int64_
 }
 
 // ---------------------------------------------------------------------------------- xent
+// label smoothing in [0, 1) and z-loss coefficient >= 0 (both 0: the plain kernels)
+static void check_xent_coeffs(double label_smoothing, double z_loss, const char* op) {
+  TORCH_CHECK_VALUE(label_smoothing >= 0.0 && label_smoothing < 1.0, op, ": label_smoothing must be in [0, 1), got ",
+                    label_smoothing);
+  TORCH_CHECK_VALUE(z_loss >= 0.0, op, ": z_loss must be >= 0, got ", z_loss);
+}
+
+// label_smoothing / z_loss: loss rows become lse - (1 - e) x_t - (e / V) sum_j x_j + z lse^2 and the
+// gradient its derivative; ce (optional, fp32 [M]) receives the plain lse - x_t.  Both 0: the plain
+// kernels run (and ce, if given, is the loss).
 static void xent(Tensor logits, c10::optional<Tensor> dlogits, c10::optional<Tensor> target,
                  c10::optional<Tensor> loss, c10::optional<Tensor> lse, c10::optional<Tensor> argmax, int64_t M,
-                 int64_t V, int64_t ld, double grad_scale, int64_t ignore_index) {
+                 int64_t V, int64_t ld, double grad_scale, int64_t ignore_index, double label_smoothing,
+                 double z_loss, c10::optional<Tensor> ce) {
+  check_xent_coeffs(label_smoothing, z_loss, "xent");
   TORCH_CHECK(logits.is_cuda(), "xent: GPU tensor expected");
   TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
               "xent: logits must be fp32 or bf16");
@@ -375,11 +395,26 @@ static void xent(Tensor logits, c10::optional<Tensor> dlogits, c10::optional<Ten
   if (lse.has_value()) TORCH_CHECK(lse->scalar_type() == at::kFloat && lse->numel() >= M, "xent: lse fp32 [M]");
   if (argmax.has_value())
     TORCH_CHECK(argmax->scalar_type() == at::kLong && argmax->numel() >= M, "xent: argmax int64 [M]");
+  if (ce.has_value())
+    TORCH_CHECK(ce->is_cuda() && ce->scalar_type() == at::kFloat && ce->is_contiguous() && ce->numel() >= M,
+                "xent: ce must be a contiguous fp32 [M] GPU tensor");
+  const bool plain = (float)label_smoothing == 0.f && (float)z_loss == 0.f;
+  if (!plain) {
+    check_rc(rtdc_xent_aux(logits.data_ptr(), ptr_or_null(dlogits), (const int64_t*)ptr_or_null(target),
+                           (float*)ptr_or_null(loss), (float*)ptr_or_null(lse), (int64_t*)ptr_or_null(argmax), (int)M,
+                           (int)V, (int)ld, (float)grad_scale, (int)ignore_index, (float)label_smoothing,
+                           (float)z_loss, (float*)ptr_or_null(ce), logits.scalar_type() == at::kBFloat16,
+                           cur_stream()),
+             "xent");
+    return;
+  }
+  if (ce.has_value() && !loss.has_value()) loss = ce;  // without the terms the plain loss is ce
   check_rc(rtdc_xent(logits.data_ptr(), ptr_or_null(dlogits), (const int64_t*)ptr_or_null(target),
                      (float*)ptr_or_null(loss), (float*)ptr_or_null(lse), (int64_t*)ptr_or_null(argmax), (int)M,
                      (int)V, (int)ld, (float)grad_scale, (int)ignore_index,
                      logits.scalar_type() == at::kBFloat16, cur_stream()),
            "xent");
+  if (ce.has_value() && ce->data_ptr() != loss->data_ptr()) ce->narrow(0, 0, M).copy_(loss->narrow(0, 0, M));
 }
 
 // ---------------------------------------------------------------------------------- optim
@@ -1004,7 +1039,9 @@ static void bn_bwd(Tensor dy, Tensor y, Tensor x, Tensor mean, Tensor rstd, Tens
 }
 // mean cross-entropy from per-row losses: out[0] = loss, out[1] = divisor (device count of
 // non-ignored targets, or fixed_n when target is None)
-static void xent_finalize(Tensor loss, c10::optional<Tensor> target, double fixed_n, Tensor out) {
+// ce (optional, fp32 rows like loss): out[2] = mean plain cross-entropy over the same divisor
+static void xent_finalize(Tensor loss, c10::optional<Tensor> target, double fixed_n, Tensor out,
+                          c10::optional<Tensor> ce) {
   check_dev(loss, "loss");
   TORCH_CHECK(loss.scalar_type() == at::kFloat && loss.is_contiguous() && out.scalar_type() == at::kFloat &&
                   out.numel() >= 2 && out.is_contiguous(),
@@ -1014,6 +1051,15 @@ static void xent_finalize(Tensor loss, c10::optional<Tensor> target, double fixe
     TORCH_CHECK(target->scalar_type() == at::kLong && target->is_contiguous() && target->numel() == loss.numel(),
                 "xent_finalize: int64 target per row");
     t = target->data_ptr<int64_t>();
+  }
+  if (ce.has_value()) {
+    TORCH_CHECK(ce->is_cuda() && ce->scalar_type() == at::kFloat && ce->is_contiguous() &&
+                    ce->numel() == loss.numel() && out.numel() >= 3,
+                "xent_finalize: fp32 ce rows matching loss / fp32 out[3]");
+    check_rc(rtdc_xent_finalize_ce(loss.data_ptr<float>(), ce->data_ptr<float>(), t, (int)loss.numel(),
+                                   (float)fixed_n, -100, out.data_ptr<float>(), cur_stream()),
+             "xent_finalize");
+    return;
   }
   check_rc(rtdc_xent_finalize(loss.data_ptr<float>(), t, (int)loss.numel(), (float)fixed_n, -100,
                               out.data_ptr<float>(), cur_stream()),
@@ -1026,8 +1072,10 @@ static void xent_alpha(Tensor g, Tensor den, Tensor out) {
            "xent_alpha");
 }
 // dlogits = (g[0] / den[0]) * (softmax - onehot) of dense [M, V] logits from the saved row logsumexp
+// (label_smoothing / z_loss as in xent; both 0: the plain kernels)
 static void xent_bwd(Tensor logits, Tensor dlogits, Tensor target, Tensor lse, Tensor g, Tensor den,
-                     int64_t ignore_index) {
+                     int64_t ignore_index, double label_smoothing, double z_loss) {
+  check_xent_coeffs(label_smoothing, z_loss, "xent_bwd");
   TORCH_CHECK(logits.is_cuda() && dlogits.is_cuda(), "xent_bwd: GPU tensors expected");
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && dlogits.is_contiguous() &&
                   dlogits.numel() == logits.numel() && logits.scalar_type() == dlogits.scalar_type() &&
@@ -1041,6 +1089,14 @@ static void xent_bwd(Tensor logits, Tensor dlogits, Tensor target, Tensor lse, T
   TORCH_CHECK(g.is_cuda() && den.is_cuda() && g.scalar_type() == at::kFloat && den.scalar_type() == at::kFloat &&
                   g.numel() >= 1 && den.numel() >= 1,
               "xent_bwd: fp32 scalars");
+  if ((float)label_smoothing != 0.f || (float)z_loss != 0.f) {
+    check_rc(rtdc_xent_bwd_aux(logits.data_ptr(), dlogits.data_ptr(), target.data_ptr<int64_t>(),
+                               lse.data_ptr<float>(), g.data_ptr<float>(), den.data_ptr<float>(), (int)M, (int)V,
+                               (int)ignore_index, (float)label_smoothing, (float)z_loss,
+                               logits.scalar_type() == at::kBFloat16, cur_stream()),
+             "xent_bwd");
+    return;
+  }
   check_rc(rtdc_xent_bwd(logits.data_ptr(), dlogits.data_ptr(), target.data_ptr<int64_t>(), lse.data_ptr<float>(),
                          g.data_ptr<float>(), den.data_ptr<float>(), (int)M, (int)V, (int)ignore_index,
                          logits.scalar_type() == at::kBFloat16, cur_stream()),
@@ -1232,7 +1288,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum_partial", &colsum_partial);
   m.def("colsum_multi", &colsum_multi);
   m.def("colsum", &colsum);
-  m.def("xent", &xent);
+  m.def("xent", &xent, py::arg("logits"), py::arg("dlogits"), py::arg("target"), py::arg("loss"), py::arg("lse"),
+        py::arg("argmax"), py::arg("M"), py::arg("V"), py::arg("ld"), py::arg("grad_scale"), py::arg("ignore_index"),
+        py::arg("label_smoothing") = 0.0, py::arg("z_loss") = 0.0, py::arg("ce") = py::none());
   m.def("adamw", &adamw, py::arg("chunks"), py::arg("nchunks"), py::arg("p"), py::arg("g"), py::arg("m"),
         py::arg("v"), py::arg("shadow"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
         py::arg("bc1"), py::arg("bc2_sqrt"), py::arg("grad_scale"), py::arg("skip_ptr") = 0,
@@ -1296,9 +1354,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_dw_s2d", &stem_dw_s2d);
   m.def("conv_w_flip_t", &conv_w_flip_t);
   m.def("maxpool_fwd", &maxpool_fwd);
-  m.def("xent_finalize", &xent_finalize);
+  m.def("xent_finalize", &xent_finalize, py::arg("loss"), py::arg("target"), py::arg("fixed_n"), py::arg("out"),
+        py::arg("ce") = py::none());
   m.def("xent_alpha", &xent_alpha);
-  m.def("xent_bwd", &xent_bwd);
+  m.def("xent_bwd", &xent_bwd, py::arg("logits"), py::arg("dlogits"), py::arg("target"), py::arg("lse"), py::arg("g"),
+        py::arg("den"), py::arg("ignore_index"), py::arg("label_smoothing") = 0.0, py::arg("z_loss") = 0.0);
   m.def("nchw_to_nhwc_bf16", &nchw_to_nhwc_bf16);
   m.def("copy2d", &copy2d);
   m.def("maxpool_bwd", &maxpool_bwd);

@@ -8,6 +8,19 @@
 // row (L2-resident: one 100 KB GPT-2 row per block) and writes scale*(softmax - onehot);
 // padded vocabulary columns [V, ld) get exactly 0.  Rows whose target is ignore_index get a
 // zero loss and zero gradient.
+//
+// Two optional loss terms, behind the compile-time switch AUX of every row kernel (the plain
+// kernels are the AUX = false instantiations and compile to the code they were, see
+// profiles/xent_aux_isa.txt; e = z = 0 is routed to them): label smoothing e and the auxiliary
+// z-loss z * lse^2.  Per row with a valid target t,
+// over the real columns j < V, with u = e / V and a = 1 + 2 z lse:
+//   L       = lse - (1 - e) x_t - u * sum_j x_j + z * lse^2
+//   dL/dx_j = a * softmax_j - u - (1 - e) [j == t]
+// The uniform term -u does not vanish by itself where exp() does, so padding columns [V, ld) and
+// ignored rows are masked explicitly and stay exactly +0.  sum_j x_j is a fixed-order reduction
+// (thread-serial, wave butterfly, waves in order) over the real columns only, read - like x_t -
+// before any store of the row, so dlogits may still alias logits.  `ce` (optional) receives the
+// plain lse - x_t per row.
 #include "gemm_common.h"
 
 #include <cstdlib>
@@ -56,6 +69,16 @@ __device__ __forceinline__ void stvec<bf16_t>(bf16_t* p, const float* v) {
                           pack_bf2(v[6], v[7]));
 }
 
+// The arguments of the AUX = true instantiations (label smoothing eps, z-loss z, optional per-row
+// plain cross-entropy ce); the plain ones take an empty struct and read nothing.
+template <bool AUX>
+struct XentAux {};
+template <>
+struct XentAux<true> {
+  float eps, z;
+  float* ce;
+};
+
 struct OnlineMax {
   float m, s;
   int arg;
@@ -82,18 +105,20 @@ __device__ __forceinline__ OnlineMax om_merge(OnlineMax a, OnlineMax b) {
   return a;
 }
 
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool AUX = false>
 __global__ __launch_bounds__(256) void xent_kernel(const T* logits, T* dlogits,
                                                   const int64_t* __restrict__ target, float* __restrict__ loss,
                                                   float* __restrict__ lse_out, int64_t* __restrict__ argmax,
                                                   int M, int V, int ld, float grad_scale,
-                                                  int ignore_index) {
+                                                  int ignore_index, XentAux<AUX> aux) {
   __shared__ float sm[4], ss[4];
   __shared__ int sa[4];
+  [[maybe_unused]] __shared__ float ssx[4];  // AUX: the waves' partial row sums
   const int row = blockIdx.x;
   if (row >= M) return;
   const T* x = logits + (long long)row * ld;
   OnlineMax o{-INFINITY, 0.f, 0x7fffffff};
+  [[maybe_unused]] float sx = 0.f;  // AUX: this thread's share of sum_j x_j over the real columns
   if constexpr (VEC) {
     // 8 elements per 16-B load (bf16) / 4 (fp32); U loads in flight per thread, and the running
     // max is rescaled once per 16-B chunk (chunk max first) instead of a data-dependent branch
@@ -106,8 +131,10 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* logits, T* dlogits,
         const int c = c0 + u * 256 * E;
         if (c < ld) ldvec<T>(x + c, v[u]);
 #pragma unroll
-        for (int e = 0; e < E; ++e)
+        for (int e = 0; e < E; ++e) {
           if (c >= ld || c + e >= V) v[u][e] = -INFINITY;
+          else if constexpr (AUX) sx += v[u][e];  // before the row's first store; padding never enters
+        }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -132,7 +159,11 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* logits, T* dlogits,
       }
     }
   } else {
-    for (int j = threadIdx.x; j < V; j += 256) om_push(o, ldv<T>(x, j), j);
+    for (int j = threadIdx.x; j < V; j += 256) {
+      const float xv = ldv<T>(x, j);
+      om_push(o, xv, j);
+      if constexpr (AUX) sx += xv;
+    }
   }
   // wave combine
 #pragma unroll
@@ -148,18 +179,33 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* logits, T* dlogits,
   const int64_t tgt = target ? target[row] : -1;
   const bool valid = target && tgt != ignore_index && tgt >= 0 && tgt < V;
   const float xt = (threadIdx.x == 0 && valid) ? ldv<T>(x, tgt) : 0.f;
+  if constexpr (AUX) sx = wave_sum(sx);
   if ((threadIdx.x & 63) == 0) {
     sm[w] = o.m;
     ss[w] = o.s;
     sa[w] = o.arg;
+    if constexpr (AUX) ssx[w] = sx;
   }
   __syncthreads();
   OnlineMax r{sm[0], ss[0], sa[0]};
 #pragma unroll
   for (int i = 1; i < 4; ++i) r = om_merge(r, OnlineMax{sm[i], ss[i], sa[i]});
   const float lse = r.m + __logf(r.s);
+  // AUX: u = e / V (a true division), a = 1 + 2 z lse; an ignored row keeps neither term
+  [[maybe_unused]] float u = 0.f, a = 1.f, hot = 1.f;
+  if constexpr (AUX) {
+    u = valid ? aux.eps / (float)V : 0.f;
+    a = 1.f + 2.f * aux.z * lse;
+    hot = 1.f - aux.eps;
+  }
   if (threadIdx.x == 0) {
-    if (loss) loss[row] = valid ? lse - xt : 0.f;
+    if constexpr (AUX) {
+      const float sumx = (ssx[0] + ssx[1]) + (ssx[2] + ssx[3]);
+      if (loss) loss[row] = valid ? lse - hot * xt - u * sumx + aux.z * lse * lse : 0.f;
+      if (aux.ce) aux.ce[row] = valid ? lse - xt : 0.f;
+    } else {
+      if (loss) loss[row] = valid ? lse - xt : 0.f;
+    }
     if (lse_out) lse_out[row] = lse;
     if (argmax) argmax[row] = r.arg;
   }
@@ -176,14 +222,21 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* logits, T* dlogits,
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int j = c + e;
-        gv[e] = j < V ? sc * (__expf(v[e] - lse) - (j == tgt ? 1.f : 0.f)) : 0.f;
+        if constexpr (AUX)
+          gv[e] = j < V ? sc * (a * __expf(v[e] - lse) - u - (j == tgt ? hot : 0.f)) : 0.f;
+        else
+          gv[e] = j < V ? sc * (__expf(v[e] - lse) - (j == tgt ? 1.f : 0.f)) : 0.f;
       }
       stvec<T>(dx + c, gv);
     }
   } else {
     for (int j = threadIdx.x; j < ld; j += 256) {
       float gv = 0.f;
-      if (j < V) gv = sc * (__expf(ldv<T>(x, j) - lse) - (j == tgt ? 1.f : 0.f));
+      if constexpr (AUX) {
+        if (j < V) gv = sc * (a * __expf(ldv<T>(x, j) - lse) - u - (j == tgt ? hot : 0.f));
+      } else {
+        if (j < V) gv = sc * (__expf(ldv<T>(x, j) - lse) - (j == tgt ? 1.f : 0.f));
+      }
       stv<T>(dx, j, gv);
     }
   }
@@ -235,6 +288,17 @@ __device__ __forceinline__ float block_sum2(float s, float* sred) {
   return r;
 }
 
+// a value that is the same in every lane of the wave, moved to a scalar register
+__device__ __forceinline__ float uniform(float x) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
+}
+// acc + both bf16 halves of w, in one instruction and without unpacking: v_dot2c_f32_bf16 against
+// the pair (1, 1) (the products by 1 are exact)
+__device__ __forceinline__ float add_bf2(uint32_t w, float acc) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w), __builtin_bit_cast(bf16x2_t, 0x3f803f80u),
+                                         acc, false);
+}
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
@@ -248,13 +312,15 @@ __device__ __forceinline__ void opaque(uint32_t (&v)[NCH][4]) {
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(v[c][i]));
 }
 
-template <int NT, int NCH, bool ARG>
+template <int NT, int NCH, bool ARG, bool AUX = false>
 __global__ __launch_bounds__(NT) void xent_reg_kernel(const bf16_t* logits, bf16_t* dlogits,
                                                      const int64_t* __restrict__ target, float* __restrict__ loss,
                                                      float* __restrict__ lse_out, int64_t* __restrict__ argmax,
-                                                     int M, int V, int ld, float grad_scale, int ignore_index) {
+                                                     int M, int V, int ld, float grad_scale, int ignore_index,
+                                                     XentAux<AUX> aux) {
   __shared__ float sred[NT / 64];
   __shared__ int sarg[NT / 64];
+  [[maybe_unused]] __shared__ float sred2[NT / 64];  // AUX: the waves' row sums
   const int row = blockIdx.x;
   const bf16_t* x = logits + (long long)row * ld;
   const int tid = threadIdx.x;
@@ -283,12 +349,39 @@ __global__ __launch_bounds__(NT) void xent_reg_kernel(const bf16_t* logits, bf16
                                                : (v[c][e >> 1] & 0xffff0000u) | 0x0000ff80u;
     }
   }
+  [[maybe_unused]] float sx = 0.f;  // AUX: this thread's share of sum_j x_j, j < V
+  if constexpr (AUX) {
+    // The row sum, from the packed words: four dot instructions per chunk, nothing unpacked, no
+    // register held longer.  A pass of its own behind the loads (a branch between two loads would
+    // keep the second from being issued ahead of the first one's data).  The outer test is the
+    // same in every lane - a scalar branch; only the chunk row that holds column V looks at its
+    // own columns, where the padding is -inf by now and must not be added.
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if ((c + 1) * NT * 8 <= V) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sx = add_bf2(v[c][i], sx);
+      } else if (c * NT * 8 < V) {
+        const int col = (c * NT + tid) * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e < V) sx += e & 1 ? bf_hi(v[c][e >> 1]) : bf_lo(v[c][e >> 1]);
+      }
+    }
+  }
   float m = -INFINITY;
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) m = fmaxf(m, fmaxf(bf_lo(v[c][i]), bf_hi(v[c][i])));
+  if constexpr (AUX) {
+    // the waves' row sums go to their own LDS row now (block_max_arg's barrier publishes them) and
+    // thread 0 adds them in wave order when it writes the loss: sx is dead before the exp pass
+    sx = wave_sum(sx);
+    if ((tid & 63) == 0) sred2[tid >> 6] = sx;
+  }
   int arg = 0x7fffffff;
+  if constexpr (ARG && AUX) opaque(v);  // (the argmax pass unpacks again: the max pass's floats are not kept for it)
   if constexpr (ARG) {  // first column holding the maximum (per thread columns ascend with c, e)
     const float mt = m;
 #pragma unroll
@@ -308,8 +401,23 @@ __global__ __launch_bounds__(NT) void xent_reg_kernel(const bf16_t* logits, bf16
     for (int i = 0; i < 4; ++i) s += __expf(bf_lo(v[c][i]) - m) + __expf(bf_hi(v[c][i]) - m);
   s = block_sum2<NT>(s, sred);
   const float lse = m + __logf(s);
+  // AUX: u = e / V (a true division), a = 1 + 2 z lse; an ignored row keeps neither term
+  [[maybe_unused]] float u = 0.f, a = 1.f, hot = 1.f;
+  if constexpr (AUX) {
+    u = valid ? aux.eps / (float)V : 0.f;
+    a = 1.f + 2.f * aux.z * lse;
+    hot = 1.f - aux.eps;
+  }
   if (tid == 0) {
-    if (loss) loss[row] = valid ? lse - xt : 0.f;
+    if constexpr (AUX) {
+      float sumx = 0.f;
+#pragma unroll
+      for (int i = 0; i < NT / 64; ++i) sumx += sred2[i];
+      if (loss) loss[row] = valid ? lse - hot * xt - u * sumx + aux.z * lse * lse : 0.f;
+      if (aux.ce) aux.ce[row] = valid ? lse - xt : 0.f;
+    } else {
+      if (loss) loss[row] = valid ? lse - xt : 0.f;
+    }
     if (lse_out) lse_out[row] = lse;
     if (argmax) argmax[row] = arg;
   }
@@ -318,10 +426,44 @@ __global__ __launch_bounds__(NT) void xent_reg_kernel(const bf16_t* logits, bf16
   opaque(v);
   const auto rd = make_rsrc(dlogits + (long long)row * ld, 0, (long long)ld * 2);
   const float sc = valid ? grad_scale : 0.f;
+  [[maybe_unused]] float sa = 0.f, su = 0.f, sh = 0.f, lse_u = 0.f;
+  if constexpr (AUX) {
+    sa = uniform(sc * a);
+    su = uniform(sc * u);
+    sh = uniform(sc * hot);
+    lse_u = uniform(lse);
+  }
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int col = (c * NT + tid) * 8;
-    {
+    if constexpr (AUX) {
+      // sc * (a p - u - (1 - e)[j == t]) with sc multiplied into the three row constants, which
+      // are the same in every lane and live in scalar registers: one FMA per column, and no
+      // vector register more than the plain loop holds.  This is (sc a) p - (sc u) - (sc hot), not
+      // the literal sc * (a p - u - hot) that xent_kernel and xent_bwd_kernel compute: all fp32,
+      // still one rounding to bf16, but the same (e, z) row can differ by an fp32 ulp before that
+      // rounding between this kernel and those two (each is judged per element on its own).
+      float g[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        g[2 * i] = sa * __expf(bf_lo(v[c][i]) - lse_u) - su;
+        g[2 * i + 1] = sa * __expf(bf_hi(v[c][i]) - lse_u) - su;
+      }
+      const int o = (int)(tgt - col);
+      if (valid && (unsigned)o < 8u) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e == o) g[e] -= sh;
+      }
+      if ((c + 1) * NT * 8 > V) {  // (a scalar branch, as above)
+        // exp() zeroed the padding, -u did not: exactly +0 there
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e >= V) g[e] = 0.f;
+      }
+      // stores past the row are dropped by the descriptor's range check
+      __builtin_amdgcn_raw_buffer_store_b128(pack8bf(g), rd, tid * 16, c * NT * 16, 0);
+    } else {
       float g[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -353,10 +495,12 @@ static bool launch_xent_reg(const void* logits, void* dlogits, const int64_t* ta
   if (ld <= NT * NCH * 8) {                                                                                 \
     if (argmax)                                                                                              \
       hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, true>), dim3(M), dim3(NT), 0, st, (const bf16_t*)logits,  \
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index);  \
+                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,   \
+                         XentAux<false>{});                                                                   \
     else                                                                                                     \
       hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, false>), dim3(M), dim3(NT), 0, st, (const bf16_t*)logits, \
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index);  \
+                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,   \
+                         XentAux<false>{});                                                                   \
     return true;                                                                                             \
   }
   // NT x NCH x 8 columns; one wave per SIMD per block so several blocks share a CU and one
@@ -382,18 +526,70 @@ extern "C" int rtdc_xent(const void* logits, void* dlogits, const int64_t* targe
   if (is_bf16) {
     if (vec)
       hipLaunchKernelGGL((xent_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)logits,
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index);
+                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
+                         XentAux<false>{});
     else
       hipLaunchKernelGGL((xent_kernel<bf16_t, false>), grid, block, 0, st, (const bf16_t*)logits,
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index);
+                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
+                         XentAux<false>{});
   } else {
     if (vec)
       hipLaunchKernelGGL((xent_kernel<float, true>), grid, block, 0, st, (const float*)logits,
-                         (float*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index);
+                         (float*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, XentAux<false>{});
     else
       hipLaunchKernelGGL((xent_kernel<float, false>), grid, block, 0, st, (const float*)logits,
-                         (float*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index);
+                         (float*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, XentAux<false>{});
   }
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// the same ladder for the kernels with label smoothing / z-loss (the caller routes eps = z = 0
+// with no ce to rtdc_xent: the plain instantiations)
+static bool launch_xent_reg_aux(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
+                                int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index, float eps,
+                                float z, float* ce, hipStream_t st) {
+  if (ld % 8 != 0 || getenv("RTDC_XENT_TWO_PASS")) return false;
+  const XentAux<true> aux{eps, z, ce};
+#define XR(NT, NCH)                                                                                            \
+  if (ld <= NT * NCH * 8) {                                                                                   \
+    if (argmax)                                                                                                \
+      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, true, true>), dim3(M), dim3(NT), 0, st,                     \
+                         (const bf16_t*)logits, (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld,         \
+                         grad_scale, ignore_index, aux);                                                       \
+    else                                                                                                       \
+      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, false, true>), dim3(M), dim3(NT), 0, st,                    \
+                         (const bf16_t*)logits, (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld,         \
+                         grad_scale, ignore_index, aux);                                                       \
+    return true;                                                                                               \
+  }
+  XR(256, 4)
+  XR(256, 8)
+  XR(256, 16)
+  XR(256, 25)
+  XR(512, 16)
+  XR(1024, 16)
+#undef XR
+  return false;
+}
+
+extern "C" int rtdc_xent_aux(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
+                             int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index, float eps,
+                             float z, float* ce, int is_bf16, hipStream_t st) {
+  if (M < 1 || V < 1 || ld < V || !(eps >= 0.f && eps < 1.f) || !(z >= 0.f)) return 1;
+  const bool vec = (ld % 8 == 0);
+  if (is_bf16 && launch_xent_reg_aux(logits, dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
+                                     eps, z, ce, st))
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+  const XentAux<true> aux{eps, z, ce};
+#define XA(T, VEC)                                                                                         \
+  hipLaunchKernelGGL((xent_kernel<T, VEC, true>), dim3(M), dim3(256), 0, st, (const T*)logits, (T*)dlogits, \
+                     target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, aux)
+  if (is_bf16) {
+    if (vec) XA(bf16_t, true); else XA(bf16_t, false);
+  } else {
+    if (vec) XA(float, true); else XA(float, false);
+  }
+#undef XA
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -419,6 +615,30 @@ __global__ __launch_bounds__(1024) void xent_finalize_kernel(const float* __rest
   }
 }
 
+// the same with the rows of plain cross-entropy `ce` summed in the same fixed order next to the
+// loss rows: out[2] = sum ce / n
+__global__ __launch_bounds__(1024) void xent_finalize_ce_kernel(const float* __restrict__ loss,
+                                                               const float* __restrict__ ce,
+                                                               const int64_t* __restrict__ target, int M,
+                                                               float fixed_n, int ignore, float* __restrict__ out) {
+  __shared__ float red[16];
+  float s = 0.f, c = 0.f, e = 0.f;
+  for (int i = threadIdx.x; i < M; i += 1024) {
+    s += loss[i];
+    e += ce[i];
+    if (target) c += target[i] != ignore ? 1.f : 0.f;
+  }
+  s = block_sum<1024>(s, red);
+  c = block_sum<1024>(c, red);
+  e = block_sum<1024>(e, red);
+  if (threadIdx.x == 0) {
+    const float n = target ? fmaxf(c, 1.f) : fixed_n;
+    out[0] = s / n;
+    out[1] = n;
+    out[2] = e / n;
+  }
+}
+
 // out[0] = g[0] / den[0]: the upstream loss gradient over the divisor, as a device alpha
 __global__ void xent_alpha_kernel(const float* __restrict__ g, const float* __restrict__ den, float* __restrict__ out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = g[0] / den[0];
@@ -429,17 +649,25 @@ __global__ void xent_alpha_kernel(const float* __restrict__ g, const float* __re
 // here, so the gradient is formed in fp32 with them and rounded to the output type ONCE (scaling
 // a stored bf16 gradient rounded it twice: up to 0.5 * (1 + mantissa of the scale) ulp).  Rows
 // whose target is ignore_index (or out of range) get exactly 0.  One block per row.
-template <typename T, bool VEC>
+// AUX: with label smoothing eps and z-loss z, (g[0] / den[0]) * (a softmax - u - (1 - e) onehot).
+template <typename T, bool VEC, bool AUX = false>
 __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ logits, T* __restrict__ dlogits,
                                                       const int64_t* __restrict__ target,
                                                       const float* __restrict__ lse_in, const float* __restrict__ g,
-                                                      const float* __restrict__ den, int M, int V, int ignore_index) {
+                                                      const float* __restrict__ den, int M, int V, int ignore_index,
+                                                      XentAux<AUX> aux) {
   const int row = blockIdx.x;
   if (row >= M) return;
   const int64_t tgt = target[row];
   const bool valid = tgt != ignore_index && tgt >= 0 && tgt < V;
   const float sc = valid ? g[0] / den[0] : 0.f;
   const float lse = lse_in[row];
+  [[maybe_unused]] float u = 0.f, a = 1.f, hot = 1.f;
+  if constexpr (AUX) {
+    u = valid ? aux.eps / (float)V : 0.f;  // an ignored row stays exactly +0
+    a = 1.f + 2.f * aux.z * lse;
+    hot = 1.f - aux.eps;
+  }
   const T* x = logits + (long long)row * V;
   T* dx = dlogits + (long long)row * V;
   if constexpr (VEC) {  // V % 8 == 0 and an aligned base: every row starts 16-B aligned
@@ -448,19 +676,38 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
       float v[E], gv[E];
       ldvec<T>(x + c, v);
 #pragma unroll
-      for (int e = 0; e < E; ++e) gv[e] = sc * (__expf(v[e] - lse) - (c + e == tgt ? 1.f : 0.f));
+      for (int e = 0; e < E; ++e) {
+        if constexpr (AUX)
+          gv[e] = sc * (a * __expf(v[e] - lse) - u - (c + e == tgt ? hot : 0.f));
+        else
+          gv[e] = sc * (__expf(v[e] - lse) - (c + e == tgt ? 1.f : 0.f));
+      }
       stvec<T>(dx + c, gv);
     }
   } else {
-    for (int j = threadIdx.x; j < V; j += 256)
-      stv<T>(dx, j, sc * (__expf(ldv<T>(x, j) - lse) - (j == tgt ? 1.f : 0.f)));
+    for (int j = threadIdx.x; j < V; j += 256) {
+      if constexpr (AUX)
+        stv<T>(dx, j, sc * (a * __expf(ldv<T>(x, j) - lse) - u - (j == tgt ? hot : 0.f)));
+      else
+        stv<T>(dx, j, sc * (__expf(ldv<T>(x, j) - lse) - (j == tgt ? 1.f : 0.f)));
+    }
   }
 }
+
 }  // namespace rtdc
 
 extern "C" int rtdc_xent_finalize(const float* loss, const int64_t* target, int M, float fixed_n, int ignore, float* out,
                                   hipStream_t st) {
   hipLaunchKernelGGL(rtdc::xent_finalize_kernel, dim3(1), dim3(1024), 0, st, loss, target, M, fixed_n, ignore, out);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// out[0..1] as rtdc_xent_finalize, out[2] = mean of the plain cross-entropy rows `ce`
+extern "C" int rtdc_xent_finalize_ce(const float* loss, const float* ce, const int64_t* target, int M, float fixed_n,
+                                     int ignore, float* out, hipStream_t st) {
+  if (!ce) return 1;
+  hipLaunchKernelGGL(rtdc::xent_finalize_ce_kernel, dim3(1), dim3(1024), 0, st, loss, ce, target, M, fixed_n, ignore,
+                     out);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -477,7 +724,25 @@ extern "C" int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* t
   const bool vec = V % 8 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
 #define XB(T, VEC)                                                                                              \
   hipLaunchKernelGGL((rtdc::xent_bwd_kernel<T, VEC>), dim3(M), dim3(256), 0, st, (const T*)logits, (T*)dlogits, \
-                     target, lse, g, den, M, V, ignore_index)
+                     target, lse, g, den, M, V, ignore_index, rtdc::XentAux<false>{})
+  if (is_bf16) {
+    if (vec) XB(bf16_t, true); else XB(bf16_t, false);
+  } else {
+    if (vec) XB(float, true); else XB(float, false);
+  }
+#undef XB
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int rtdc_xent_bwd_aux(const void* logits, void* dlogits, const int64_t* target, const float* lse,
+                                 const float* g, const float* den, int M, int V, int ignore_index, float eps, float z,
+                                 int is_bf16, hipStream_t st) {
+  if (M < 1 || V < 1 || !(eps >= 0.f && eps < 1.f) || !(z >= 0.f)) return 1;
+  const bool vec = V % 8 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
+  const rtdc::XentAux<true> aux{eps, z, nullptr};
+#define XB(T, VEC)                                                                                        \
+  hipLaunchKernelGGL((rtdc::xent_bwd_kernel<T, VEC, true>), dim3(M), dim3(256), 0, st, (const T*)logits,  \
+                     (T*)dlogits, target, lse, g, den, M, V, ignore_index, aux)
   if (is_bf16) {
     if (vec) XB(bf16_t, true); else XB(bf16_t, false);
   } else {

@@ -95,9 +95,15 @@ class Block(nn.Module):
 
 
 class GPT2(nn.Module):
-    def __init__(self, cfg: GPT2Config):
+    def __init__(self, cfg: GPT2Config, z_loss: float = 0.0, label_smoothing: float = 0.0):
+        """z_loss / label_smoothing: the two optional terms of ops.lm_head_cross_entropy, plain
+        attributes (not in the config, not in the state_dict; settable later).  With either one
+        non-zero `forward(idx, targets)` still returns the optimised loss and leaves the mean
+        plain cross-entropy of that forward in `self.last_ce` (a 0-dim device tensor); a forward
+        with both at 0 sets it back to None."""
         super().__init__()
         self.cfg = cfg
+        self.z_loss, self.label_smoothing, self.last_ce = z_loss, label_smoothing, None
         self.wte = nn.Parameter(torch.empty(cfg.padded_vocab, cfg.n_embd))
         self.wpe = nn.Parameter(torch.empty(cfg.n_positions, cfg.n_embd))
         self.h = nn.ModuleList([Block(cfg) for _ in range(cfg.n_layer)])
@@ -134,6 +140,12 @@ class GPT2(nn.Module):
             prev_bias = blk.mlp.c_proj.bias
         x = self.ln_f(x, grad_sum_into=prev_bias)
         if targets is not None:
+            if self.z_loss or self.label_smoothing:
+                loss, self.last_ce = ops.lm_head_cross_entropy(x, self.wte, targets, self.cfg.vocab_size,
+                                                               label_smoothing=self.label_smoothing or 0.0,
+                                                               z_loss=self.z_loss or 0.0, return_ce=True)
+                return loss
+            self.last_ce = None  # never an earlier forward's value once the terms are switched off
             return ops.lm_head_cross_entropy(x, self.wte, targets, self.cfg.vocab_size)
         logits = ops.linear(x, self.wte)
         return logits[..., : self.cfg.vocab_size]

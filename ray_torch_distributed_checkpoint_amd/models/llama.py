@@ -101,9 +101,15 @@ class TransformerBlock(nn.Module):
 
 
 class Llama(nn.Module):
-    def __init__(self, cfg: LlamaConfig, device=None):
+    def __init__(self, cfg: LlamaConfig, device=None, z_loss: float = 0.0, label_smoothing: float = 0.0):
+        """z_loss / label_smoothing: the two optional terms of ops.lm_head_cross_entropy, plain
+        attributes (not in the config, not in the state_dict; settable later).  With either one
+        non-zero `forward(idx, targets)` still returns the optimised loss and leaves the mean
+        plain cross-entropy of that forward in `self.last_ce` (a 0-dim device tensor); a forward
+        with both at 0 sets it back to None."""
         super().__init__()
         self.cfg = cfg
+        self.z_loss, self.label_smoothing, self.last_ce = z_loss, label_smoothing, None
         factory = {"device": device} if device is not None else {}
         with torch.device(device) if device is not None else _nullctx():
             self.tok_embeddings = nn.Parameter(torch.empty(cfg.padded_vocab, cfg.dim))
@@ -137,6 +143,12 @@ class Llama(nn.Module):
             x = blk(x, docs)
         x = self.norm(x)
         if targets is not None:
+            if self.z_loss or self.label_smoothing:
+                loss, self.last_ce = ops.lm_head_cross_entropy(x, self.output, targets, self.cfg.vocab_size,
+                                                               label_smoothing=self.label_smoothing or 0.0,
+                                                               z_loss=self.z_loss or 0.0, return_ce=True)
+                return loss
+            self.last_ce = None  # never an earlier forward's value once the terms are switched off
             return ops.lm_head_cross_entropy(x, self.output, targets, self.cfg.vocab_size)
         return ops.linear(x, self.output)[..., : self.cfg.vocab_size]
 

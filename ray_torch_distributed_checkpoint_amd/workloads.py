@@ -46,7 +46,7 @@ from . import ops
 from . import train
 from .checkpoint import dcp
 from .checkpoint.state_dict import get_state_dict, set_state_dict
-from .ops.xent import IGNORE_INDEX
+from .ops.xent import IGNORE_INDEX, check_loss_coeffs
 from .optim import FusedAdamW, FusedSGD, GradAccumulator
 from .parallel.sampler import DistributedSampler
 from .utils.profiling import phase
@@ -89,6 +89,11 @@ class WorkloadConfig:
     # host-scalar ones at ResNet-18 size, and a step ends with one more tiny launch
     # (profiles/adamw_capturable_ab.md).
     opt_capturable: bool = False
+    # optional terms of the fused cross-entropy kernels (ops/xent.py), every workload: the auxiliary
+    # z-loss z * logsumexp^2 per row and label smoothing in [0, 1) (None / 0: off).  With either on
+    # the report rows also carry ce_loss / ce_losses, the plain cross-entropy of the same steps.
+    z_loss: Optional[float] = None
+    label_smoothing: Optional[float] = None
 
     @classmethod
     def from_dict(cls, d: dict) -> "WorkloadConfig":
@@ -282,6 +287,8 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     sched_kw = {} if sched is None else {"lr_schedule": sched}
     if cfg.opt_capturable and torch.device(device).type == "cuda":
         sched_kw["capturable"] = True
+    ls, zl = check_loss_coeffs(cfg.label_smoothing, cfg.z_loss)
+    aux = bool(ls or zl)  # the loss function then returns (loss, plain cross-entropy)
     torch.manual_seed(cfg.seed)
     name = cfg.model
     if name.startswith("resnet18"):
@@ -291,6 +298,10 @@ def build(cfg: WorkloadConfig, device) -> Workload:
         model = ResNet18(num_classes=cfg.num_classes).to(device)
         opt = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=5e-5, max_grad_norm=clip, **sched_kw)
         data = SyntheticImages(cfg.dataset_size, S, cfg.num_classes, device, seed=cfg.seed)
+        if aux:
+            return Workload(model, opt, data, B, S, 0, model.flops_per_sample(S),
+                            lambda net, x, y: ops.cross_entropy(net(x), y, label_smoothing=ls, z_loss=zl,
+                                                                return_ce=True))
         return Workload(model, opt, data, B, S, 0, model.flops_per_sample(S),
                         lambda net, x, y: ops.cross_entropy(net(x), y))
     if name.startswith("llama"):
@@ -311,6 +322,14 @@ def build(cfg: WorkloadConfig, device) -> Workload:
                      state_dtype=getattr(torch, _OPT_STATE_DTYPES[cfg.opt_state_dtype]), rounding_seed=cfg.seed, **sched_kw)
     data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed, doc_len=cfg.doc_len or None)
     # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle)
+    if aux:
+        model.z_loss, model.label_smoothing = zl, ls  # forward() leaves the plain cross-entropy in last_ce
+
+        def lm_loss(net, x, y, docs=None):
+            loss = net(x, y) if docs is None else net(x, y, docs)
+            return loss, _unwrap(net).last_ce
+
+        return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S, lm_loss)
     return Workload(model, opt, data, B, S, S, model.flops_per_token(S) * S,
                     lambda net, x, y, docs=None: net(x, y) if docs is None else net(x, y, docs))
 
@@ -478,6 +497,8 @@ def train_loop_per_worker(config: dict):
     clipping = bool(cfg.max_grad_norm)
     scheduled = getattr(opt, "lr_schedule", None) is not None
     norms = []  # per-step pre-clip gradient norms (device scalars, read with the losses)
+    aux = bool(cfg.z_loss or cfg.label_smoothing)  # the loss function returns (loss, plain cross-entropy)
+    ces = []  # aux: per-step plain cross-entropy (device scalars, read with the losses)
     t_last, n_last = time.perf_counter(), 0
     k = int(cfg.grad_accum_steps or 1)
     if k < 1:
@@ -490,26 +511,35 @@ def train_loop_per_worker(config: dict):
             batch = stream.next()  # (x, y), or (x, y, docs) for packed sequences (doc_len)
             with phase("fwd"):
                 loss = wl.loss_fn(net, *batch)
+                if aux:
+                    loss, ce = loss
             with phase("bwd"):
                 loss.backward()
             loss = loss.detach()
         else:
-            micro = []
+            micro, micro_ce = [], []
             for i in range(k):
                 batch = stream.next()
                 with acc.micro_step(i):
                     with phase("fwd"):
                         li = wl.loss_fn(net, *batch)
+                        if aux:
+                            li, ci = li
+                            micro_ce.append(ci)
                     with phase("bwd"):
                         li.backward()
                 micro.append(li.detach())
             loss = torch.stack(micro).float().mean()  # (on the device: still one host sync per report)
+            if aux:
+                ce = torch.stack(micro_ce).float().mean()
         with phase("opt"):
             opt.step()
             opt.zero_grad(set_to_none=True)
         losses.append(loss)
         if clipping:
             norms.append(opt.grad_norm.clone())
+        if aux:
+            ces.append(ce)
         n_last += 1
         done = step + 1
         do_ckpt = bool(every) and (done % every == 0 or done == cfg.steps)
@@ -518,8 +548,11 @@ def train_loop_per_worker(config: dict):
         vals = torch.stack(losses).float()
         if clipping:
             vals = torch.cat([vals, torch.stack(norms)])
+        if aux:
+            vals = torch.cat([vals, torch.stack(ces).float()])
         vals = vals.tolist()  # the one host sync per report
-        vals, gnorms = vals[:len(losses)], vals[len(losses):]
+        n = len(losses)
+        vals, gnorms, cvals = vals[:n], vals[n:n + len(norms)], vals[n + len(norms):]
         dt = time.perf_counter() - t_last
         metrics = {"step": done, "loss": vals[-1], "losses": vals, "epoch": stream.epoch,
                    "samples_per_s": samples_per_s(n_last, k, wl.batch, world, dt)}
@@ -529,7 +562,9 @@ def train_loop_per_worker(config: dict):
             metrics["grad_norm"], metrics["grad_norms"] = gnorms[-1], gnorms
         if scheduled:
             metrics["lr"] = opt.get_last_lr()[0]  # the last step's, group 0
-        losses, norms, n_last = [], [], 0
+        if aux:
+            metrics["ce_loss"], metrics["ce_losses"] = cvals[-1], cvals
+        losses, norms, ces, n_last = [], [], [], 0
         ck = None
         if do_ckpt:
             with phase("ckpt"):
@@ -571,7 +606,8 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
                    doc_len: int | None = None, opt_state_dtype: str = "fp32", grad_accum_steps: int = 1,
                    lr_schedule: str = "constant", warmup_steps: int = 0, min_lr_ratio: float = 0.0,
-                   lr_total_steps: int | None = None, opt_capturable: bool = False):
+                   lr_total_steps: int | None = None, opt_capturable: bool = False, z_loss: float | None = None,
+                   label_smoothing: float | None = None):
     """`train_fashion_mnist`'s counterpart for the bf16 workloads (R/my_ray_module.py:216-251).
     zero_stage -1: `default_zero_stage(model, num_workers)`.  max_grad_norm: clip the global
     gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
@@ -590,11 +626,19 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     `steps` needs the original `lr_total_steps` given explicitly.  The default (constant, no warmup)
     attaches nothing: rows, checkpoints and bits are unchanged.  opt_capturable (GPU): the fused
     optimizer reads lr, the bias corrections and the step number from device tables
-    (`capturable=True`): the same bits as the host path, and a step that may be captured."""
+    (`capturable=True`): the same bits as the host path, and a step that may be captured.
+    z_loss / label_smoothing (every workload; None / 0: off): the auxiliary z-loss
+    z * logsumexp(logits)^2 per row and label smoothing in [0, 1), both computed inside the fused
+    cross-entropy kernels (ops/xent.py).  `loss` / `losses` stay the optimised objective; with either
+    term on the rows also carry `ce_loss` / `ce_losses`, the plain cross-entropy of the same steps
+    (the mean over the micro-batches under grad_accum_steps).  Nothing new is checkpointed: an
+    exact resume with the same two arguments is bit-identical; with both off rows, checkpoints and
+    bits are unchanged."""
     if int(grad_accum_steps) < 1:
         raise ValueError(f"grad_accum_steps must be >= 1, got {grad_accum_steps}")
     if opt_state_dtype not in _OPT_STATE_DTYPES:
         raise ValueError(f"opt_state_dtype must be one of {sorted(_OPT_STATE_DTYPES)}, got {opt_state_dtype!r}")
+    check_loss_coeffs(label_smoothing, z_loss)  # (argument errors here, not in the workers)
     if zero_stage < 0:
         zero_stage = default_zero_stage(model, num_workers)
     cfg = WorkloadConfig(model=model, steps=steps, batch_size_per_worker=batch_size_per_worker, seq_len=seq_len,
@@ -604,7 +648,8 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                          opt_state_dtype=opt_state_dtype, grad_accum_steps=int(grad_accum_steps),
                          lr_schedule=lr_schedule, warmup_steps=int(warmup_steps or 0),
                          min_lr_ratio=float(min_lr_ratio or 0.0), lr_total_steps=lr_total_steps or None,
-                         opt_capturable=bool(opt_capturable))
+                         opt_capturable=bool(opt_capturable), z_loss=float(z_loss) if z_loss else None,
+                         label_smoothing=float(label_smoothing) if label_smoothing else None)
     make_schedule(cfg)  # (argument errors here, not in the workers)
     run_config = train.RunConfig(
         name=name, storage_path=checkpoint_storage_path, verbose=verbose,
@@ -655,6 +700,11 @@ def main(argv=None):
     ap.add_argument("--opt-capturable", action="store_true",
                     help="GPU: fused optimizer with device-resident step count, lr and bias-correction tables "
                          "(capturable=True; same bits as the default host path)")
+    ap.add_argument("--z-loss", type=float, default=None,
+                    help="auxiliary z-loss z * logsumexp(logits)^2 per row, inside the fused cross-entropy kernels "
+                         "(default: off); rows then also carry the plain ce_loss")
+    ap.add_argument("--label-smoothing", type=float, default=None,
+                    help="label smoothing of the training cross-entropy, in [0, 1) (default: off)")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
     use_gpu = torch.cuda.is_available() and not a.cpu
@@ -663,7 +713,8 @@ def main(argv=None):
                          zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len,
                          opt_state_dtype=a.opt_state_dtype, grad_accum_steps=a.grad_accum_steps,
                          lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, min_lr_ratio=a.min_lr_ratio,
-                         lr_total_steps=a.lr_total_steps, opt_capturable=a.opt_capturable)
+                         lr_total_steps=a.lr_total_steps, opt_capturable=a.opt_capturable, z_loss=a.z_loss,
+                         label_smoothing=a.label_smoothing)
     print(res)
 
 

@@ -63,6 +63,18 @@ def parse(path):
     return stats
 
 
+def plain_name(d):
+    """Every trailing `false` template argument dropped (kernel<A, false, false> and the parent's
+    kernel<A, false> are both kernel<A>), and with it the empty argument struct that such a switch
+    adds to the parameter list (`, rtdc::XentAux<false>`): the name the kernel had before."""
+    d = re.sub(r", rtdc::XentAux<false>\)", ")", d)
+    while True:
+        n = re.sub(r", false>", ">", d)
+        if n == d:
+            return d
+        d = n
+
+
 def short(d):
     d = re.sub(r"^void rtdc::fa::", "", d)
     return re.sub(r"\(rtdc::fa::Args\)$", "", d)
@@ -77,7 +89,7 @@ def main(argv):
     # kernel<DH, NS> is the new kernel<DH, NS, false>) names the same kernel
     for i, t in enumerate(tabs):
         d = demangle(sorted(t))
-        tabs[i] = {re.sub(r", false>", ">", d[k]): v for k, v in t.items()}
+        tabs[i] = {plain_name(d[k]): v for k, v in t.items()}
     names = sorted(set().union(*tabs))
     dm = {n: n for n in names}
     cols = [k for k, _ in FIELDS] + ["insts"]

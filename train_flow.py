@@ -54,6 +54,11 @@ class RayTorchTrain(FlowSpec):
     max_grad_norm = Parameter("max_grad_norm", default=0.0,
                               help="bf16 workloads: clip the global gradient norm inside the fused optimizer step "
                                    "(0: off)")
+    z_loss = Parameter("z_loss", default=0.0,
+                       help="auxiliary z-loss z * logsumexp(logits)^2 per row, inside the fused cross-entropy "
+                            "kernels (0: off); rows then also carry the plain ce_loss")
+    label_smoothing = Parameter("label_smoothing", default=0.0,
+                                help="label smoothing of the training cross-entropy, in [0, 1) (0: off)")
     doc_len = Parameter("doc_len", default=0,
                         help="LM workloads: packed sequences of synthetic documents of this mean length, attention "
                              "and RoPE positions per document (0: off)")
@@ -120,7 +125,8 @@ class RayTorchTrain(FlowSpec):
             print("Training from newly initialized")
 
         if self.model == "mlp":
-            self.result = train_fashion_mnist(**args)
+            self.result = train_fashion_mnist(**args, label_smoothing=float(self.label_smoothing),
+                                              z_loss=float(self.z_loss))
         else:
             mode = "exact" if self.resume_mode == "exact" else "weights"
             self.result = train_workload(
@@ -135,7 +141,8 @@ class RayTorchTrain(FlowSpec):
                 opt_state_dtype=str(self.opt_state_dtype), grad_accum_steps=int(self.grad_accum_steps),
                 lr_schedule=str(self.lr_schedule), warmup_steps=int(self.warmup_steps),
                 min_lr_ratio=float(self.min_lr_ratio), lr_total_steps=int(self.lr_total_steps) or None,
-                opt_capturable=bool(int(self.opt_capturable)))
+                opt_capturable=bool(int(self.opt_capturable)), z_loss=float(self.z_loss) or None,
+                label_smoothing=float(self.label_smoothing) or None)
         self.next(self.join)
 
     @step

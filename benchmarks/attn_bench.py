@@ -3,6 +3,7 @@ Llama-3-8B shapes; random operands, one process, interleaved repetitions.
 
     python benchmarks/attn_bench.py [--reps 20]
     python benchmarks/attn_bench.py --doc-len T T/8 100 [--only gpt2] [--rounds 7]
+    python benchmarks/attn_bench.py --variants default 1,1,1 [--rounds 1]
 
 --doc-len L times the document-masked kernels (packed sequences: equal documents of length L, the
 last one shorter when L does not divide T) next to the plain causal kernels on the same shape and
@@ -106,8 +107,49 @@ def doc_mask_ab(args):
             print(json.dumps(res), flush=True)
 
 
+def variants_ab(args):
+    """The forward and the backward kernel calls, timed apart, at each rows-per-wave setting: one
+    JSON line per (shape, setting) with the time of every round.  Two builds are compared by running
+    this in alternating processes (RTDC_EXT_SO), one round each."""
+    from ray_torch_distributed_checkpoint_amd.ops.attention import _dkdv_head_split
+
+    ext = gpu_ext()
+    knobs = ("RTDC_FA_FWD", "RTDC_FA_DQ", "RTDC_FA_DKDV")
+    for name, B, T, H, Hkv, Dh in SHAPES[:2]:
+        if args.only and name != args.only:
+            continue
+        W, scale = (H + 2 * Hkv) * Dh, Dh ** -0.5
+        q_ = (torch.randn(B, T, W, device="cuda") * 0.5).bfloat16()
+        o_ = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device="cuda")
+        lse = torch.empty((B * H, T), dtype=torch.float32, device="cuda")
+        dy = torch.randn_like(o_)
+        dqkv = torch.empty_like(q_)
+        delta = torch.empty_like(lse)
+        qs = _dkdv_head_split(B, T, H, Hkv, q_.device)
+        part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device="cuda") if qs > 1 else None
+        arms = {"fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale),
+                "bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs)}
+        for spec in args.variants:
+            for k, v in zip(knobs, spec.split(",") if spec != "default" else (None,) * 3):
+                os.environ.pop(k, None)
+                if v is not None:
+                    os.environ[k] = v
+            arms["fwd"]()  # the backward reads this setting's o / lse
+            # repetitions so that every timed window is at least --window-ms long (as --doc-len)
+            reps = {k: max(args.reps, int(1.25 * args.window_ms * 1e-3 / timeit(fn, 200)) + 1) for k, fn in arms.items()}
+            t = {k: [round(timeit(fn, reps[k]) * 1e6, 2) for _ in range(args.rounds)] for k, fn in arms.items()}
+            print(json.dumps({"shape": name, "B": B, "T": T, "H": H, "Hkv": Hkv, "Dh": Dh, "variant": spec,
+                              "dkdv_head_split": qs, "reps": reps, "window_ms": args.window_ms,
+                              "fwd_us": t["fwd"], "bwd_us": t["bwd"]}), flush=True)
+        for k in knobs:
+            os.environ.pop(k, None)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--variants", nargs="+", default=None, metavar="F,Q,K",
+                    help="time the forward and backward kernel calls at each RTDC_FA_FWD,RTDC_FA_DQ,RTDC_FA_DKDV "
+                         "setting (`default` = all unset), --rounds windows of --window-ms each")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--only", default=None)
     ap.add_argument("--doc-len", nargs="+", default=None, metavar="L",
@@ -123,6 +165,8 @@ def main():
     warm_up_clocks()
     if args.doc_len:
         return doc_mask_ab(args)
+    if args.variants:
+        return variants_ab(args)
     for name, B, T, H, Hkv, Dh in SHAPES:
         if args.only and name != args.only:
             continue

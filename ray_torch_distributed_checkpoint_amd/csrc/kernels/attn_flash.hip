@@ -11,18 +11,23 @@
 // / Q / K tiles with the transposing LDS read ds_read_b64_tr_b16 (4 consecutive rows x 16
 // columns per 16-lane group).
 //
-//   fwd     : block = 64 query rows (4 waves x 16) of one (b, h); K/V tiles of 64 keys
-//             streamed through LDS by global_load_lds; online softmax in the log2 domain;
-//             writes O and the row log-sum-exp.
-//   bwd_dkdv: block = 64 keys (4 waves x 16) of one (b, kv-head); loops over the query
-//             blocks at or after the diagonal and over the q-heads of the GQA group; keeps
-//             dK/dV in registers - no atomics.
-//   bwd_dq  : block = 64 query rows; loops over key blocks up to the diagonal.  Recomputing
-//             P here instead of accumulating dQ with float atomics keeps the backward
-//             bitwise reproducible (MI355X_MICROARCH.md §Global float atomics).
-//   delta   : D[b,h,t] = sum_d dO * O (the softmax-backward row term), computed by bwd_dq
-//             in its prologue (bwd_dq runs first).
-// Requires T % 64 == 0 and Dh in {64, 128}.
+// A wave owns G in {1, 2} 16-row groups, so a block (4 waves) covers 64 G query rows or keys; tiles
+// stay 64 rows.  The forward and dQ are one kernel each, a template over <DH, NS, DOC, G>; dK/dV is
+// still a pair, bwd_dkdv_kernel (G = 1) and bwd_dkdv2_kernel (G = 2), see the note above them.
+//   fwd_kernel     : block = 64 G query rows of one (b, h); K/V tiles of 64 keys streamed
+//                    through LDS by global_load_lds; online softmax in the log2 domain; writes O
+//                    and the row log-sum-exp.
+//   bwd_dkdv_kernel, bwd_dkdv2_kernel: block = 64 G keys of one (b, kv-head); loops over the
+//                    query tiles at or after the diagonal and over the q-heads of the GQA group;
+//                    keeps dK/dV in registers - no atomics.  (dkdv_reduce_kernel sums the fp32
+//                    partials of a GQA head split.)
+//   bwd_dq_kernel  : block = 64 G query rows; loops over key tiles up to the diagonal.
+//                    Recomputing P here instead of accumulating dQ with float atomics keeps the
+//                    backward bitwise reproducible (MI355X_MICROARCH.md §Global float atomics).
+//   delta          : D[b,h,t] = sum_d dO * O (the softmax-backward row term), computed by
+//                    bwd_dq_kernel in its prologue (it runs first).
+// Requires T % 64 == 0 and Dh in {64, 128}; G = 2 needs T % 128 == 0.  Which G runs: the
+// launchers at the end of the file (RTDC_FA_FWD / RTDC_FA_DQ / RTDC_FA_DKDV).
 //
 // DOC = true (packed sequences, rtdc_flash_fwd_doc / rtdc_flash_bwd_doc): row q attends to the
 // keys doc_start[q] <= key <= q of its own document.  The query-row kernels (fwd, dQ) start the
@@ -43,7 +48,7 @@
 // drain the DMA queue).  The tile of step j+NS-1 is issued at the top of step j into the slot
 // that step j-1 read, which every wave has left: its reads completed (lgkmcnt(0)) before the
 // barrier that closed step j-1.  All LDS is one __shared__ array.
-// NS (ring slots) is 2 at every launch (see the note above rtdc_flash_fwd): LDS per block grows
+// NS (ring slots) is 2 at every launch (see the note above FA_LAUNCH): LDS per block grows
 // with NS and sets how many blocks share a CU, so deeper rings trade occupancy for DMA depth.
 #include "common.h"
 
@@ -242,15 +247,48 @@ __device__ __forceinline__ f32x4 mfma(const bf16x8& a, const bf16x8& b, const f3
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+// The K/V ring of the query-row kernels (fwd, dQ): NS K slots, then NS V slots, of TILE bytes each
+// in the kernel's `smem`; key tile kb of the loop kb_lo .. nkb-1 lives in slot (kb - kb_lo) % NS
+// (indexed from the loop start).  Prologue, issue-next and the end of a step (counted wait +
+// barrier) stay written out in the loops.  Both were tried as shared code: with prologue and
+// issue-next as members of a ring struct fwd_kernel<128, 2, false, 2> measured 57.80 against 57.51
+// us (profiles/attn_merge_ab.md), and with the end of a step in a function the one-group loops
+// lost their specialised copies (fwd_kernel<64, 2, false, 1>: 932 instead of 1252 instructions).
+#define KT(s) (smem + (s) * TILE)
+#define VT(s) (smem + (NS + (s)) * TILE)
+
+// bf16 store of a wave's fragment rows times mul: the lane's row, columns 4g..4g+3 of each
+// 16-column block d (the layout wave_colsum16 sums)
+template <int DT>
+__device__ __forceinline__ void store_rows_bf16(bf16_t* row, const f32x4 (&v)[DT], float mul, int g) {
+#pragma unroll
+  for (int d = 0; d < DT; ++d)
+    *(uint2*)(row + 16 * d + 4 * g) =
+        make_uint2(pack_bf2(v[d][0] * mul, v[d][1] * mul), pack_bf2(v[d][2] * mul, v[d][3] * mul));
+}
+
+// The forward and dQ own G 16-row groups per wave (G = 1: 64-row block, G = 2: 128-row block).
+// With two groups every fragment read from LDS - row reads and transposed reads alike - feeds the
+// MFMAs of both groups, halving LDS bytes per MFMA (the Dh = 64 dK/dV loop with one group is
+// LDS-bound: per step and wave 24 ds_read_b128 + 32 ds_read_b64_tr_b16 = 160 LDS-array cycles for
+// 32 MFMAs, 12 waves per CU; MI355X_MICROARCH.md §LDS); one group needs half the registers.  Both
+// are live (see the launchers).  Where the two really differ the difference sits under a test of
+// G with its reason.  In particular the one-group loops keep their own wave-uniform conditions,
+// `G == 1 ||` in front of the tile-skip guard and diag as an equality with the block index:
+// given these hipcc emits the specialised copies of the loop body (fwd_kernel<64, 2, false, 1>:
+// 54 MFMAs = 3 x 18); given the two-group range tests at G = 1 it emits one generic copy (762
+// instead of 1252 instructions) - and fwd_kernel<64, 2, false, 1> is GPT-2's production forward.
+
 // ------------------------------------------------------------------------------ forward
-template <int DH, int NS, bool DOC = false>
+template <int DH, int NS, bool DOC, int G>
 __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
-  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
+  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, BLK = 64 * G;
+  constexpr int TILE = 64 * DH * 2, PER = DH / 16;  // PER: DMA instructions per wave and tile
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4;
-  const int nqb = a.T / BQ;
+  const int nqb = a.T / BLK;
   int bx, bh;
   grid_pos(a, bx, bh);
   const int qb = nqb - 1 - bx;  // heaviest (longest causal prefix) blocks first
@@ -259,201 +297,43 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
   const int C = a.H * DH, W = C + 2 * a.Hkv * DH;
   const bf16_t* base = a.qkv + (long long)b * a.T * W;
   const int qcol = h * DH, kcol = C + kvh * DH, vcol = C + a.Hkv * DH + kvh * DH;
-  const int q0w = qb * BQ + wave * 16;
-  const int myq = q0w + (lane & 15);
+  const int q0w = qb * BLK + wave * (16 * G);  // this wave: rows [q0w, q0w + 16 G)
+  int myq[G];
+#pragma unroll
+  for (int qg = 0; qg < G; ++qg) myq[qg] = q0w + 16 * qg + (lane & 15);
   const float c = a.scale * LOG2E;
   uint32_t troff[DH / 16];
   tr_lane_offsets<DH>(troff, lane);
-  const int nkb = qb + 1;
+  const int nkb = (qb + 1) * G;
   // DOC: the first key tile any row of the block attends to (start is non-decreasing, so the
   // block's first row has the minimum) - a scalar load, ahead of the prologue DMAs
   int kb_lo = 0;
-  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ]) / BKV;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BLK]) / BKV;
 
-#define KT(s) (smem + (s) * TILE)
-#define VT(s) (smem + (NS + (s)) * TILE)
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
     if (kb_lo + s < nkb) {
       stage<DH>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
       stage<DH>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
     }
-  bf16x8 qf[KS];
+  bf16x8 qf[G][KS];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = gload8(base + (long long)myq * W + qcol + ks * 32 + g * 8);
-  int mylo = 0;  // DOC: first key of this row's document
-  if constexpr (DOC) mylo = a.doc_start[(long long)b * a.T + myq];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) settle(qf[ks]);
-  if constexpr (DOC) settle(mylo);
-  // DOC: tiles that begin before the document of the wave's last row need the low mask
-  int wlo = 0;
-  if constexpr (DOC) wlo = __builtin_amdgcn_readlane(mylo, 15);
-  step_barrier();
-
-  f32x4 o[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // row sums of P on the matrix core: an all-ones A operand makes every row of the P.V-shaped
-  // product the sum over the keys, so lacc[*] = l for the lane's query row (no VALU adds, no
-  // cross-lane reduction at the end; the sum is over the same bf16 P the numerator uses)
-  f32x4 lacc = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (short)0x3F80;
-  float m = DOC ? M_INIT_DOC : -INFINITY;
-
-  for (int kb = kb_lo; kb < nkb; ++kb) {
-    const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
-    if (kb + NS - 1 < nkb) {
-      const int nx = (kb - kb_lo + NS - 1) % NS;
-      stage<DH>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
-      stage<DH>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
-    }
-    const char* kt = KT(cur);
-    const uint32_t vbase = lds_addr(VT(cur));
-    f32x4 s[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) s[t] = mfma(frag_rows<DH>(kt, 16 * t, ks, lane), qf[ks], s[t]);
-    }
-    // causal mask on the diagonal block, running max of the raw scores (c > 0: scaling into the
-    // log2 domain commutes with max, so it folds into one FMA per probability)
-    float mx = -INFINITY;
-    // DOC: the tile also needs a mask when it begins before the document of the wave's last row
-    // (wave-uniform, like diag); keys before the row's document are masked like the keys after
-    // the row - both by ONE unsigned range test, key - mylo <= myq - mylo, so a DOC tile costs
-    // the compare the causal mask costs (the loop is VALU-issue bound)
-    const bool diag = (kb == qb) || (DOC && kb * BKV < wlo);
-    const int koff = kb * BKV + 4 * g - mylo;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = s[t][r];
-        if (diag) {
-          if constexpr (DOC) {
-            if ((unsigned)(koff + 16 * t + r) > (unsigned)(myq - mylo)) v = -INFINITY;
-          } else {
-            const int key = kb * BKV + 16 * t + 4 * g + r;
-            if (key > myq) v = -INFINITY;
-          }
-        }
-        s[t][r] = v;
-        mx = fmaxf(mx, v);
-      }
-    mx = max_rows4(mx);
-    // lazy rescale: the running max moves (and O, l are rescaled) only when some row of the
-    // wave would otherwise see probabilities above 2^8 - after the first key blocks the max
-    // rarely grows that much, so the 4*DT+4 multiplies and the exp are skipped (wave-uniform)
-    if (__any(mx * c > m + 8.f)) {
-      const float mn = fmaxf(m, mx * c);
-      const float alpha = fexp2(m - mn);
-      m = mn;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lacc[r] *= alpha;
-#pragma unroll
-      for (int d = 0; d < DT; ++d)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[d][r] *= alpha;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s[t][r] = fexp2(fmaf(s[t][r], c, -m));
-    const bf16x8 p0 = pack_pair(s[0], s[1]), p1 = pack_pair(s[2], s[3]);
-    lacc = mfma(ones, p0, lacc);
-    lacc = mfma(ones, p1, lacc);
-#pragma unroll
-    for (int d0 = 0; d0 < DT; d0 += DB) {
-      TrPair vq[DB][2];
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        const uint32_t la = vbase + troff[d0 + d];
-        vq[d][0] = frag_cols_at<DH, 0>(la);
-        vq[d][1] = frag_cols_at<DH, 32>(la);
-      }
-      lgkm_wait0();
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        o[d0 + d] = mfma(tr_use(vq[d][0]), p0, o[d0 + d]);
-        o[d0 + d] = mfma(tr_use(vq[d][1]), p1, o[d0 + d]);
-      }
-    }
-    if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
-    step_barrier();
-  }
-#undef KT
-#undef VT
-  const float l = lacc[0];
-  const float inv = 1.f / l;
-  bf16_t* orow = a.out + ((long long)b * a.T + myq) * C + h * DH;
-#pragma unroll
-  for (int d = 0; d < DT; ++d) {
-    const uint2 v = make_uint2(pack_bf2(o[d][0] * inv, o[d][1] * inv), pack_bf2(o[d][2] * inv, o[d][3] * inv));
-    *(uint2*)(orow + 16 * d + 4 * g) = v;
-  }
-  if (g == 0) a.lse[(long long)bh * a.T + myq] = m + log2f(l);
-}
-
-// Forward, 32 query rows per wave (block = 128 rows): every K fragment read from LDS feeds
-// two S MFMAs and every V fragment two P.V MFMAs, halving LDS bytes per FLOP.  Same
-// accumulator-as-operand layout and the same DMA ring as fwd_kernel.
-template <int DH, int NS, bool DOC = false>
-__global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
-  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, QG = 2, BQ2 = 128, PER = DH / 16;
-  __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = lane >> 4;
-  const int nqb = a.T / BQ2;
-  int bx, bh;
-  grid_pos(a, bx, bh);
-  const int qb = nqb - 1 - bx;  // heaviest (longest causal prefix) blocks first
-  const int b = bh / a.H, h = bh % a.H;
-  const int grp = a.H / a.Hkv, kvh = h / grp;
-  const int C = a.H * DH, W = C + 2 * a.Hkv * DH;
-  const bf16_t* base = a.qkv + (long long)b * a.T * W;
-  const int qcol = h * DH, kcol = C + kvh * DH, vcol = C + a.Hkv * DH + kvh * DH;
-  const int q0w = qb * BQ2 + wave * 32;  // this wave: rows [q0w, q0w + 32)
-  int myq[QG];
-#pragma unroll
-  for (int qg = 0; qg < QG; ++qg) myq[qg] = q0w + 16 * qg + (lane & 15);
-  const float c = a.scale * LOG2E;
-  uint32_t troff[DH / 16];
-  tr_lane_offsets<DH>(troff, lane);
-  const int nkb = (qb + 1) * (BQ2 / BKV);
-  // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
-  int kb_lo = 0;
-  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ2]) / BKV;
-
-#define KT(s) (smem + (s) * TILE)
-#define VT(s) (smem + (NS + (s)) * TILE)
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (kb_lo + s < nkb) {
-      stage<DH>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
-      stage<DH>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
-    }
-  bf16x8 qf[QG][KS];
-#pragma unroll
-  for (int qg = 0; qg < QG; ++qg)
+  for (int qg = 0; qg < G; ++qg)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[qg][ks] = gload8(base + (long long)myq[qg] * W + qcol + ks * 32 + g * 8);
-  int mylo[QG], wlo[QG];  // DOC: first key of the row's document; that of each group's last row
+  int mylo[G], wlo[G];  // DOC: first key of the row's document; that of each group's last row
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
+  for (int qg = 0; qg < G; ++qg) {
     mylo[qg] = 0;
     if constexpr (DOC) mylo[qg] = a.doc_start[(long long)b * a.T + myq[qg]];
   }
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg)
+  for (int qg = 0; qg < G; ++qg)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) settle(qf[qg][ks]);
+  // DOC: tiles that begin before the document of a group's last row need the low mask
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
+  for (int qg = 0; qg < G; ++qg) {
     wlo[qg] = 0;
     if constexpr (DOC) {
       settle(mylo[qg]);
@@ -462,15 +342,24 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
   }
   step_barrier();
 
-  f32x4 o[QG][DT];
-  float m[QG], l[QG];
+  f32x4 o[G][DT];
+  float m[G], l[G];
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
+  for (int qg = 0; qg < G; ++qg) {
     m[qg] = DOC ? M_INIT_DOC : -INFINITY;
     l[qg] = 0.f;
 #pragma unroll
     for (int d = 0; d < DT; ++d) o[qg][d] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+  // G == 1 takes the row sums of P on the matrix core: an all-ones A operand makes every row of
+  // the P.V-shaped product the sum over the keys, so lacc[*] = l for the lane's query row (no
+  // VALU adds, no cross-lane reduction at the end; the sum is over the same bf16 P the numerator
+  // uses).  G == 2 adds the fp32 P on the VALU (l[]) and reduces over the 4 lane rows at the end.
+  // The two sums differ in bits (bf16 P against fp32 P), so each group count keeps its own.
+  f32x4 lacc = f32x4{0.f, 0.f, 0.f, 0.f};
+  bf16x8 ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = (short)0x3F80;
 
   for (int kb = kb_lo; kb < nkb; ++kb) {
     const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
@@ -479,30 +368,37 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
       stage<DH>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
       stage<DH>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
     }
-    // keys of this tile all after this wave's last row: nothing to add (barriers still run)
-    if (kb * BKV <= q0w + 31) {
+    // G == 2: keys of this tile all after this wave's last row - nothing to add (barriers still
+    // run).  G == 1: the loop ends with the block's own tile, which every wave meets
+    if (G == 1 || kb * BKV <= q0w + 16 * G - 1) {
       const char* kt = KT(cur);
       const uint32_t vbase = lds_addr(VT(cur));
-      f32x4 sc[QG][4];
+      f32x4 sc[G][4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
 #pragma unroll
-        for (int qg = 0; qg < QG; ++qg) sc[qg][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int qg = 0; qg < G; ++qg) sc[qg][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const bf16x8 kf = frag_rows<DH>(kt, 16 * t, ks, lane);
 #pragma unroll
-          for (int qg = 0; qg < QG; ++qg) sc[qg][t] = mfma(kf, qf[qg][ks], sc[qg][t]);
+          for (int qg = 0; qg < G; ++qg) sc[qg][t] = mfma(kf, qf[qg][ks], sc[qg][t]);
         }
       }
-      const bool diag = (kb * BKV + BKV - 1 > q0w);
-      bf16x8 pp[QG][2];
+      // causal mask where the tile meets the wave's rows (wave-uniform).  G == 1: that is the
+      // block's last tile, as an equality (keeps the specialised loop copies, see above)
+      const bool diag = G == 1 ? (kb == qb) : (kb * BKV + BKV - 1 > q0w);
+      bf16x8 pp[G][2];
 #pragma unroll
-      for (int qg = 0; qg < QG; ++qg) {
-        // DOC: one unsigned range test masks the keys after the row and those before its
-        // document, on the tiles that meet either edge (wave-uniform; see fwd_kernel)
+      for (int qg = 0; qg < G; ++qg) {
+        // DOC: the tile also needs a mask when it begins before the document of the group's last
+        // row (wave-uniform, like diag); keys before the row's document are masked like the keys
+        // after the row - both by ONE unsigned range test, key - mylo <= myq - mylo, so a DOC tile
+        // costs the compare the causal mask costs (the loop is VALU-issue bound)
         const bool edge = diag || (DOC && kb * BKV < wlo[qg]);
         const int koff = kb * BKV + 4 * g - mylo[qg];
+        // running max of the raw scores (c > 0: scaling into the log2 domain commutes with max, so
+        // it folds into one FMA per probability)
         float mx = -INFINITY;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -521,14 +417,20 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
             mx = fmaxf(mx, v);
           }
         mx = max_rows4(mx);
-        // lazy rescale (as fwd_kernel): the running max moves - and O, l are rescaled - only when
-        // some row of the wave would otherwise see probabilities above 2^8 (wave-uniform branch;
+        // lazy rescale: the running max moves (and O, l are rescaled) only when some row of the
+        // wave would otherwise see probabilities above 2^8 - after the first key blocks the max
+        // rarely grows that much, so the multiplies and the exp are skipped (wave-uniform branch;
         // a fully masked row keeps mx = -inf and never triggers it)
         if (__any(mx * c > m[qg] + 8.f)) {
           const float mn = fmaxf(m[qg], mx * c);
           const float alpha = fexp2(m[qg] - mn);
           m[qg] = mn;
-          l[qg] *= alpha;
+          if constexpr (G == 1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lacc[r] *= alpha;
+          } else {
+            l[qg] *= alpha;
+          }
 #pragma unroll
           for (int d = 0; d < DT; ++d)
 #pragma unroll
@@ -544,9 +446,13 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
             sc[qg][t][r] = pv;
             ps += pv;
           }
-        l[qg] += ps;
+        l[qg] += ps;  // (dead at G == 1)
         pp[qg][0] = pack_pair(sc[qg][0], sc[qg][1]);
         pp[qg][1] = pack_pair(sc[qg][2], sc[qg][3]);
+        if constexpr (G == 1) {
+          lacc = mfma(ones, pp[0][0], lacc);
+          lacc = mfma(ones, pp[0][1], lacc);
+        }
       }
 #pragma unroll
       for (int d0 = 0; d0 < DT; d0 += DB) {
@@ -562,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
         for (int d = 0; d < DB; ++d) {
           const bf16x8 v0 = tr_use(vq[d][0]), v1 = tr_use(vq[d][1]);
 #pragma unroll
-          for (int qg = 0; qg < QG; ++qg) {
+          for (int qg = 0; qg < G; ++qg) {
             o[qg][d0 + d] = mfma(v0, pp[qg][0], o[qg][d0 + d]);
             o[qg][d0 + d] = mfma(v1, pp[qg][1], o[qg][d0 + d]);
           }
@@ -572,24 +478,19 @@ __global__ __launch_bounds__(256, 2) void fwd2_kernel(Args a) {
     if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
     step_barrier();
   }
-#undef KT
-#undef VT
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
-    const float lt = sum_rows4(l[qg]);
-    const float inv = 1.f / lt;
-    bf16_t* orow = a.out + ((long long)b * a.T + myq[qg]) * C + h * DH;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-      const uint2 v = make_uint2(pack_bf2(o[qg][d][0] * inv, o[qg][d][1] * inv),
-                                 pack_bf2(o[qg][d][2] * inv, o[qg][d][3] * inv));
-      *(uint2*)(orow + 16 * d + 4 * g) = v;
-    }
+  for (int qg = 0; qg < G; ++qg) {
+    const float lt = G == 1 ? lacc[0] : sum_rows4(l[qg]);
+    store_rows_bf16<DT>(a.out + ((long long)b * a.T + myq[qg]) * C + h * DH, o[qg], 1.f / lt, g);
     if (g == 0) a.lse[(long long)bh * a.T + myq[qg]] = m[qg] + log2f(lt);
   }
 }
 
 // ------------------------------------------------------------------------------ dK / dV
+// Not merged into one <DH, NS, DOC, G> kernel like the forward and dQ: the two-group body instantiated
+// with one group at Dh = 128 measured 0.26 - 0.28 % slower than bwd_dkdv_kernel<128> on the Llama
+// backward, outside the parent's run-to-run spread (profiles/attn_merge_ab.md), so both stay as
+// they were.
 // Ring slot = Q tile | dO tile | LSE[64] | delta[64] of one (q-head, q-block) step.  The 512 B
 // of row constants come by DMA as well (waves 0-1: LSE halves, waves 2-3: delta halves, 8
 // lanes x 16 B each), so every wave issues the same DH/16 + 1 DMA instructions per step.
@@ -1016,167 +917,17 @@ __global__ __launch_bounds__(256) void dkdv_reduce_kernel(Args a) {
 }
 
 // ------------------------------------------------------------------------------ dQ
-template <int DH, int NS, bool DOC = false>
+// Block = 64 G query rows of one (b, h), 16 G per wave; same K/V ring as the forward.
+template <int DH, int NS, bool DOC, int G>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
-  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
+  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, BLK = 64 * G;
+  constexpr int TILE = 64 * DH * 2, PER = DH / 16;
+  constexpr bool HOIST = DH != 64;  // see stage()
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4;
-  const int nqb = a.T / BQ;
-  int bx, bh;
-  grid_pos(a, bx, bh);
-  const int qb = nqb - 1 - bx;
-  const int b = bh / a.H, h = bh % a.H;
-  const int grp = a.H / a.Hkv, kvh = h / grp;
-  const int C = a.H * DH, W = C + 2 * a.Hkv * DH;
-  const bf16_t* base = a.qkv + (long long)b * a.T * W;
-  const int qcol = h * DH, kcol = C + kvh * DH, vcol = C + a.Hkv * DH + kvh * DH;
-  const int myq = qb * BQ + wave * 16 + (lane & 15);
-  const float c = a.scale * LOG2E;
-  uint32_t troff[DH / 16];
-  tr_lane_offsets<DH>(troff, lane);
-  const long long r = (long long)bh * a.T + myq;
-  const int nkb = qb + 1;
-  // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
-  int kb_lo = 0;
-  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ]) / BKV;
-
-#define KT(s) (smem + (s) * TILE)
-#define VT(s) (smem + (NS + (s)) * TILE)
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (kb_lo + s < nkb) {
-      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
-      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
-    }
-  bf16x8 qf[KS], of[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    qf[ks] = gload8(base + (long long)myq * W + qcol + ks * 32 + g * 8);
-    of[ks] = gload8(a.dout + ((long long)b * a.T + myq) * C + h * DH + ks * 32 + g * 8);
-  }
-  // delta = sum_d dO * O of this row (the softmax-backward row term): the lane's 8*KS columns
-  // of O against its dO fragment, summed over the 4 lane rows; stored for the dK/dV kernel,
-  // which runs after this one
-  bf16x8 ofw[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) ofw[ks] = gload8(a.out + ((long long)b * a.T + myq) * C + h * DH + ks * 32 + g * 8);
-  const float lse2 = a.lse[r];
-  int mylo = 0;  // DOC: first key of this row's document
-  if constexpr (DOC) mylo = a.doc_start[(long long)b * a.T + myq];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    settle(qf[ks]);
-    settle(of[ks]);
-    settle(ofw[ks]);
-  }
-  settle(lse2);
-  int wlo = 0;  // DOC: tiles that begin before the document of the wave's last row need the low mask
-  if constexpr (DOC) {
-    settle(mylo);
-    wlo = __builtin_amdgcn_readlane(mylo, 15);
-  }
-  float dsum = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      dsum = fmaf(bf2f((bf16_t)of[ks][e]), bf2f((bf16_t)ofw[ks][e]), dsum);
-  const float del = sum_rows4(dsum);
-  if (g == 0) a.delta[r] = del;
-  step_barrier();
-
-  f32x4 dq[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  for (int kb = kb_lo; kb < nkb; ++kb) {
-    const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
-    if (kb + NS - 1 < nkb) {
-      const int nx = (kb - kb_lo + NS - 1) % NS;
-      stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
-      stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
-    }
-    const char* kt = KT(cur);
-    const char* vt = VT(cur);
-    const uint32_t kbase_lds = lds_addr(kt);
-    const bool diag = (kb == qb);
-    f32x4 ds[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      f32x4 sacc = f32x4{0.f, 0.f, 0.f, 0.f}, dpacc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        sacc = mfma(frag_rows<DH>(kt, 16 * t, ks, lane), qf[ks], sacc);   // D[key][q]
-        dpacc = mfma(frag_rows<DH>(vt, 16 * t, ks, lane), of[ks], dpacc); // D[key][q]
-      }
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const float pv = fexp2(fmaf(sacc[rr], c, -lse2));
-        ds[t][rr] = pv * (dpacc[rr] - del);
-      }
-    }
-    if (diag) {  // causal mask on the diagonal block only (wave-uniform)
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-          if (kb * BKV + 16 * t + 4 * g + rr > myq) ds[t][rr] = 0.f;
-    }
-    if constexpr (DOC) {
-      if (kb * BKV < wlo) {  // (wave-uniform) keys before the row's document
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr)
-            if (kb * BKV + 16 * t + 4 * g + rr < mylo) ds[t][rr] = 0.f;
-      }
-    }
-    const bf16x8 d0 = pack_pair(ds[0], ds[1]), d1 = pack_pair(ds[2], ds[3]);
-#pragma unroll
-    for (int e0 = 0; e0 < DT; e0 += DB) {
-      TrPair fk[DB][2];
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        const uint32_t lk = kbase_lds + troff[e0 + d];
-        fk[d][0] = frag_cols_at<DH, 0>(lk);
-        fk[d][1] = frag_cols_at<DH, 32>(lk);
-      }
-      lgkm_wait0();
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        dq[e0 + d] = mfma(tr_use(fk[d][0]), d0, dq[e0 + d]);
-        dq[e0 + d] = mfma(tr_use(fk[d][1]), d1, dq[e0 + d]);
-      }
-    }
-    if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
-    step_barrier();
-  }
-#undef KT
-#undef VT
-  bf16_t* qrow = a.dqkv + ((long long)b * a.T + myq) * W + qcol;
-#pragma unroll
-  for (int d = 0; d < DT; ++d)
-    *(uint2*)(qrow + 16 * d + 4 * g) =
-        make_uint2(pack_bf2(dq[d][0] * a.scale, dq[d][1] * a.scale), pack_bf2(dq[d][2] * a.scale, dq[d][3] * a.scale));
-  if (a.cs_ws)
-    wave_colsum16<DT>(dq, a.scale, a.cs_ws + (((long long)b * a.T + qb * BQ + wave * 16) >> 4) * W + qcol, lane);
-}
-
-// dQ with 32 query rows per wave (block = 128 rows): every K / V fragment read from LDS (row and
-// transposed) feeds the MFMAs of two 16-row query groups, halving LDS bytes per MFMA of
-// bwd_dq_kernel - the change that took dK/dV from 130 to 82 us at GPT-2 shapes (bwd_dkdv2_kernel).
-// Same DMA ring, delta prologue, causal skip / mask and output contract.
-template <int DH, int NS, bool DOC = false>
-__global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
-  constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2, PER = DH / 16;
-  constexpr int QG = 2, BQ2 = 128;
-  __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = lane >> 4;
-  const int nqb = a.T / BQ2;
+  const int nqb = a.T / BLK;
   int bx, bh;
   grid_pos(a, bx, bh);
   const int qb = nqb - 1 - bx;  // heaviest (longest causal prefix) blocks first
@@ -1185,31 +936,29 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
   const int C = a.H * DH, W = C + 2 * a.Hkv * DH;
   const bf16_t* base = a.qkv + (long long)b * a.T * W;
   const int qcol = h * DH, kcol = C + kvh * DH, vcol = C + a.Hkv * DH + kvh * DH;
-  const int q0w = qb * BQ2 + wave * 32;  // this wave: rows [q0w, q0w + 32)
-  int myq[QG];
+  const int q0w = qb * BLK + wave * (16 * G);  // this wave: rows [q0w, q0w + 16 G)
+  int myq[G];
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) myq[qg] = q0w + 16 * qg + (lane & 15);
+  for (int qg = 0; qg < G; ++qg) myq[qg] = q0w + 16 * qg + (lane & 15);
   const float c = a.scale * LOG2E;
   uint32_t troff[DH / 16];
   tr_lane_offsets<DH>(troff, lane);
-  const int nkb = (qb + 1) * (BQ2 / BKV);
+  const int nkb = (qb + 1) * G;
   // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
   int kb_lo = 0;
-  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BQ2]) / BKV;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BLK]) / BKV;
 
-#define KT(s) (smem + (s) * TILE)
-#define VT(s) (smem + (NS + (s)) * TILE)
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
     if (kb_lo + s < nkb) {
-      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
-      stage<DH, DH != 64>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
+      stage<DH, HOIST>(base, W, (kb_lo + s) * BKV, kcol, KT(s), wave, lane);
+      stage<DH, HOIST>(base, W, (kb_lo + s) * BKV, vcol, VT(s), wave, lane);
     }
-  bf16x8 qf[QG][KS], of[QG][KS], ofw[QG][KS];
-  float lse2[QG];
-  int mylo[QG], wlo[QG];  // DOC: first key of the row's document; that of each group's last row
+  bf16x8 qf[G][KS], of[G][KS], ofw[G][KS];  // Q, dO and (for delta) O rows
+  float lse2[G];
+  int mylo[G], wlo[G];  // DOC: first key of the row's document; that of each group's last row
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
+  for (int qg = 0; qg < G; ++qg) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       qf[qg][ks] = gload8(base + (long long)myq[qg] * W + qcol + ks * 32 + g * 8);
@@ -1221,7 +970,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
     if constexpr (DOC) mylo[qg] = a.doc_start[(long long)b * a.T + myq[qg]];
   }
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
+  for (int qg = 0; qg < G; ++qg) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       settle(qf[qg][ks]);
@@ -1229,16 +978,18 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
       settle(ofw[qg][ks]);
     }
     settle(lse2[qg]);
-    wlo[qg] = 0;
+    wlo[qg] = 0;  // DOC: tiles that begin before the document of the group's last row need the low mask
     if constexpr (DOC) {
       settle(mylo[qg]);
       wlo[qg] = __builtin_amdgcn_readlane(mylo[qg], 15);
     }
   }
-  // delta = sum_d dO * O per row (the softmax-backward row term), stored for the dK/dV kernel
-  float del[QG];
+  // delta = sum_d dO * O of each row (the softmax-backward row term): the lane's 8*KS columns
+  // of O against its dO fragment, summed over the 4 lane rows; stored for the dK/dV kernel,
+  // which runs after this one
+  float del[G];
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
+  for (int qg = 0; qg < G; ++qg) {
     float dsum = 0.f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
@@ -1249,9 +1000,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
   }
   step_barrier();
 
-  f32x4 dq[QG][DT];
+  f32x4 dq[G][DT];
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg)
+  for (int qg = 0; qg < G; ++qg)
 #pragma unroll
     for (int d = 0; d < DT; ++d) dq[qg][d] = f32x4{0.f, 0.f, 0.f, 0.f};
 
@@ -1259,32 +1010,34 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
     const int cur = (kb - kb_lo) % NS;  // the ring is indexed from the loop start
     if (kb + NS - 1 < nkb) {
       const int nx = (kb - kb_lo + NS - 1) % NS;
-      stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
-      stage<DH, DH != 64>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
+      stage<DH, HOIST>(base, W, (kb + NS - 1) * BKV, kcol, KT(nx), wave, lane);
+      stage<DH, HOIST>(base, W, (kb + NS - 1) * BKV, vcol, VT(nx), wave, lane);
     }
-    // keys of this tile all after this wave's last row: nothing to add (barriers still run)
-    if (kb * BKV <= q0w + 31) {
+    // G == 2: keys of this tile all after this wave's last row - nothing to add (barriers still
+    // run).  G == 1: the loop ends with the block's own tile, which every wave meets
+    if (G == 1 || kb * BKV <= q0w + 16 * G - 1) {
       const char* kt = KT(cur);
       const char* vt = VT(cur);
       const uint32_t kbase_lds = lds_addr(kt);
-      const bool diag = kb * BKV + BKV - 1 > q0w;
-      f32x4 ds[QG][4];
+      // G == 1: the last tile, as an equality (keeps the specialised loop copies, see above)
+      const bool diag = G == 1 ? (kb == qb) : (kb * BKV + BKV - 1 > q0w);
+      f32x4 ds[G][4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        f32x4 sacc[QG], dpacc[QG];
+        f32x4 sacc[G], dpacc[G];
 #pragma unroll
-        for (int qg = 0; qg < QG; ++qg) sacc[qg] = dpacc[qg] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int qg = 0; qg < G; ++qg) sacc[qg] = dpacc[qg] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const bf16x8 kf = frag_rows<DH>(kt, 16 * t, ks, lane), vf = frag_rows<DH>(vt, 16 * t, ks, lane);
 #pragma unroll
-          for (int qg = 0; qg < QG; ++qg) {
+          for (int qg = 0; qg < G; ++qg) {
             sacc[qg] = mfma(kf, qf[qg][ks], sacc[qg]);    // D[key][q]
             dpacc[qg] = mfma(vf, of[qg][ks], dpacc[qg]);  // D[key][q]
           }
         }
 #pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
+        for (int qg = 0; qg < G; ++qg)
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const float pv = fexp2(fmaf(sacc[qg][rr], c, -lse2[qg]));
@@ -1293,7 +1046,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
       }
       if (diag) {  // causal mask where the tile meets this wave's rows (wave-uniform)
 #pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
+        for (int qg = 0; qg < G; ++qg)
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -1302,7 +1055,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
       }
       if constexpr (DOC) {
 #pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
+        for (int qg = 0; qg < G; ++qg)
           if (kb * BKV < wlo[qg]) {  // (wave-uniform) keys before the row's document
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -1311,9 +1064,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
                 if (kb * BKV + 16 * t + 4 * g + rr < mylo[qg]) ds[qg][t][rr] = 0.f;
           }
       }
-      bf16x8 d0[QG], d1[QG];
+      bf16x8 d0[G], d1[G];
 #pragma unroll
-      for (int qg = 0; qg < QG; ++qg) {
+      for (int qg = 0; qg < G; ++qg) {
         d0[qg] = pack_pair(ds[qg][0], ds[qg][1]);
         d1[qg] = pack_pair(ds[qg][2], ds[qg][3]);
       }
@@ -1331,7 +1084,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
         for (int d = 0; d < DB; ++d) {
           const bf16x8 k0 = tr_use(fk[d][0]), k1 = tr_use(fk[d][1]);
 #pragma unroll
-          for (int qg = 0; qg < QG; ++qg) {
+          for (int qg = 0; qg < G; ++qg) {
             dq[qg][e0 + d] = mfma(k0, d0[qg], dq[qg][e0 + d]);
             dq[qg][e0 + d] = mfma(k1, d1[qg], dq[qg][e0 + d]);
           }
@@ -1341,19 +1094,16 @@ __global__ __launch_bounds__(256, 2) void bwd_dq2_kernel(Args a) {
     if (kb + 1 < nkb) wait_vm_upto(PER * (min(kb + NS - 1, nkb - 1) - kb - 1));
     step_barrier();
   }
-#undef KT
-#undef VT
 #pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
-    bf16_t* qrow = a.dqkv + ((long long)b * a.T + myq[qg]) * W + qcol;
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-      *(uint2*)(qrow + 16 * d + 4 * g) = make_uint2(pack_bf2(dq[qg][d][0] * a.scale, dq[qg][d][1] * a.scale),
-                                                   pack_bf2(dq[qg][d][2] * a.scale, dq[qg][d][3] * a.scale));
+  for (int qg = 0; qg < G; ++qg) {
+    store_rows_bf16<DT>(a.dqkv + ((long long)b * a.T + myq[qg]) * W + qcol, dq[qg], a.scale, g);
     if (a.cs_ws)
       wave_colsum16<DT>(dq[qg], a.scale, a.cs_ws + (((long long)b * a.T + q0w + 16 * qg) >> 4) * W + qcol, lane);
   }
 }
+
+#undef KT
+#undef VT
 
 }  // namespace fa
 }  // namespace rtdc
@@ -1367,12 +1117,30 @@ static int fa_xcd() {
   return v;
 }
 
+// 16-row groups per wave (the kernels' G) from a rows-per-wave knob: 1 | 2 forces that many,
+// unset (or 0) takes dflt; blocks of 128 rows need T % 128 == 0, every other T runs one group.
+// (read per call: tests A/B the knobs in one process)
+static int fa_groups(const char* knob, int dflt, int T) {
+  const char* e = getenv(knob);
+  const int forced = e ? atoi(e) : 0;
+  return (forced ? forced : dflt) == 2 && T % 128 == 0 ? 2 : 1;
+}
+
+// KERNEL<Dh, 2, DOC, G> on T / (64 G) blocks x NY, on `st`.
 // Ring depth: every kernel is launched with NS = 2.  Measured at Dh = 64 on GPT-2 shapes (B16
 // T1024 H12, benchmarks/attn_bench.py): NS 2 / 3 / 4 = fwd 108 / 113 / 135 us, bwd 285 / 335 /
 // 357 us - every extra slot costs a co-resident block per CU (32 / 48 / 64 KiB of LDS per
 // block), and at these 8-16-step loops occupancy hides more HBM latency than a deeper ring.
 // At Dh = 128 a third slot leaves one block per CU.
-#define FA_LAUNCH(KERNEL, DH, GRID, ARGS) hipLaunchKernelGGL((KERNEL<DH, 2, DOC>), GRID, dim3(256), 0, st, ARGS)
+#define FA_LAUNCH_1(KERNEL, DH, G, NY, ARGS) \
+  hipLaunchKernelGGL((KERNEL<DH, 2, DOC, G>), dim3(T / (64 * G), NY), dim3(256), 0, st, ARGS)
+#define FA_LAUNCH(KERNEL, G, NY, ARGS)                        \
+  do {                                                        \
+    if (Dh == 64 && (G) == 1) FA_LAUNCH_1(KERNEL, 64, 1, NY, ARGS);   \
+    else if (Dh == 64) FA_LAUNCH_1(KERNEL, 64, 2, NY, ARGS);          \
+    else if ((G) == 1) FA_LAUNCH_1(KERNEL, 128, 1, NY, ARGS);         \
+    else FA_LAUNCH_1(KERNEL, 128, 2, NY, ARGS);                       \
+  } while (0)
 
 // DOC = true: the document-masked kernels (doc_start / doc_end set); same dispatch
 template <bool DOC>
@@ -1387,18 +1155,8 @@ static int flash_fwd_launch(const void* qkv, void* out, float* lse, int B, int T
   // measured (benchmarks/attn_bench.py, before the DMA ring): 32 rows/wave wins at Dh = 128
   // (Llama: 101 vs 108 us), 16 rows/wave at Dh = 64 (GPT-2: 100 vs 109 us); RTDC_FA_FWD=1|2
   // forces one
-  const char* fwd_env = getenv("RTDC_FA_FWD");  // (read per call: tests A/B it in one process)
-  const int forced = fwd_env ? atoi(fwd_env) : 0;
-  const int variant = forced ? forced : (Dh == 128 ? 2 : 1);
-  if (variant == 2 && T % 128 == 0) {  // 32 rows per wave
-    dim3 grid(T / 128, B * H);
-    if (Dh == 64) FA_LAUNCH(fa::fwd2_kernel, 64, grid, a);
-    else FA_LAUNCH(fa::fwd2_kernel, 128, grid, a);
-  } else {
-    dim3 grid(T / 64, B * H);
-    if (Dh == 64) FA_LAUNCH(fa::fwd_kernel, 64, grid, a);
-    else FA_LAUNCH(fa::fwd_kernel, 128, grid, a);
-  }
+  const int G = fa_groups("RTDC_FA_FWD", Dh == 128 ? 2 : 1, T);
+  FA_LAUNCH(fa::fwd_kernel, G, B * H, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -1421,7 +1179,6 @@ static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, 
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
   if (qs < 1 || (H / Hkv) % qs != 0 || (qs > 1 && part == nullptr) || ((Hkv * 2 * Dh) % 4) != 0) return 1;
   if (DOC && (doc_start == nullptr || doc_end == nullptr)) return 1;
-  // dQ first: it also computes the row terms delta = rowsum(dO * O) that dK/dV read
   fa::Args a{};
   a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)out; a.dout = (const bf16_t*)dout; a.lse = (float*)lse;
   a.delta = delta;
@@ -1430,34 +1187,20 @@ static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, 
   a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
   a.part = part; a.qs = qs;
   a.doc_start = doc_start; a.doc_end = doc_end;
-  dim3 g1(T / 64, B * Hkv * qs), g2(T / 64, B * H);
-  // dK/dV at Dh = 64: 32 keys per wave (bwd_dkdv2_kernel) unless RTDC_FA_DKDV=1 (16 keys per wave)
-  const char* dkdv_env = getenv("RTDC_FA_DKDV");  // (read per call: tests A/B it in one process)
-  const int dkdv_v = dkdv_env ? atoi(dkdv_env) : 2;
-  // dQ: 32 query rows per wave (bwd_dq2_kernel; GPT-2 63 -> 59 us, Llama-3-8B shapes 165 -> 140 us
-  // per call, benchmarks/attn_bench.py under rocprofv3) unless RTDC_FA_DQ=1 (16 rows per wave)
-  const char* dq_env = getenv("RTDC_FA_DQ");  // (read per call: tests A/B it in one process)
-  const bool dq2 = (dq_env ? atoi(dq_env) : 2) == 2 && T % 128 == 0;
-  const dim3 g2b(T / 128, B * H);
-  if (Dh == 64) {
-    if (dq2) FA_LAUNCH(fa::bwd_dq2_kernel, 64, g2b, a);
-    else FA_LAUNCH(fa::bwd_dq_kernel, 64, g2, a);
-    if (dkdv_v == 2 && T % 128 == 0) {
-      dim3 g3(T / 128, B * Hkv * qs);
-      FA_LAUNCH(fa::bwd_dkdv2_kernel, 64, g3, a);
-    } else {
-      FA_LAUNCH(fa::bwd_dkdv_kernel, 64, g1, a);
-    }
-  } else {
-    if (dq2) FA_LAUNCH(fa::bwd_dq2_kernel, 128, g2b, a);
-    else FA_LAUNCH(fa::bwd_dq_kernel, 128, g2, a);
-    if (dkdv_env && dkdv_v == 2 && T % 128 == 0) {  // opt-in at Dh = 128 (occupancy 1)
-      dim3 g3(T / 128, B * Hkv * qs);
-      FA_LAUNCH(fa::bwd_dkdv2_kernel, 128, g3, a);
-    } else {
-      FA_LAUNCH(fa::bwd_dkdv_kernel, 128, g1, a);
-    }
-  }
+  // dQ first: it also computes the row terms delta = rowsum(dO * O) that dK/dV read.  32 query
+  // rows per wave (GPT-2 63 -> 59 us, Llama-3-8B shapes 165 -> 140 us per call,
+  // benchmarks/attn_bench.py under rocprofv3) unless RTDC_FA_DQ=1 (16 rows per wave)
+  const int gdq = fa_groups("RTDC_FA_DQ", 2, T);
+  FA_LAUNCH(fa::bwd_dq_kernel, gdq, B * H, a);
+  // dK/dV: 32 keys per wave at Dh = 64 unless RTDC_FA_DKDV=1 (16 keys per wave); at Dh = 128 two
+  // groups run at occupancy 1 and are slower, so they are an opt-in there (RTDC_FA_DKDV=2)
+  const int gdkdv = fa_groups("RTDC_FA_DKDV", Dh == 64 ? 2 : 1, T);
+  // (still two kernels, see above them: G picks the kernel, not a template argument)
+  const dim3 gkv(T / (64 * gdkdv), B * Hkv * qs);
+  if (gdkdv == 2 && Dh == 64) hipLaunchKernelGGL((fa::bwd_dkdv2_kernel<64, 2, DOC>), gkv, dim3(256), 0, st, a);
+  else if (gdkdv == 2) hipLaunchKernelGGL((fa::bwd_dkdv2_kernel<128, 2, DOC>), gkv, dim3(256), 0, st, a);
+  else if (Dh == 64) hipLaunchKernelGGL((fa::bwd_dkdv_kernel<64, 2, DOC>), gkv, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((fa::bwd_dkdv_kernel<128, 2, DOC>), gkv, dim3(256), 0, st, a);
   if (qs > 1) {
     const int KV = Hkv * 2 * Dh;
     dim3 gr((unsigned)((long long)B * T / 16), (unsigned)((KV / 4 + 255) / 256));

@@ -3,7 +3,11 @@
 in profiles/.
 
     python scripts/bitwise_dump.py attn|norm|resnet|gemm OUT.pt
-    python -c "import torch; a, b = torch.load('A.pt'), torch.load('B.pt'); ..."   (compare)
+    python scripts/bitwise_dump.py compare A.pt B.pt
+
+`attn` runs every instantiation of the flash kernels at small shapes (all three rows-per-wave knobs
+at 1 and at 2, head splits, plain and document-masked, every output), then three large default
+cases (profiles/attn_merge_bitwise.md).
 
 The `optim` family compares two COMMITS, not two builds: it covers the Python side of the fused
 optimizers' step as well, so drop this file into a checkout of the other commit, build the
@@ -20,10 +24,61 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _attn_variants(out):
+    """Every instantiation of the flash kernels, and dkdv_reduce_kernel, at small shapes: the native
+    entry points called as ops/attention.py's backward calls them (column-sum workspace requested,
+    head split from RTDC_FA_QS as _dkdv_head_split takes it), with every output kept - y, lse, dqkv,
+    delta and the colsum workspace.  T = 192 falls back to one 16-row group per wave at any knob,
+    T = 384 is an odd number of 128-row blocks; (2, 2, 2) at Dh = 128 is the dK/dV opt-in.  Plain, and
+    one ragged document layout: boundaries inside a tile (37, T - 5, 100) and, from T = 192 on, a
+    document that spans several tiles."""
+    from ray_torch_distributed_checkpoint_amd.ops import DocLayout
+    from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+
+    ext, B = gpu_ext(), 2
+    saved = {k: os.environ.get(k) for k in ("RTDC_FA_FWD", "RTDC_FA_DQ", "RTDC_FA_DKDV")}
+    for T in (64, 192, 256, 384):
+        docs = DocLayout.from_lengths([[37, T - 42, 5], [100, T - 100] if T > 100 else [T]], T, "cuda")
+        for H, Hkv, Dh in ((4, 4, 64), (8, 2, 64), (8, 2, 128)):
+            W, scale = (H + 2 * Hkv) * Dh, Dh ** -0.5
+            torch.manual_seed(T + H + Dh)
+            qkv = (torch.randn(B, T, W, device="cuda") * 0.5).bfloat16()
+            dy = torch.randn(B, T, H * Dh, device="cuda").bfloat16()
+            for knob in (1, 2):
+                for k in saved:
+                    os.environ[k] = str(knob)
+                for qs in (1, 2, 4):
+                    if (H // Hkv) % qs:
+                        continue
+                    for d in (None, docs):
+                        y = torch.zeros((B, T, H * Dh), dtype=torch.bfloat16, device="cuda")
+                        lse = torch.zeros((B * H, T), dtype=torch.float32, device="cuda")
+                        delta, dqkv = torch.zeros_like(lse), torch.zeros_like(qkv)
+                        cs = torch.zeros((B * T // 16, W), dtype=torch.float32, device="cuda")
+                        part = torch.zeros(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device="cuda") if qs > 1 else None
+                        if d is None:
+                            ext.flash_fwd(qkv, y, lse, B, T, H, Hkv, Dh, scale)
+                            ext.flash_bwd(qkv, y, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs)
+                        else:
+                            ext.flash_fwd_doc(qkv, y, lse, d.start, d.end, B, T, H, Hkv, Dh, scale)
+                            ext.flash_bwd_doc(qkv, y, dy, lse, delta, dqkv, d.start, d.end, B, T, H, Hkv, Dh, scale,
+                                              cs, part, qs)
+                        torch.cuda.synchronize()
+                        name = f"T{T}.H{H}kv{Hkv}d{Dh}.knobs{knob}.qs{qs}.{'plain' if d is None else 'doc'}"
+                        out[name] = {"y": y.cpu(), "lse": lse.cpu(), "dqkv": dqkv.cpu(), "delta": delta.cpu(),
+                                     "colsum": cs.cpu()}
+    for k, v in saved.items():  # the large cases below run at the caller's knobs
+        if v is None:
+            del os.environ[k]
+        else:
+            os.environ[k] = v
+
+
 def attn():
     from ray_torch_distributed_checkpoint_amd.ops.attention import causal_attention
 
     out = {}
+    _attn_variants(out)
     for name, B, T, H, Hkv, Dh in [("gpt2", 4, 1024, 12, 12, 64), ("gqa64", 2, 512, 8, 2, 64),
                                    ("llama", 1, 1024, 32, 8, 128)]:
         torch.manual_seed(7)

@@ -68,6 +68,14 @@ def plain_name(d):
     kernel<A, false> are both kernel<A>), and with it the empty argument struct that such a switch
     adds to the parameter list (`, rtdc::XentAux<false>`): the name the kernel had before."""
     d = re.sub(r", rtdc::XentAux<false>\)", ")", d)
+    # flash attention: the row groups per wave became the kernels' fourth template argument, so
+    # name2_kernel<D, NS[, true]> is name_kernel<D, NS, doc, 2> and name_kernel<D, NS[, true]> is
+    # name_kernel<D, NS, doc, 1>; both trees are keyed by the four-argument name (a pair that is
+    # still two kernels in both trees lines up under those names as well)
+    m = re.match(r"(.*\bfa::(?:fwd|bwd_dq|bwd_dkdv))(2?)_kernel<(\d+), (\d+)(?:, (true|false))?>(.*)$", d)
+    if m:
+        return "%s_kernel<%s, %s, %s, %d>%s" % (m.group(1), m.group(3), m.group(4), m.group(5) or "false",
+                                                2 if m.group(2) else 1, m.group(6))
     while True:
         n = re.sub(r", false>", ">", d)
         if n == d:

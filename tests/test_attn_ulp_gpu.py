@@ -11,8 +11,8 @@ test its WORST lines; those of one run are kept in profiles/attn_ulp_worst.txt.
 Kernel -> the cases that reach it (U.attn_launches mirrors flash_fwd_launch / flash_bwd_launch;
 tests/test_ulp_cpu.py::test_attn_grids_meet_every_xcd_branch checks the grids):
 
-  fwd / bwd_dq / bwd_dkdv      RTDC_FA_* = 1 at every T; whatever the knob at T = 64 and 192
-  fwd2 / bwd_dq2 / bwd_dkdv2   RTDC_FA_* = 2 at T = 128, 256, 384 (Dh = 128 dkdv2: opt-in, set here)
+  fwd / bwd_dq with G = 1, bwd_dkdv    RTDC_FA_* = 1 at every T; whatever the knob at T = 64 and 192
+  fwd / bwd_dq with G = 2, bwd_dkdv2   RTDC_FA_* = 2 at T = 128, 256, 384 (Dh = 128 dkdv2: opt-in, set here)
   dkdv_reduce                  RTDC_FA_QS = 2, 4 where the group size allows
   DOC instantiations           layouts A, aligned, ones; the plain ones with docs=None
   composed GEMM + softmax      T = 100 (no flash kernel), T = 128 with RTDC_ATTN=gemm

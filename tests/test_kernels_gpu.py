@@ -900,7 +900,7 @@ def test_flash_forward_lazy_rescale_branch(Dh, H, Hkv):
     (a rare, data-dependent, wave-uniform branch): spike Q.K scores at LATER key blocks so the
     branch fires mid-row (twice, at key blocks 3 and 4 for query 300, once at block 6 for query
     450), and compare the whole output and the gradients against the fp32 reference
-    (cdna_hip_programming.md §5.4 rule 26).  Dh 64 runs fwd_kernel, Dh 128 fwd2_kernel."""
+    (cdna_hip_programming.md §5.4 rule 26).  Dh 64 runs fwd_kernel with G = 1, Dh 128 with G = 2."""
     from ray_torch_distributed_checkpoint_amd.ops import causal_attention
     from ray_torch_distributed_checkpoint_amd.ops.attention import causal_attention_ref
 
@@ -1079,7 +1079,7 @@ def test_flash_dkdv_32_keys_per_wave_equals_16(monkeypatch, H, Hkv, T):
 
 @pytest.mark.parametrize("Dh,H,Hkv,T", [(64, 4, 4, 256), (64, 4, 2, 512), (64, 2, 2, 1024), (128, 4, 1, 384)])
 def test_flash_dq_32_rows_per_wave_equals_16(monkeypatch, Dh, H, Hkv, T):
-    """dQ with two 16-row query groups per wave (bwd_dq2_kernel, RTDC_FA_DQ=2) runs every row
+    """dQ with two 16-row query groups per wave (bwd_dq_kernel with G = 2, RTDC_FA_DQ=2) runs every row
     over the same key tiles in the same MFMA order as the 16-rows-per-wave kernel (a tile the
     wave's upper group reaches but its lower one does not adds exact zeros): bitwise equal
     gradients and row terms; colsum partials equal to fp32 rounding."""

@@ -266,7 +266,8 @@ def test_attn_offset_heads():
 
 
 def test_attn_grids_meet_every_xcd_branch():
-    """every kernel of attn_flash.hip is launched, over the case table x variants x head splits, on
+    """every kernel of attn_flash.hip is launched with one and with two row groups per wave (the
+    names ending in 2: fwd_kernel and bwd_dq_kernel with G = 2, bwd_dkdv2_kernel), over the case table x variants x head splits, on
     grids that take each branch of xcd_grid: gridDim.y % 8 == 0; n % 8 == 0 with gridDim.y % 8 != 0;
     n % 8 != 0, once with n < 8.  The table also holds every value the issue lists."""
     seen = {}

@@ -563,7 +563,8 @@ def judge_rope(J, shape, x, H, Hkv, Dh, inverse, out, what="y"):
 
 
 # ------------------------------------------------------------------------------- flash attention
-# attn_flash.hip (fwd, fwd2, bwd_dq, bwd_dq2, bwd_dkdv, bwd_dkdv2, dkdv_reduce) and the composed
+# attn_flash.hip (fwd_kernel and bwd_dq_kernel with one and two 16-row groups per wave, G = 1 | 2;
+# bwd_dkdv_kernel, bwd_dkdv2_kernel, dkdv_reduce_kernel) and the composed
 # GEMM + softmax path of ops/attention.py, judged per element against an explicit fp64 forward and
 # backward.  Unlike the row kernels these round to bf16 INSIDE the computation (the probabilities
 # feed MFMAs as bf16 operands), so the allowance is not measured from an unrounded twin: it is the
@@ -651,7 +652,7 @@ def attn_ref(dtype, qkv, dout, B, T, H, Hkv, Dh, docs=None, twin=False, mutant="
 
     dtype float64, twin False: the reference; it also returns the per-element allowance of every
     output ("allow_<name>").  twin=True (float32): the kernel's bf16 roundings where attn_flash.hip
-    places them - e ahead of P.V and of the row sum (pack_pair in fwd_kernel; fwd2_kernel sums the
+    places them - e ahead of P.V and of the row sum (pack_pair in fwd_kernel; with G = 2 it sums the
     unrounded e, one rounding fewer), O as stored and as delta reads it, P ahead of dV, dS ahead of
     dQ / dK, each stored gradient once after the fp32 sum over the group (registers, or the
     head-split partials).  path="gemm": the composed path of ops/attention.py, which also stores
@@ -894,7 +895,8 @@ def attn_head_splits(H, Hkv):
 
 def attn_launches(B, T, H, Hkv, Dh, v, qs):
     """(kernel, gridDim.x, gridDim.y) of the three launches, from flash_fwd_launch / flash_bwd_launch
-    with all three variant knobs set (so Dh = 128 takes bwd_dkdv2 when asked)."""
+    with all three variant knobs set (so Dh = 128 takes bwd_dkdv2 when asked).  "fwd2" and "dq2" are
+    fwd_kernel and bwd_dq_kernel with G = 2 (32 rows per wave, 128-row blocks), the bare names G = 1."""
     two = T % 128 == 0
     f, d, kv = (x == 2 and two for x in v)
     return [("fwd2" if f else "fwd", T // (128 if f else 64), B * H),

@@ -22,6 +22,7 @@ int rtdc_gemm_f32(const rtdc::GemmF32Args* args, hipStream_t st);
 int rtdc_gemm8_grouped(const rtdc::GemmArgs* args, int n, int a_kmajor, int b_kmajor, int out_fp32, hipStream_t st);
 int rtdc_gemm4b_set(int v);
 int rtdc_conv_gemm(const rtdc::GemmArgs* args, int mode, hipStream_t stream);
+int rtdc_conv_knobs_reload();
 int rtdc_layernorm_fwd(const void* x, const void* g, const void* b, void* y, float* mean, float* rstd,
                        int M, int D, float eps, hipStream_t st);
 int rtdc_rmsnorm_fwd(const void* x, const void* g, void* y, float* rstd, int M, int D, float eps,
@@ -1344,6 +1345,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("im2col", &im2col);
   m.def("conv_gemm", &conv_gemm);
+  m.def("conv_knobs_reload", []() { return (int64_t)rtdc_conv_knobs_reload(); },
+        "forget the cached RTDC_CONV* / RTDC_BN_SPLIT_FINALIZE knobs and read the environment again; returns the "
+        "values read, one bit per knob");
   m.def("conv_gemm_bnb", &conv_gemm_bnb);
   m.def("col2im", &col2im);
   m.def("bn_fwd", &bn_fwd);

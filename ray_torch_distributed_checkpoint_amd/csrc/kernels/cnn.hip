@@ -614,8 +614,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16_t* __restri
       for (int kw = 0; kw < K; ++kw) {
         const int w = wo * s - p + kw;
         if ((unsigned)w >= (unsigned)W) continue;
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        acc8(v, *(const uint4*)(x + ((size_t)(b * H + h) * W + w) * C + c));
+        float v[8];  // (unpacked, not added to zero: 0 + -0 is +0, and y keeps the bits of its maximum)
+        unpack8(*(const uint4*)(x + ((size_t)(b * H + h) * W + w) * C + c), v);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           if (v[e] > best[e]) {
@@ -1079,13 +1079,19 @@ extern "C" int rtdc_col2im(const void* dcols, void* dx, const void* addend, int 
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+static int g_split_finalize = -1;  // cached; rtdc_bn_knobs_reload() forgets it
 static bool split_finalize_enabled() {
-  static int v = -1;  // RTDC_BN_SPLIT_FINALIZE=0: one block per channel over all partials (A/B)
+  int& v = g_split_finalize;  // RTDC_BN_SPLIT_FINALIZE=0: one block per channel over all partials (A/B)
   if (v < 0) {
     const char* e = getenv("RTDC_BN_SPLIT_FINALIZE");
     v = (e && e[0] == '0') ? 0 : 1;
   }
   return v == 1;
+}
+
+extern "C" int rtdc_bn_knobs_reload() {  // called by rtdc_conv_knobs_reload (gemm_bf16.hip)
+  g_split_finalize = -1;
+  return split_finalize_enabled() ? 1 : 0;
 }
 
 // pmean/pm2 (optional): per-row-block statistics already computed by the producer (the

@@ -495,8 +495,13 @@ static void launch_cfg(const GemmArgs& a, int batch, hipStream_t st) {
 // (32x64 each: 97-102 VGPRs, four waves per SIMD with two blocks per CU) instead of 4 waves of
 // 64x64 (169 registers, two waves per SIMD): ResNet-18 8.74 vs 8.88 ms/step
 // (profiles/conv_w8_ab_r3.txt).  RTDC_CONV64_W8=0 restores the 4-wave tiles.
+// The convolution knobs are read once and cached (they sit on the launch path);
+// rtdc_conv_knobs_reload() forgets the cached values.  Slots: RTDC_CONV64_W8, RTDC_CONV128_W8,
+// RTDC_CONV64WG_W8, RTDC_CONV3_WGRAD, RTDC_CONV3_KP.
+static int g_conv_knob[5] = {-1, -1, -1, -1, -1};
+
 static bool conv64_w8() {
-  static int v = -1;
+  int& v = g_conv_knob[0];
   if (v < 0) {
     const char* e = getenv("RTDC_CONV64_W8");
     v = (e && e[0] == '0') ? 0 : 1;
@@ -507,7 +512,7 @@ static bool conv64_w8() {
 // waves (32x64 each) instead of 4 (64x64): ResNet-18 8.56 vs 8.71 ms/step
 // (profiles/conv_w8_ab_r3.txt).  RTDC_CONV128_W8=0 restores the 4-wave tiles.
 static bool conv128_w8() {
-  static int v = -1;
+  int& v = g_conv_knob[1];
   if (v < 0) {
     const char* e = getenv("RTDC_CONV128_W8");
     v = (e && e[0] == '0') ? 0 : 1;
@@ -516,7 +521,7 @@ static bool conv128_w8() {
 }
 // RTDC_CONV64WG_W8=1: the Cout = 64 weight gradients on 64x256 tiles of 8 waves (64x32 each)
 static bool conv64wg_w8() {
-  static int v = -1;
+  int& v = g_conv_knob[2];
   if (v < 0) {
     const char* e = getenv("RTDC_CONV64WG_W8");
     v = (e && e[0] == '1') ? 1 : 0;
@@ -1040,7 +1045,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_wgrad_kernel(wg3::Args a) {
 }
 
 static bool conv3_wgrad_enabled() {
-  static int v = -1;  // RTDC_CONV3_WGRAD=0: the implicit-GEMM weight gradient (A/B)
+  int& v = g_conv_knob[3];  // RTDC_CONV3_WGRAD=0: the implicit-GEMM weight gradient (A/B)
   if (v < 0) {
     const char* e = getenv("RTDC_CONV3_WGRAD");
     v = (e && e[0] == '0') ? 0 : 1;
@@ -1050,17 +1055,22 @@ static bool conv3_wgrad_enabled() {
 
 // mode-2 arguments of a 3x3 / stride 1 / pad 1 weight gradient -> conv3x3_wgrad_kernel (+ the
 // split reduce); 1 = shape not taken (the caller runs the implicit GEMM)
+static int conv3_kp() {
+  int& kp_env = g_conv_knob[4];  // RTDC_CONV3_KP=128: 128-pixel chunks where they fit (A/B; default 64)
+  if (kp_env < 0) {
+    const char* e = getenv("RTDC_CONV3_KP");
+    kp_env = (e && e[0] == '1') ? 128 : 64;
+  }
+  return kp_env;
+}
+
 static int launch_conv3x3_wgrad(const GemmArgs& ga, hipStream_t st) {
   const int H = ga.cv_H, W = ga.cv_W, Cin = ga.cv_C, Cout = ga.M;
   if (Cin % 64 || Cout % 64 || W < 1 || W > 64 || H < 1 || ga.lda != Cout) return 1;
   const int B = ga.cv_npix / (H * W);
   // 128-pixel chunks (half the barriers and staging rounds per pixel) when whole rows fill at
   // least 3/4 of them and the halo fits; else 64
-  static int kp_env = -1;  // RTDC_CONV3_KP=128: 128-pixel chunks where they fit (A/B; default 64)
-  if (kp_env < 0) {
-    const char* e = getenv("RTDC_CONV3_KP");
-    kp_env = (e && e[0] == '1') ? 128 : 64;
-  }
+  const int kp_env = conv3_kp();
   int KP = 128, RC = 128 / W;
   RC = RC < H ? RC : H;
   if (kp_env == 64 || RC * W * 4 < 3 * 128 || (RC + 2) * (W + 2) > wg3::Cfg<128>::kMaxHalo) {
@@ -1105,6 +1115,17 @@ static int launch_conv3x3_wgrad(const GemmArgs& ga, hipStream_t st) {
     launch_splitk_reduce<float>(r, st);
   }
   return 0;
+}
+
+extern "C" int rtdc_bn_knobs_reload();  // cnn.hip: RTDC_BN_SPLIT_FINALIZE
+
+// Forgets the six cached convolution / BatchNorm knobs and reads the environment again (tests
+// switch arms in one process; nothing is added to the launch path).  Returns what it read, one
+// bit per knob in the slot order of g_conv_knob (bit 4: 128-pixel chunks), bit 5: RTDC_BN_SPLIT_FINALIZE.
+extern "C" int rtdc_conv_knobs_reload() {
+  for (int& v : g_conv_knob) v = -1;
+  return (conv64_w8() ? 1 : 0) | (conv128_w8() ? 2 : 0) | (conv64wg_w8() ? 4 : 0) | (conv3_wgrad_enabled() ? 8 : 0) |
+         (conv3_kp() == 128 ? 16 : 0) | (rtdc_bn_knobs_reload() ? 32 : 0);
 }
 
 // Implicit-GEMM convolution products on the same MFMA kernel (see ConvStagerK / ConvStagerMN):

@@ -28,7 +28,7 @@ def _nhwc(x):
         (2, 16, 64, 128, 1, 2, 0),  # projection shortcut
         (2, 32, 3, 64, 7, 2, 3),  # stem (C=3: scalar im2col, K padded 147 -> 192)
         (2, 224, 3, 64, 7, 2, 3),  # ImageNet stem: LDS-staged im2col (224 wide)
-        (4, 8, 128, 64, 1, 1, 0),  # 1x1/s1: direct (no im2col)
+        (4, 8, 128, 64, 1, 1, 0),  # 1x1/s1, C % 64 == 0: the implicit GEMM (the `direct` branch is unreachable)
         (1, 7, 64, 64, 3, 1, 1),  # M = 49: rows padded to 64
         (2, 14, 128, 256, 3, 1, 1),  # implicit GEMM, 128x128 tiles
         (4, 28, 128, 64, 3, 1, 1),  # Cout = 64: 256x64 fwd tile, 64x256 wgrad tile

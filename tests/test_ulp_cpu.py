@@ -13,7 +13,14 @@
 * GEMM (after it): the fp32 twin of `gemm_ref` stays under its ceilings on every case of the GEMM
   table, which fixes FLOOR_GEMM (half of it leaves the ceiling); eight deliberate errors each
   leave the allowance on the output they corrupt, at (520, 392, 192) and at the split-K shape
-  (264, 264, 2048); the whole-tensor yardstick accepts four of them on a bf16 output.
+  (264, 264, 2048); the whole-tensor yardstick accepts four of them on a bf16 output;
+* CNN (the last section): the twins of `conv_ref`, `bn_ref` and the pool references stay under
+  their ceilings on every case and generator of the CNN tables (the column-path dgrad inside its
+  counted allowance), which fixes FLOOR_BN_Y and FLOOR_BN_DX; the tap-loop references equal torch's
+  convolution and pooling in float64 and the layout formulas are consistent with one another;
+  seven convolution, six BatchNorm and three pooling errors each leave the allowance; the
+  whole-tensor yardstick of tests/test_cnn_gpu.py accepts four of them (six at its own sizes);
+  mirrors of the launchers' grid arithmetic show that the table meets every branch the GPU tests name.
 """
 import pytest
 import torch
@@ -431,3 +438,340 @@ def test_old_yardstick_accepts_gemm_mutants():
     both = tuple(m for m in U.GEMM_MUTANTS if GEMM_MUTANT_WHERE[m][1] == "C"
                  and all(accepted[(m, s)][0] for s in GEMM_MUTANT_SHAPES))
     assert set(both) == set(GEMM_OLD_ACCEPTS), both
+
+
+# ------------------------------------------------------------------------------- CNN (ResNet path)
+_cnn_refs: dict = {}
+
+
+def _conv_case(case, gen="randn"):
+    """(inputs, reference, twin) of one row of a CNN_CONV_* table, computed once"""
+    key = (case, gen)
+    if key not in _cnn_refs:
+        _, B, H, W, C, Co, k, s, p = case
+        c = U.conv_inputs(gen, B, H, W, C, Co, k, k, s, p, addend=True)
+        a = (c["x"], c["w"], s, p, c["dy"], c["addend"])
+        _cnn_refs[key] = (c, a, U.conv_ref(F64, *a), U.conv_ref(F32, *a))
+    return _cnn_refs[key]
+
+
+def _wgrad3_as_conv(row, B=3):
+    name, H, W, C, Co = row
+    return (name, B, H, W, C, Co, 3, 1, 1)
+
+
+def _bn_case(gen, N, C, res, relu):
+    key = ("bn", gen, N, C, res, relu)
+    if key not in _cnn_refs:
+        c = U.bn_inputs(gen, N, C, res=res)
+        a = (c["x"], c["gamma"], c["beta"], 1e-5, 0.1, c["rm"], c["rv"], c["res"], relu)
+        r = U.bn_ref(F64, *a, dy=c["dy"])
+        t = U.bn_ref(F32, *a, mask=(r["y"] > 0) if relu else None, dy=c["dy"])   # the mask is an input
+        _cnn_refs[key] = (c, a, r, t)
+    return _cnn_refs[key]
+
+
+CNN_BN_WAYS = ((False, False), (False, True), (True, True), (True, False))   # (residual, relu)
+CNN_BN_FWD = ("y", "running_mean", "running_var")
+CNN_BN_BWD = ("dx", "dgamma", "dbeta")
+
+
+def test_twin_cnn_conv():
+    """every convolution case x generator: the twin under its ceilings on y, dx (implicit GEMM, with
+    the addend) and dw; the strided cases also through linear_dgrad + col2im, where the twin applies
+    the kernels' bf16 roundings and has to stay inside the counted allowance"""
+    J = U.Judge()
+    cases = U.CNN_CONV_IMPLICIT + U.CNN_CONV_STATS + [_wgrad3_as_conv(r) for r in U.CNN_WGRAD3 + U.CNN_WGRAD3_KP128]
+    for gen in U.CNN_GENS:
+        for case in cases + [U.CNN_WGRAD_SPLITK]:
+            c, a, r, t = _conv_case(case, gen)
+            U.judge_conv(J, "conv", (case[0], gen), r, t, {}, pixels=r["y"].numel() // r["y"].shape[-1])
+            if case[7] > 1:
+                rc = U.conv_ref(F64, *a, path="cols")
+                tc = U.conv_ref(F32, *a, path="cols", twin=True)
+                J.within("col2im", (case[0], gen), "dx", None, rc["dx"], tc["dx"], rc["allow_dx"])
+    J.check()
+
+
+def test_twin_cnn_batchnorm_and_fused_statistics():
+    J = U.Judge()
+    for gen in U.CNN_GENS + ("planted",):
+        for N, C in U.CNN_BN + [U.CNN_BN_BIG, U.CNN_BN_MANY]:
+            for res, relu in CNN_BN_WAYS:
+                c, a, r, t = _bn_case(gen, N, C, res, relu)
+                U.judge_bn(J, "bn", (gen, N, C, res, relu), r, t, {}, U.bn_serial_rows(N, C, 1), CNN_BN_FWD, CNN_BN_BWD)
+                assert torch.equal(t["dres"].to(U.BF16), r["dres"].to(U.BF16))   # a masked copy: exact
+    # eval mode: the running statistics as given
+    c, a, r, t = _bn_case("offset", 231, 64, False, True)
+    ev = lambda dt: U.bn_ref(dt, *a, training=False)
+    J.ulp("bn-eval", (231, 64), "y", None, ev(F64)["y"], ev(F32)["y"], U.FLOOR_BN_Y * ev(F64)["S_y"])
+    # the per-tile partials of the epilogue, from the twin's stored y
+    for gen in U.CNN_GENS:
+        for case in U.CNN_CONV_STATS:
+            _, _, r, t = _conv_case(case, gen)
+            if gen == "offset":   # the output channels carry the offset: mean about 8 x the deviation
+                v = r["y"].reshape(-1, case[5])
+                ratio = (v.mean(0) / v.std(0)).abs().median().item()
+                print("offset", case[0], "output mean / std", ratio)
+                assert 7 <= ratio <= 9, ratio
+            y = t["y"].to(U.BF16).reshape(-1, case[5])
+            bm = 256 if case[5] <= 64 else 128
+            sr, st = U.tile_stats_ref(F64, y, bm), U.tile_stats_ref(F32, y, bm)
+            for n in ("mean", "m2"):
+                J.rel("tilestats", (case[0], gen), n, None, sr[n], st[n], sr[n + "_scale"], U.CNN_STATS_ROWS)
+    J.check()
+
+
+def test_twin_cnn_pools():
+    J = U.Judge()
+    for B, H, W, C, k, s, p in U.CNN_POOLS:
+        for gen in ("randn", "planted"):
+            c = U.pool_inputs(gen, B, H, W, C, k, s, p)
+            f = U.maxpool_ref(c["x"], k, s, p)
+            r, t = (U.maxpool_bwd_ref(dt, c["dy"], f["arg"], H, W, k, s, p) for dt in (F64, F32))
+            J.ulp("maxpool", (B, H, W, C, k, s, p, gen), "dx", None, r["dx"], t["dx"], 0.0)
+    B, H, W, C = U.CNN_AVGPOOL
+    g = torch.Generator().manual_seed(5)
+    x, dy = torch.randn(B, H, W, C, generator=g).to(U.BF16), torch.randn(B, C, generator=g).to(U.BF16)
+    r, t = U.avgpool_ref(F64, x, dy), U.avgpool_ref(F32, x, dy)
+    J.ulp("avgpool", U.CNN_AVGPOOL, "y", None, r["y"], t["y"], 0.0)
+    J.ulp("avgpool", U.CNN_AVGPOOL, "dx", None, r["dx"], t["dx"], 0.0)
+    J.check()
+
+
+def test_cnn_references_against_torch_and_each_other():
+    """the tap-loop references equal torch's own convolution / pooling in float64, and the layout
+    formulas are consistent: the 4x4 / 1 / 2 convolution of the space-to-depth image with the
+    rearranged weight IS the 7x7 / 2 / 3 stem, and its weight gradient gathers back"""
+    import torch.nn.functional as Fn
+
+    for case in U.CNN_CONV_IMPLICIT:
+        c, a, r, _ = _conv_case(case)
+        _, B, H, W, C, Co, k, s, p = case
+        xr = c["x"].double().permute(0, 3, 1, 2).requires_grad_(True)
+        wr = c["w"].to(U.BF16).double().requires_grad_(True)
+        y = Fn.conv2d(xr, wr, stride=s, padding=p)
+        y.backward(c["dy"].double().permute(0, 3, 1, 2))
+        for got, ref in ((r["y"], y.permute(0, 2, 3, 1)), (r["dw"], wr.grad),
+                         (r["dx"] - c["addend"].double(), xr.grad.permute(0, 2, 3, 1))):
+            assert (got - ref).abs().max().item() <= 1e-12 * (1 + ref.abs().max().item()), case[0]
+        cols = U.im2col_ref(c["x"], k, k, s, p, k * k * C + 8, B * r["y"].shape[1] * r["y"].shape[2] + 3)
+        unf = Fn.unfold(c["x"].float().permute(0, 3, 1, 2), k, padding=p, stride=s)   # [B, C k k, L], (c, kh, kw)
+        unf = unf.view(B, C, k * k, -1).permute(0, 3, 2, 1).reshape(-1, k * k * C)
+        assert torch.equal(cols[:unf.shape[0], :k * k * C].float(), unf) and not cols[unf.shape[0]:].any()
+        assert not cols[:, k * k * C:].any()
+        if s == 1:   # the stride-1 dgrad is the convolution of dy with the flipped, transposed kernel
+            wm = c["w"].to(U.BF16).permute(0, 2, 3, 1).reshape(Co, -1)
+            wt = U.w_flip_t_ref(wm, Co, k, k, C).view(C, k, k, Co).permute(0, 3, 1, 2)
+            d = U.conv_ref(F64, c["dy"], wt, 1, k - 1 - p)["y"]
+            assert (d + c["addend"].double() - r["dx"]).abs().max().item() <= 1e-12 * r["dx"].abs().max().item()
+    for B, H, W in U.CNN_STEM_S2D:
+        g = torch.Generator().manual_seed(H)
+        x, w = torch.randn(B, 3, H, W, generator=g), torch.randn(64, 3, 7, 7, generator=g) * 0.1
+        wm = w.to(U.BF16).permute(0, 2, 3, 1).reshape(64, 147)
+        dy = torch.randn(B, H // 2, W // 2, 64, generator=g).to(U.BF16)
+        full = U.conv_ref(F64, U.nhwc_bf16_ref(x), w, 2, 3, dy)
+        wp = U.stem_w_s2d_ref(wm).view(64, 4, 4, 16).permute(0, 3, 1, 2)
+        # (pad 2 yields one more output row and column than the stem has: the kernel is handed
+        # Ho = H / 2, Wo = W / 2 and never computes them)
+        dyp = torch.zeros(B, H // 2 + 1, W // 2 + 1, 64, dtype=U.BF16)
+        dyp[:, :-1, :-1] = dy
+        s2d = U.conv_ref(F64, U.s2d_ref(x), wp, 1, 2, dyp)
+        assert (s2d["y"][:, :-1, :-1] - full["y"]).abs().max().item() <= 1e-12
+        dwp = s2d["dw"].permute(0, 2, 3, 1).reshape(64, 256)
+        assert (U.stem_dw_ref(dwp) - full["dw"].permute(0, 2, 3, 1).reshape(64, 147)).abs().max().item() <= 1e-12
+    for B, H, W, C, k, s, p in U.CNN_POOLS:
+        c = U.pool_inputs("planted", B, H, W, C, k, s, p)
+        f = U.maxpool_ref(c["x"], k, s, p)
+        xr = c["x"].double().permute(0, 3, 1, 2).requires_grad_(True)
+        y = Fn.max_pool2d(xr, k, s, p)
+        assert torch.equal(f["y"].double(), y.permute(0, 2, 3, 1))
+
+
+def test_floor_bn_is_the_smallest_power_of_two():
+    """at half of FLOOR_BN_Y the twin leaves its ceiling on the BatchNorm table; at the floor it holds.
+    FLOOR_BN_DX is the smallest power of two at which the twin holds on the CPU and on the device:
+    here it holds at the floor and has left the ceiling at a quarter of it; that the device's twin
+    is over the ceiling at half of it is held by tests/test_cnn_ulp_gpu.py."""
+    for name, S, floor, steps in (("y", "S_y", U.FLOOR_BN_Y, 2), ("dx", "S_dx", U.FLOOR_BN_DX, 4)):
+        at, below = 0.0, 0.0
+        for gen in U.CNN_GENS + ("planted",):
+            for N, C in U.CNN_BN + [U.CNN_BN_BIG, U.CNN_BN_MANY]:
+                for res, relu in CNN_BN_WAYS:
+                    _, _, r, t = _bn_case(gen, N, C, res, relu)
+                    at = max(at, U.ulp_err(t[name], r[name], floor * r[S]))
+                    below = max(below, U.ulp_err(t[name], r[name], floor / steps * r[S]))
+        print(name, "twin at the floor", at, "at 1 /", steps, "of it", below)
+        assert at <= U.TWIN_ULP_CEIL < below, (name, at, below)
+
+
+# mutant -> (the case that shows it, the output it corrupts)
+CNN_CONV_MUTANT_WHERE = {"pad_clamp": ("c64", "y"), "khkw_swapped": ("k5", "y"), "hw_swapped": ("c64", "y"),
+                         "col2im_phase": ("s2", "dx_cols"), "dw_last_row": ("c64", "dw"), "truncate": ("c64", "y"),
+                         "addend_after": ("c64", "dx")}
+_CONV_BY_NAME = {c[0]: c for c in U.CNN_CONV_IMPLICIT}
+
+
+def _conv_mutant_caught(mutant, case, name):
+    c, a, r, t = _conv_case(case)
+    if name == "dx_cols":
+        rc = U.conv_ref(F64, *a, path="cols")
+        m = U.conv_ref(F32, *a, path="cols", twin=True, mutant=mutant)
+        return U.allow_err(m["dx"].to(U.BF16), rc["dx"], rc["allow_dx"]) > 1.0, m["dx"], rc["dx"]
+    m = U.conv_ref(F32, *a, mutant=mutant)
+    if name == "dw":
+        return _rel_caught(m["dw"], r["dw"], t["dw"], r["S_dw"], r["y"].numel() // r["y"].shape[-1]), m["dw"], r["dw"]
+    return _ulp_caught(m[name], r[name], t[name], U.FLOOR_GEMM * r["S_" + name]), m[name], r[name]
+
+
+@pytest.mark.parametrize("mutant", U.CONV_MUTANTS)
+def test_mutant_conv(mutant):
+    case, name = CNN_CONV_MUTANT_WHERE[mutant]
+    assert _conv_mutant_caught(mutant, _CONV_BY_NAME[case], name)[0], mutant
+
+
+CNN_BN_MUTANT_WHERE = {"biased_var": "running_var", "eps": "y", "mask_ge": "dx", "mask_pre_res": "dx",
+                       "dbeta_dropped": "dx", "dres_unmasked": "dres"}
+
+
+def _bn_mutant(mutant, gen="randn", N=231, C=64):
+    c, a, r, t = _bn_case(gen, N, C, True, True)
+    return r, t, U.bn_ref(F32, *a, dy=c["dy"], mutant=mutant)
+
+
+@pytest.mark.parametrize("mutant", U.BN_MUTANTS)
+def test_mutant_batchnorm(mutant):
+    name = CNN_BN_MUTANT_WHERE[mutant]
+    r, t, m = _bn_mutant(mutant)
+    if name == "dres":
+        assert not torch.equal(m["dres"].to(U.BF16), r["dres"].to(U.BF16))
+    elif name == "running_var":
+        assert _rel_caught(m[name], r[name], t[name], r[name + "_scale"], U.bn_serial_rows(231, 64, 1))
+    else:
+        S, fl = ("S_y", U.FLOOR_BN_Y) if name == "y" else ("S_dx", U.FLOOR_BN_DX)
+        assert _ulp_caught(m[name], r[name], t[name], fl * r[S]), mutant
+    if mutant in ("mask_ge", "mask_pre_res"):   # a wrong mask also moves the channel sums
+        for n in ("dbeta", "dgamma"):
+            assert _rel_caught(m[n], r[n], t[n], r[n + "_scale"], U.bn_serial_rows(231, 64, 1)), (mutant, n)
+
+
+def _pool_mutant(mutant, case):
+    B, H, W, C, k, s, p = case
+    c = U.pool_inputs("planted", B, H, W, C, k, s, p)
+    f, m = U.maxpool_ref(c["x"], k, s, p), U.maxpool_ref(c["x"], k, s, p, mutant=mutant)
+    r, t = (U.maxpool_bwd_ref(dt, c["dy"], f["arg"], H, W, k, s, p) for dt in (F64, F32))
+    return f, m, r, t, U.maxpool_bwd_ref(F32, c["dy"], f["arg"], H, W, k, s, p, mutant=mutant)
+
+
+@pytest.mark.parametrize("mutant", U.POOL_MUTANTS)
+def test_mutant_pool(mutant):
+    """on the planted windows: the last maximum is another tap, padding read as zero wins the
+    all-negative border windows, a dropped window at the (odd) border leaves its gradient out"""
+    for case in (U.CNN_POOLS[0], U.CNN_POOLS[1]):
+        f, m, r, t, mb = _pool_mutant(mutant, case)
+        if mutant == "last_argmax":
+            assert not torch.equal(f["arg"], m["arg"])
+        elif mutant == "pad_zero":
+            assert not torch.equal(f["y"].view(torch.int16), m["y"].view(torch.int16))
+        else:
+            assert _ulp_caught(mb["dx"], r["dx"], t["dx"], 0.0)
+
+
+# what `_close` of tests/test_cnn_gpu.py lets through at its tolerances (0.02 y and dw, 0.03 dx, 0.01
+# the BatchNorm sums, 1e-4 the running statistics).  No border mutant passes it on the small shapes
+# of the table (a wrong border pixel is an O(1) error next to the largest magnitude); the two
+# below the line do at the sizes that test itself uses - a 56-row image batch.
+CNN_OLD_ACCEPTS = {("conv", "truncate"), ("conv", "addend_after"), ("bn", "eps"), ("bn", "dbeta_dropped")}
+CNN_OLD_ACCEPTS_LARGE = {("conv", "dw_last_row"), ("bn", "biased_var")}
+
+
+def test_old_yardstick_accepts_cnn_mutants():
+    """the gap this section closes, kept on record; each of these leaves the per-element allowance
+    (test_mutant_conv, test_mutant_batchnorm)"""
+    tol = {"y": 0.02, "dx": 0.03, "dx_cols": 0.03, "dw": 0.02, "running_var": 1e-4, "dres": 0.01}
+    accepted = set()
+    for mutant in U.CONV_MUTANTS:
+        case, name = CNN_CONV_MUTANT_WHERE[mutant]
+        caught, m, r = _conv_mutant_caught(mutant, _CONV_BY_NAME[case], name)
+        ok = U.old_yardstick(m if name == "dw" else m.to(U.BF16), r, tol[name])
+        print("conv", mutant, "old criterion accepts:", ok)
+        if ok:
+            accepted.add(("conv", mutant))
+    for mutant in U.BN_MUTANTS:
+        name = CNN_BN_MUTANT_WHERE[mutant]
+        r, t, m = _bn_mutant(mutant)
+        ok = U.old_yardstick(m[name] if name == "running_var" else m[name].to(U.BF16), r[name].double(), tol[name])
+        print("bn", mutant, "old criterion accepts:", ok)
+        if ok:
+            accepted.add(("bn", mutant))
+    for mutant in U.POOL_MUTANTS:
+        f, m, r, t, mb = _pool_mutant(mutant, U.CNN_POOLS[0])
+        ok = U.old_yardstick(m["y"], f["y"].double(), 1e-6) and U.old_yardstick(mb["dx"].to(U.BF16), r["dx"], 0.01)
+        print("pool", mutant, "old criterion accepts:", ok)
+        if ok and mutant != "last_argmax":   # (the old test never looked at the argmax)
+            accepted.add(("pool", mutant))
+    assert accepted == CNN_OLD_ACCEPTS, accepted
+    # at the old test's own sizes: one dropped pixel row of 12544, the biased variance of 25088 rows
+    large = set()
+    big = ("big", 4, 56, 56, 64, 64, 3, 1, 1)
+    caught, m, r = _conv_mutant_caught("dw_last_row", big, "dw")
+    assert caught
+    if U.old_yardstick(m, r, 0.02):
+        large.add(("conv", "dw_last_row"))
+    _cnn_refs.pop((big, "randn"))
+    r, t, m = _bn_mutant("biased_var", N=8 * 56 * 56, C=64)
+    R = U.bn_serial_rows(8 * 56 * 56, 64, U.bn_blocks(8 * 56 * 56, 64))
+    assert _rel_caught(m["running_var"], r["running_var"], t["running_var"], r["running_var_scale"], R)
+    if U.old_yardstick(m["running_var"], r["running_var"], 1e-4):
+        large.add(("bn", "biased_var"))
+    _cnn_refs.pop(("bn", "randn", 8 * 56 * 56, 64, True, True))
+    assert large == CNN_OLD_ACCEPTS_LARGE, large
+
+
+def test_cnn_grids_meet_every_branch():
+    """the case table reaches every branch the GPU tests name: mirrors of _bn_blocks, the split merge
+    of rtdc_bn_fwd and launch_conv3x3_wgrad"""
+    # BatchNorm at _BN_LOADS = 1 (the GPU tests patch it) and at the default
+    seen = set()
+    for N, C in U.CNN_BN + [U.CNN_BN_BIG, U.CNN_BN_MANY]:
+        seen |= U.bn_reduce_branches(N, C, U.bn_blocks(N, C, 1)) | U.bn_reduce_branches(N, C, U.bn_blocks(N, C))
+    assert seen >= {"apply_hoisted", "apply_generic", "idle_lanes", "second_gbase", "empty_block", "unrolled",
+                    "remainder", "finalize_wraps"}, seen
+    assert U.bn_blocks(*U.CNN_BN_MANY, 1) > 256 and U.bn_blocks(*U.CNN_BN_BIG) >= 2
+    assert {256 % (C // 8) == 0 for _, C in U.CNN_BN} == {True, False}
+    assert all(N % (4 * (256 // min(256, C // 8))) for N, C in U.CNN_BN)
+    # the split merge: 26 tiles of 128 rows -> S = 4 splits of 7, the last one of 5; not without the knob
+    N, C = U.CNN_BN_BIG
+    tiles = -(-N // 128)
+    assert tiles == 26 and U.bn_split(tiles, C, U.bn_blocks(N, C, 1)) == (4, 7) and tiles % 7
+    assert U.bn_split(tiles, C, U.bn_blocks(N, C)) == (4, 7) and U.bn_split(tiles, C, 216, enabled=False) is None
+    assert U.bn_split(2, 64, 1) is None          # the 256-row tiles of st64: the finalize alone
+    st = U.CNN_CONV_STATS[1]
+    assert st[1] * U.out_hw(st[2], st[3], 3, 3, 1, 1)[0] * U.out_hw(st[2], st[3], 3, 3, 1, 1)[1] == N and st[5] == C
+    # conv3x3_wgrad_kernel, B = 3
+    plans = {r[0]: U.conv3_wgrad_plan(3, *r[1:]) for r in U.CNN_WGRAD3}
+    assert plans["img"] == (64, 5, 1, 3, 1)                      # RC = H: the whole image, 35 of 64 pixels
+    assert plans["rows3"][:3] == (64, 3, 6) and 17 % 3           # the last chunk of an image partial
+    assert plans["w33"][:3] == (64, 1, 4) and plans["w64"][:3] == (64, 1, 3)
+    KP, RC, cpi, S, per = plans["uneven"]
+    assert per == 2 and 3 * cpi % per == 1 and S == 35           # chunks split unevenly over the blocks
+    for r in U.CNN_WGRAD3_KP128:
+        assert U.conv3_wgrad_plan(3, *r[1:], kp_env=128)[0] == 128 and U.conv3_wgrad_plan(3, *r[1:])[0] == 64
+    assert U.conv3_wgrad_plan(3, 17, 19, 64, 64, kp_env=128)[0] == 128    # 6 rows of 19 = 114 >= 96
+    assert U.conv3_wgrad_plan(3, 5, 7, 64, 64, kp_env=128)[0] == 64       # 35 pixels: the 3/4 rule refuses
+    # mode 2 of the implicit GEMM: more than four tiles, a window that is not 3x3, a strided 3x3
+    by = _CONV_BY_NAME
+    assert U.conv3_wgrad_plan(by["c192"][1], *by["c192"][2:6]) is None
+    assert by["k5"][6] == 5 and by["s2"][7] == 2
+    # pick_splitk: 37 k-tiles of 64 (padded) pixels under 7 tiles of 64x256 - its time model takes 4 slabs;
+    # no other mode-2 case of the table is long enough to split
+    _, B, H, W, C, Co, k, s, p = U.CNN_WGRAD_SPLITK
+    assert U.pick_splitk(Co, k * k * C, -(-B * H * W // 64) * 64, -(-k * k * C // 256), 64 << 20) == 4
+    for _, B, H, W, C, Co, k, s, p in U.CNN_CONV_IMPLICIT:
+        Ho, Wo = U.out_hw(H, W, k, k, s, p)
+        assert U.pick_splitk(Co, k * k * C, -(-B * Ho * Wo // 64) * 64, 1, 64 << 20) == 1
+    # every shape has H != W
+    for c in U.CNN_CONV_IMPLICIT + U.CNN_CONV_STATS + [U.CNN_WGRAD_SPLITK]:
+        assert c[2] != c[3]
+    assert all(r[1] != r[2] for r in U.CNN_WGRAD3 + U.CNN_WGRAD3_KP128)
+    assert all(c[1] != c[2] for c in U.CNN_POOLS) and all(H != W for _, H, W in U.CNN_STEM_S2D)

@@ -41,6 +41,11 @@ accumulate in fp32 and round every output to bf16 once, split-K included (its sl
   arm reduces the stored C and is judged against the fp64 column sum of the kernel's own C;
 * the case table (GEMM_*) is data shared by tests/test_ulp_cpu.py (twin condition, mutants) and
   tests/test_gemm_ulp_gpu.py (the kernels).
+
+The CNN section (the last) does the same for the ResNet path - cnn.hip, the implicit-GEMM
+convolution modes, conv3x3_wgrad_kernel and the statistics epilogues of gemm_bf16.hip: `conv_ref`,
+`bn_ref` and the pool references, the index formulas of the kernels that only move data, the
+generators (randn, offset, planted) and the CNN_* tables; tests/test_cnn_ulp_gpu.py runs the kernels.
 """
 from __future__ import annotations
 
@@ -1233,3 +1238,545 @@ def judge_gemm(J, op, shape, c, r, t, outs, cs_rows=None, aux_fp32=False):
             st = (C if C is not None else t["C"].to(F32 if c["out_fp32"] else BF16))
             J.rel(op, shape, "colsum*", outs.get("colsum"), st.double().sum(-2), st.float().sum(-2),
                   st.double().abs().sum(-2), gemm_colsum_fallback_rows(c["M"]))
+
+
+# ------------------------------------------------------------------------------- CNN (ResNet path)
+# cnn.hip, the implicit-GEMM convolution modes of rtdc_conv_gemm, conv3x3_wgrad_kernel and the
+# conv_tile_stats / bnb_tile_stats epilogues of gemm_bf16.hip, under the first yardstick where the
+# kernel accumulates in fp32 and rounds once (conv y, implicit dgrad, BatchNorm, pools), and under
+# a per-element allowance where bf16 values are summed (dgrad through linear_dgrad + col2im).
+# No reference here calls a convolution library: windows are explicit tap loops over a padded
+# image and the products are matmuls, so every one runs in float64 on either device.
+# * `conv_ref`: y / dx / dw and S, the sum of |terms| at the leaves;
+# * `bn_ref`: forward (y, mean, var, running statistics) and backward (dx, dgamma, dbeta, dres);
+#   the backward takes the ReLU mask as an input (an element within an fp32 rounding of the
+#   boundary flips dbeta by a whole gradient value: the GPU tests pass `stored y > 0`);
+# * `maxpool_ref` / `maxpool_bwd_ref` / `avgpool_ref`, and the index formulas of the kernels that
+#   only move data (`im2col_ref`, `w_flip_t_ref`, `s2d_ref`, `stem_w_s2d_ref`, `stem_dw_ref`);
+# * the case tables (CNN_*) are data shared by tests/test_ulp_cpu.py and tests/test_cnn_ulp_gpu.py;
+#   every shape has H != W.
+#
+# BatchNorm y = x ka + (beta - mean ka) (+ res), ka = rstd gamma: x ka and mean ka cancel (the
+# `offset` generator puts the channel mean at 8 standard deviations), and y lands near -res.
+# Times S_y = |x ka| + (sum |x| / N) |ka| + |beta| + |res|: the leaves of the kernel's fma, the mean
+# taken at its own leaves (it is a sum of N signed terms).
+FLOOR_BN_Y = 2.0 ** -11
+# BatchNorm dx = gr (g - dbeta / N - xhat dgamma / N), gr = gamma rstd, formed by the kernel as
+# gr g + kB x + (kD - kB mean): g and the two channel means cancel, and so do kB x and kB mean.
+# Times S_dx = |gr| (|g| + sum |g| / N + rstd (|x| + sum |x| / N) sum |g| rstd (|x| + sum |x| / N) / N):
+# the leaves.  The smallest power of two at which the twin holds both as the CPU computes it and as the
+# device does (the GPU tests compute theirs there, with the device's division and square root): at 2^-13
+# the CPU's still passes (0.050 ulp), the device's does not (0.075 at 35 x 2056, planted), and at 2^-14
+# the CPU's has left the ceiling too (0.10).  tests/test_ulp_cpu.py holds the CPU's half of that,
+# tests/test_cnn_ulp_gpu.py::test_floor_bn_dx_on_the_device the device's.
+FLOOR_BN_DX = 2.0 ** -12
+# The pools take no floor (every element is judged in its own last place): max-pool backward adds at
+# most K^2 bf16 values in fp32 - exact but for an exponent spread above 16 bits - and rounds once, the
+# global average adds HW = 35 bf16 values the same way, and its backward is one product.
+
+CONV_MUTANTS = ("pad_clamp", "khkw_swapped", "hw_swapped", "col2im_phase", "dw_last_row", "truncate", "addend_after")
+BN_MUTANTS = ("biased_var", "eps", "mask_ge", "mask_pre_res", "dbeta_dropped", "dres_unmasked")
+POOL_MUTANTS = ("last_argmax", "pad_zero", "bwd_window_dropped")
+# terms a lane adds serially.  Tile statistics (conv_tile_stats): a lane adds its TM <= 4 rows, then
+# the 16-lane tree, then WM <= 8 waves in order.  BatchNorm partial rows (bn_reduce_kernel): see
+# bn_serial_rows.  Weight gradients: one MFMA accumulator takes every pixel of its split serially
+# (gemm_bf16_kernel mode 2: K = the padded pixel count; conv3x3_wgrad_kernel: per x KP pixels), so
+# R = the pixel count, as gemm's R = K.
+CNN_STATS_ROWS = 4 + 8
+
+
+def out_hw(H, W, KH, KW, stride, pad):
+    return (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+
+
+def _windows(x, KH, KW, stride, pad, fill=0.0, clamp=False):
+    """[B, Ho, Wo, KH * KW, C] of an NHWC tensor: tap (kh, kw) of output pixel (ho, wo) is input
+    pixel (ho s - p + kh, wo s - p + kw), `fill` outside the image (clamp: the border pixel)."""
+    B, H, W, C = x.shape
+    Ho, Wo = out_hw(H, W, KH, KW, stride, pad)
+    if clamp:
+        hi = torch.arange(-pad, H + pad, device=x.device).clamp(0, H - 1)
+        wi = torch.arange(-pad, W + pad, device=x.device).clamp(0, W - 1)
+        xp = x[:, hi][:, :, wi]
+    else:
+        xp = torch.full((B, H + 2 * pad, W + 2 * pad, C), fill, dtype=x.dtype, device=x.device)
+        xp[:, pad:pad + H, pad:pad + W] = x
+    taps = [xp[:, kh:kh + stride * (Ho - 1) + 1:stride, kw:kw + stride * (Wo - 1) + 1:stride]
+            for kh in range(KH) for kw in range(KW)]
+    return torch.stack(taps, 3)
+
+
+def _col2im(dcols, B, H, W, C, KH, KW, stride, pad, phase=True):
+    """gather form of col2im_kernel: dx[b, h, w] = sum over taps with (h + p - kh) % s == 0 of
+    dcols[(b, (h + p - kh) / s, (w + p - kw) / s)][(kh, kw)]; returns the [T, B, H, W, C] terms
+    (zero where a tap does not reach).  phase=False drops the `% s` test (a mutant)."""
+    Ho, Wo = out_hw(H, W, KH, KW, stride, pad)
+    dc = dcols.reshape(B, Ho, Wo, KH * KW, C)
+    hh, ww = torch.arange(H, device=dcols.device), torch.arange(W, device=dcols.device)
+    out = []
+    for kh in range(KH):
+        hs = hh + pad - kh
+        okh = (hs >= 0) & (hs // stride < Ho) & ((hs % stride == 0) if phase else True)
+        for kw in range(KW):
+            ws = ww + pad - kw
+            okw = (ws >= 0) & (ws // stride < Wo) & ((ws % stride == 0) if phase else True)
+            v = dc[:, (hs // stride).clamp(0, Ho - 1)][:, :, (ws // stride).clamp(0, Wo - 1)][:, :, :, kh * KW + kw]
+            out.append(v * (okh[:, None] & okw[None, :])[None, :, :, None].to(v.dtype))
+    return torch.stack(out)
+
+
+def conv_ref(dtype, x, w, stride, pad, dy=None, addend=None, mutant="", path="implicit", twin=False):
+    """NHWC convolution x [B, H, W, C] (bf16) * w [Cout, C, KH, KW] (rounded to bf16 here, as the
+    kernels' shadow is), no bias: y [B, Ho, Wo, Cout]; with dy also dw [Cout, C, KH, KW] and dx.
+    S_* = the sum of |terms| at the leaves.  addend: the GradStash tensor, added to dx in fp32 ahead
+    of the single rounding.  path="cols" (float64, no mutant): dx as linear_dgrad + col2im forms it -
+    every column value is stored as bf16 and up to ceil(KH / s) ceil(KW / s) of them are added - with
+    allow_dx, the per-element allowance counted from those roundings; twin=True applies them in
+    `dtype`.  `mutant`: a deliberate error (CONV_MUTANTS)."""
+    assert mutant == "" or mutant in CONV_MUTANTS
+    B, H, W, C = x.shape
+    Cout, _, KH, KW = w.shape
+    Ho, Wo = out_hw(H, W, KH, KW, stride, pad)
+    M, K = B * Ho * Wo, KH * KW * C
+    xs = x.to(dtype)
+    wb = w.to(BF16).to(dtype)
+    if mutant == "khkw_swapped":
+        wb = wb.transpose(2, 3)
+    wm = wb.permute(0, 2, 3, 1).reshape(Cout, K)           # k = (kh KW + kw) C + c
+    cols = _windows(xs, KH, KW, stride, pad, clamp=mutant == "pad_clamp").reshape(M, K)
+    y = cols @ wm.T
+    out = {"S_y": (cols.abs() @ wm.abs().T).view(B, Ho, Wo, Cout)}
+    if mutant == "hw_swapped":
+        y = y.view(B, Wo, Ho, Cout).transpose(1, 2).reshape(M, Cout)
+    if mutant == "truncate":
+        y = _truncate_bf16(y)
+    out["y"] = y.view(B, Ho, Wo, Cout)
+    if dy is None:
+        return out
+    g = dy.to(dtype).reshape(M, Cout)
+    gw = g
+    if mutant == "dw_last_row":
+        gw = g.clone()
+        gw[-1] = 0
+    back = lambda m: m.view(Cout, KH, KW, C).permute(0, 3, 1, 2)
+    out.update(dw=back(gw.T @ cols), S_dw=back(g.abs().T @ cols.abs()))
+    dcols = g @ wm
+    S_dc = g.abs() @ wm.abs()
+    rounded = path == "cols" and twin
+    terms = _col2im(_rb(dcols, rounded), B, H, W, C, KH, KW, stride, pad, phase=mutant != "col2im_phase")
+    dx, S_dx = terms.sum(0), _col2im(S_dc, B, H, W, C, KH, KW, stride, pad).sum(0)
+    if addend is not None:
+        a = addend.to(dtype)
+        S_dx = S_dx + a.abs()
+        dx = _rb(dx, True) + a if mutant == "addend_after" else dx + a
+    out.update(dx=_rb(dx, rounded), S_dx=S_dx)
+    if path == "cols" and dtype == F64 and not twin and not mutant:
+        # a column value is within F(Cout) S of its fp64 value before linear_dgrad stores it as
+        # bf16; col2im adds the stored values (and the addend) in fp32 and rounds the sum once
+        a_col = _stored(dcols, _f32_terms(Cout) * S_dc)
+        A = _col2im(a_col, B, H, W, C, KH, KW, stride, pad)
+        live = _col2im(torch.ones_like(dcols), B, H, W, C, KH, KW, stride, pad)
+        out["allow_dx"] = _stored(dx, (A * live).sum(0) + _f32_terms(KH * KW + 1) * S_dx)
+    return out
+
+
+def bn_serial_rows(N, C, nblk):
+    """terms a thread of bn_reduce_kernel adds serially (its share of a row-block), plus the row
+    lanes and the partials a thread of the finalize adds in order"""
+    cg = C // 8
+    rl = 256 // min(256, cg)
+    R = -(-N // nblk)
+    return -(-R // rl) + rl + -(-nblk // 256)
+
+
+def bn_ref(dtype, x, gamma, beta, eps, momentum, rm, rv, res=None, relu=False, mask=None, dy=None, training=True,
+           mutant=""):
+    """BatchNorm over the rows of x [N, C] (bf16; an NHWC tensor flattened), fp32 gamma / beta and
+    running statistics, in the kernels' form: ka = rstd gamma, y = x ka + (beta - mean ka) (+ res),
+    ReLU.  Returns y, mean, var, running_mean, running_var (unbiased, n / (n - 1)) and their scales;
+    with dy the backward: g = dy where mask (given, or `y > 0` of this forward), dbeta = sum g,
+    dgamma = sum g xhat, dx = gamma rstd (g - dbeta / N - xhat dgamma / N), dres = g.
+    `mutant`: a deliberate error (BN_MUTANTS)."""
+    assert mutant == "" or mutant in BN_MUTANTS
+    N, C = x.shape
+    xs, ga, be = x.to(dtype), gamma.to(dtype), beta.to(dtype)
+    e = torch.tensor(_f32(1e-4 if mutant == "eps" else eps), dtype=dtype, device=x.device)
+    mo = torch.tensor(_f32(momentum), dtype=dtype, device=x.device)
+    out = {}
+    if training:
+        mean = xs.sum(0) / N
+        m2 = ((xs - mean) ** 2).sum(0)
+        var = m2 / N
+        out.update(running_mean=(1 - mo) * rm.to(dtype) + mo * mean,
+                   running_mean_scale=(1 - mo) * rm.to(dtype).abs() + mo * xs.abs().sum(0) / N,
+                   running_var=(1 - mo) * rv.to(dtype) + mo * (var if mutant == "biased_var" else m2 / max(N - 1, 1)),
+                   mean_scale=xs.abs().sum(0) / N)
+        out["running_var_scale"] = (1 - mo) * rv.to(dtype).abs() + mo * m2 / max(N - 1, 1)
+    else:
+        mean, var = rm.to(dtype), rv.to(dtype)
+    # the mean at its leaves: a batch mean is a sum of N signed terms, in error by fp32 roundings of
+    # sum |x| / N however small it comes out itself
+    am = out["mean_scale"] if training else mean.abs()
+    rstd = 1.0 / torch.sqrt(var + e)
+    ka = rstd * ga
+    t0 = xs * ka + (be - mean * ka)
+    t = t0 if res is None else t0 + res.to(dtype)
+    y = t.clamp_min(0) if relu else t
+    S_y = (xs * ka).abs() + am * ka.abs() + be.abs() + (0 if res is None else res.to(dtype).abs())
+    out.update(y=y, mean=mean, var=var, rstd=rstd, S_y=S_y.expand_as(y))
+    if dy is None:
+        return out
+    g = dy.to(dtype)
+    if relu:
+        if mutant == "mask_ge":
+            mk = y >= 0
+        elif mutant == "mask_pre_res":
+            mk = t0 > 0
+        else:
+            mk = (y > 0) if mask is None else mask
+        gm = torch.where(mk, g, torch.zeros_like(g))
+    else:
+        gm = g
+    xhat = (xs - mean) * rstd
+    dbeta, dgamma = gm.sum(0), (gm * xhat).sum(0)
+    gr = ga * rstd
+    dx = gr * (gm - (0 if mutant == "dbeta_dropped" else dbeta / N) - xhat * dgamma / N)
+    # the leaves: dbeta and dgamma are themselves sums of N signed terms, taken with their |terms|
+    sb, sg = gm.abs().sum(0), (gm * rstd).abs().mul(xs.abs() + am).sum(0)
+    S_dx = gr.abs() * (gm.abs() + sb / N + rstd * (xs.abs() + am) * sg / N)
+    out.update(dx=dx, S_dx=S_dx, dbeta=dbeta, dbeta_scale=sb, dgamma=dgamma, dgamma_scale=sg,
+               dres=g if mutant == "dres_unmasked" else gm)
+    return out
+
+
+def tile_stats_ref(dtype, y, bm):
+    """(mean, M2) of every bm-row tile of the stored y [M, C] as conv_tile_stats forms them, and the
+    leaf terms its one-pass form sums: sum |v| / n for the mean, sum v^2 for M2 = Q - S mean"""
+    M, C = y.shape
+    v = y.to(dtype)
+    nt = -(-M // bm)
+    vp = torch.zeros(nt * bm, C, dtype=dtype, device=y.device)
+    vp[:M] = v
+    vp = vp.view(nt, bm, C)
+    n = torch.tensor([min(bm, M - i * bm) for i in range(nt)], dtype=dtype, device=y.device)[:, None]
+    live = (torch.arange(bm, device=y.device)[None, :, None] < n[:, :, None]).to(dtype)
+    mean = vp.sum(1) / n
+    return {"mean": mean, "m2": (((vp - mean[:, None]) * live) ** 2).sum(1), "mean_scale": vp.abs().sum(1) / n,
+            "m2_scale": (vp * vp).sum(1)}
+
+
+def first_max_tap(win, last=False):
+    """index of the first (last: the mutant) maximum along the tap axis 3 of [B, Ho, Wo, T, C]"""
+    T = win.shape[3]
+    idx = torch.arange(T, device=win.device)[None, None, None, :, None].expand_as(win)
+    hit = win == win.amax(3, keepdim=True)
+    if last:
+        return torch.where(hit, idx, torch.full_like(idx, -1)).amax(3)
+    return torch.where(hit, idx, torch.full_like(idx, T)).amin(3)
+
+
+def maxpool_ref(x, k, s, p, mutant=""):
+    """max-pool of an NHWC bf16 tensor: y (the stored bits of the first maximum in (kh, kw) order,
+    the sign of a zero included) and arg, its tap index kh K + kw (uint8); padding never competes"""
+    assert mutant == "" or mutant in POOL_MUTANTS
+    win = _windows(x.double(), k, k, s, p, fill=0.0 if mutant == "pad_zero" else -math.inf)
+    arg = first_max_tap(win, last=mutant == "last_argmax")
+    raw = _windows(x, k, k, s, p, fill=0.0)
+    return {"y": raw.gather(3, arg[:, :, :, None]).squeeze(3), "arg": arg.to(torch.uint8)}
+
+
+def maxpool_bwd_ref(dtype, dy, arg, H, W, k, s, p, mutant=""):
+    """dx[b, h, w] = sum of dy over the windows whose argmax tap is (h, w): at most K^2 values (4 for
+    3x3 / 2), one rounding.  S_dx the sum of their magnitudes."""
+    B, Ho, Wo, C = dy.shape
+    g = dy.to(dtype)
+    if mutant == "bwd_window_dropped":
+        g = g.clone()
+        g[:, Ho - 1, Wo - 1] = 0
+    hot = torch.zeros(B, Ho, Wo, k * k, C, dtype=dtype, device=dy.device)
+    hot.scatter_(3, arg.long()[:, :, :, None], 1.0)
+    cols = lambda v: (hot * v[:, :, :, None]).reshape(B * Ho * Wo, k * k * C)
+    return {"dx": _col2im(cols(g), B, H, W, C, k, k, s, p).sum(0),
+            "S_dx": _col2im(cols(dy.to(dtype).abs()), B, H, W, C, k, k, s, p).sum(0)}
+
+
+def avgpool_ref(dtype, x, dy=None):
+    """global average [B, H, W, C] -> [B, C] (the sum over HW, divided by HW) and its backward dy / HW"""
+    B, C = x.shape[0], x.shape[-1]
+    v = x.to(dtype).reshape(B, -1, C)
+    HW = v.shape[1]
+    out = {"y": v.sum(1) / HW, "S_y": v.abs().sum(1) / HW}
+    if dy is not None:
+        out["dx"] = (dy.to(dtype) / HW)[:, None, :].expand(B, HW, C).reshape(x.shape)
+    return out
+
+
+# -- kernels that only move data: the index formula each must match bit for bit
+def im2col_ref(x, KH, KW, stride, pad, Kp, Mp):
+    """cols [Mp, Kp]: k = (kh KW + kw) C + c, zero for padding taps, for k >= K and for rows M..Mp"""
+    B, H, W, C = x.shape
+    win = _windows(x, KH, KW, stride, pad)
+    M, K = B * win.shape[1] * win.shape[2], KH * KW * C
+    cols = torch.zeros(Mp, Kp, dtype=x.dtype, device=x.device)
+    cols[:M, :K] = win.reshape(M, K)
+    return cols
+
+
+def w_flip_t_ref(wm, Cout, KH, KW, C):
+    """out[c][(kh, kw, co)] = wm[co][(KH - 1 - kh, KW - 1 - kw, c)] (the stride-1 dgrad operand)"""
+    return wm.view(Cout, KH, KW, C).flip(1, 2).permute(3, 1, 2, 0).reshape(C, KH * KW * Cout).contiguous()
+
+
+def nhwc_bf16_ref(x):
+    return x.permute(0, 2, 3, 1).to(BF16).contiguous()
+
+
+def s2d_ref(x):
+    """X'[b][i][j][(2 di + dj) 3 + c] = X[b][c][2 i + di][2 j + dj], channels 12..15 zero"""
+    B, _, H, W = x.shape
+    v = x.view(B, 3, H // 2, 2, W // 2, 2).permute(0, 2, 4, 3, 5, 1).reshape(B, H // 2, W // 2, 12)
+    return torch.cat([v, torch.zeros_like(v[..., :4])], -1).to(BF16).contiguous()
+
+
+def _stem_index():
+    """for k = (a 4 + bb) 16 + q of the 4x4x16 space-to-depth weight: its (kh, kw, c) in the 7x7x3
+    weight, or -1 (q >= 12, or kh / kw = 2 a + di - 1 / 2 bb + dj - 1 = -1)"""
+    idx = torch.full((256,), -1, dtype=torch.int64)
+    for k in range(256):
+        a, bb, q = k >> 6, (k >> 4) & 3, k & 15
+        if q < 12:
+            di, dj, c = q // 6, (q // 3) & 1, q % 3
+            kh, kw = 2 * a + di - 1, 2 * bb + dj - 1
+            if kh >= 0 and kw >= 0:
+                idx[k] = (kh * 7 + kw) * 3 + c
+    return idx
+
+
+def stem_w_s2d_ref(wm):
+    """[Cout, 147] (kh, kw, c) -> [Cout, 256]"""
+    idx = _stem_index().to(wm.device)
+    out = wm[:, idx.clamp_min(0)]
+    return torch.where(idx[None, :] >= 0, out, torch.zeros_like(out))
+
+
+def stem_dw_ref(dwp):
+    """[Cout, 256] -> [Cout, 147]: the inverse gather"""
+    idx = _stem_index()
+    inv = torch.empty(147, dtype=torch.int64)
+    inv[idx[idx >= 0]] = torch.nonzero(idx >= 0)[:, 0]
+    return dwp[:, inv.to(dwp.device)]
+
+
+# -- inputs
+CNN_GENS = ("randn", "offset")
+
+
+def conv_inputs(gen, B, H, W, C, Cout, KH, KW, stride, pad, seed=0, dev="cpu", addend=False):
+    """x, w, dy (and the GradStash addend).  offset: input channel 0 is the constant 4 and reaches
+    every filter through its centre tap alone (never a padding tap) with weight 2, next to K - 9
+    random products of variance 1 / K, so that an OUTPUT channel's mean is 8 x its standard deviation
+    at every pixel, the border included (tests/test_ulp_cpu.py holds the ratio): what the fused
+    statistics of the epilogue then see."""
+    g = torch.Generator().manual_seed(97 * H + 31 * W + 7 * C + Cout + 3 * KH + stride + len(gen) + seed)
+    K = KH * KW * C
+    x = torch.randn(B, H, W, C, generator=g)
+    w = torch.randn(Cout, C, KH, KW, generator=g) * K ** -0.5
+    if gen == "offset":
+        x[..., 0] = 4.0
+        w[:, 0] = 0.0
+        w[:, 0, KH // 2, KW // 2] = 2.0
+    else:
+        assert gen == "randn"
+    Ho, Wo = out_hw(H, W, KH, KW, stride, pad)
+    c = {"x": x.to(BF16), "w": w, "dy": torch.randn(B, Ho, Wo, Cout, generator=g).to(BF16),
+         "addend": torch.randn(B, H, W, C, generator=g).to(BF16) if addend else None}
+    return {k: v.to(dev) if torch.is_tensor(v) else v for k, v in c.items()}
+
+
+def bn_inputs(gen, N, C, seed=0, dev="cpu", res=False):
+    """x [N, C], gamma, beta, running statistics, dy (and a residual).  offset: channel mean = 8 x
+    the channel's standard deviation.  planted: channel 0 constant (variance 0), channel 1 with
+    gamma = 0, channel 2 at magnitude 2^-20."""
+    g = torch.Generator().manual_seed(1013 * C + N + 5 * len(gen) + seed)
+    sd = 0.5 + torch.rand(C, generator=g)
+    x = torch.randn(N, C, generator=g) * sd
+    gamma = 0.5 + torch.rand(C, generator=g)
+    gamma[C // 2:] *= -1          # negative gammas too
+    if gen == "offset":
+        x += 8 * sd
+    elif gen == "planted":
+        x[:, 0] = 1.5
+        gamma[1] = 0.0
+        x[:, 2] *= 2.0 ** -20
+    else:
+        assert gen == "randn"
+    c = {"x": x.to(BF16), "gamma": gamma, "beta": 0.3 * torch.randn(C, generator=g),
+         "rm": 0.1 * torch.randn(C, generator=g), "rv": 0.5 + torch.rand(C, generator=g),
+         "dy": torch.randn(N, C, generator=g).to(BF16),
+         "res": torch.randn(N, C, generator=g).to(BF16) if res else None}
+    return {k: v.to(dev) if torch.is_tensor(v) else v for k, v in c.items()}
+
+
+def pool_inputs(gen, B, H, W, C, k, s, p, seed=0, dev="cpu"):
+    """x [B, H, W, C] and dy.  planted: constant 2x2 and 3x3 patches (ties inside a window), +0 and
+    -0 next to each other in an otherwise negative window, and an all-negative border ring (rows 0
+    and H - 1, columns 0 and W - 1), where padding read as zero would win."""
+    g = torch.Generator().manual_seed(131 * H + 17 * W + C + k + seed)
+    x = torch.randn(B, H, W, C, generator=g)
+    if gen == "planted":
+        x[:, 0] = -x[:, 0].abs() - 0.5
+        x[:, H - 1] = -x[:, H - 1].abs() - 0.5
+        x[:, :, 0] = -x[:, :, 0].abs() - 0.5
+        x[:, :, W - 1] = -x[:, :, W - 1].abs() - 0.5
+        x[:, 1:2, 1:2] = -x[:, 1:2, 1:2].abs() - 0.5          # window (0, 0) of 3x3/2/1 is all negative
+        x[:, 2:4, 2:4] = 3.0                                   # 2x2 tie
+        x[:, H - 5:H - 2, W - 5:W - 2] = 2.5                   # 3x3 tie
+        x[:, 4:7, 0:3] = -x[:, 4:7, 0:3].abs() - 0.5
+        x[:, 5, 1, 0::2] = 0.0
+        x[:, 5, 2, 0::2] = -0.0
+        x[:, 5, 1, 1::2] = -0.0
+        x[:, 5, 2, 1::2] = 0.0
+    else:
+        assert gen == "randn"
+    Ho, Wo = out_hw(H, W, k, k, s, p)
+    return {"x": x.to(BF16).to(dev), "dy": torch.randn(B, Ho, Wo, C, generator=g).to(BF16).to(dev)}
+
+
+# -- the case tables.  Convolutions: (name, B, H, W, C, Cout, KH, stride, pad); every H != W
+CNN_CONV_IMPLICIT = [
+    ("c64", 1, 17, 19, 64, 64, 3, 1, 1),         # 323 pixels: two 256-row tiles, the last partial, M % 8 != 0
+    ("c128", 1, 17, 19, 64, 128, 3, 1, 1),       # 128x128 tiles
+    ("c192", 2, 9, 11, 128, 192, 3, 1, 1),       # partial second column tile, two k-tiles per tap, > 4 wgrad tiles
+    ("s2", 2, 9, 11, 64, 128, 3, 2, 1),          # strided: dgrad through linear_dgrad + col2im
+    ("p1x1s2", 2, 9, 11, 64, 128, 1, 2, 0),      # projection shortcut
+    ("k5", 1, 9, 11, 64, 64, 5, 1, 2),           # 5x5: mode-2 weight gradient
+    ("s2odd", 1, 10, 13, 64, 64, 3, 2, 1),       # stride 2, even / odd size
+]
+# 3x3 / 1 / 1 weight gradients on conv3x3_wgrad_kernel, B = 3: (name, H, W, C, Cout)
+CNN_WGRAD3 = [
+    ("img", 5, 7, 64, 64),        # the whole image in one partial chunk (35 of 64 pixels)
+    ("rows3", 17, 19, 64, 64),    # 3 rows of 19 per chunk, 6 chunks per image, the last partial
+    ("w33", 4, 33, 64, 128),      # one row of 33 of 64 pixels per chunk
+    ("w64", 3, 64, 64, 64),       # one full row per chunk
+    ("uneven", 23, 33, 128, 128),  # four tiles, 69 chunks over 64 splits: two chunks a block, the last one
+]
+CNN_WGRAD3_KP128 = [("w33x3", 5, 33, 64, 64), ("w40x3", 4, 40, 64, 64)]   # 99 and 120 of 128 pixels
+# fused statistics (GM 3): 256-row tiles (323 rows: the last partial) and 128-row tiles (CNN_BN_BIG's rows)
+CNN_CONV_STATS = [("st64", 1, 17, 19, 64, 64, 3, 1, 1), ("st128", 3, 31, 35, 64, 128, 3, 1, 1)]
+CNN_WGRAD_SPLITK =("k5long", 2, 33, 35, 64, 64, 5, 1, 2)               # 2310 pixels: 37 k-tiles, pick_splitk splits
+# BatchNorm: (N, C); N = 3 x 7 x 11 and others that are no multiple of 4 x the row lanes
+CNN_BN = [(231, 64), (231, 192), (77, 512), (35, 2056)]
+CNN_BN_BIG = (3 * 31 * 35, 128)     # 3255 rows: 26 tiles of 128 (S = 4 splits of 7, 7, 7, 5); default nblk = 6
+CNN_BN_MANY = (3255, 192)           # _BN_LOADS = 1: 305 row-blocks of 11 rows, the last 9 empty
+CNN_POOLS = [(2, 9, 12, 64, 3, 2, 1), (2, 10, 7, 64, 3, 2, 1), (2, 9, 12, 128, 3, 2, 1), (2, 10, 7, 128, 3, 2, 1),
+             (2, 10, 12, 64, 2, 2, 0), (1, 9, 12, 128, 2, 2, 0)]
+CNN_AVGPOOL = (3, 5, 7, 512)        # HW = 35
+CNN_STEM_S2D = [(2, 12, 20), (1, 10, 36)]
+CNN_STEM_COLS = [("small", 2, 10, 14), ("stem224", 1, 8, 224)]
+
+
+def conv_case_id(c):
+    return c[0]
+
+
+# -- grid arithmetic of the launchers (mirrors, for the branch-coverage test)
+def bn_blocks(N, C, loads=32):
+    """_bn_blocks of ops/cnn.py"""
+    return max(1, min(2048, (N * C) // (256 * 8 * loads)))
+
+
+def bn_reduce_branches(N, C, nblk):
+    """the paths of bn_reduce_kernel / bn_finalize_kernel / the apply kernels this launch takes"""
+    cg = C // 8
+    R = -(-N // nblk)
+    out = set()
+    grid = max(1, min(16384, -(-(N * cg) // 256)))
+    out.add("apply_hoisted" if (grid * 256) % cg == 0 else "apply_generic")
+    if 256 % min(256, cg) != 0:
+        out.add("idle_lanes")
+    if cg > 256:
+        out.add("second_gbase")
+    for b in range(nblk):
+        n = max(0, min(N, (b + 1) * R) - b * R)
+        if n == 0:
+            out.add("empty_block")
+        rl = 256 // min(256, cg)
+        rows0 = len(range(0, n, rl))           # rows of lane 0
+        if rows0 >= 4:
+            out.add("unrolled")
+        if rows0 % 4 or n % rl:
+            out.add("remainder")
+    if nblk > 256:
+        out.add("finalize_wraps")
+    return out
+
+
+def bn_split(p_nblk, C, nblk, enabled=True):
+    """(S, per) of the split merge of rtdc_bn_fwd, or None where the finalize runs alone"""
+    cg = (C + 63) // 64
+    S = min((512 + cg - 1) // cg, (p_nblk + 7) // 8, nblk)
+    if S < 4 or not enabled:
+        return None
+    per = -(-p_nblk // S)
+    return -(-p_nblk // per), per
+
+
+def conv3_wgrad_plan(B, H, W, Cin, Cout, kp_env=64, ws_elems=1 << 40):
+    """(KP, RC, cpi, S, per) of launch_conv3x3_wgrad, or None where it hands the shape back"""
+    if Cin % 64 or Cout % 64 or W < 1 or W > 64 or H < 1:
+        return None
+    max_halo = {128: (4 * 768 - 128 * 8) // 8, 64: (3 * 768 - 64 * 8) // 8}
+    KP, RC = 128, min(128 // W, H)
+    if kp_env == 64 or RC * W * 4 < 3 * 128 or (RC + 2) * (W + 2) > max_halo[128]:
+        KP, RC = 64, min(64 // W, H)
+    if KP == 64 and (RC + 2) * (W + 2) > max_halo[64]:
+        return None
+    cpi = -(-H // RC)
+    nchunks = B * cpi
+    tiles = (Cout // 64) * (Cin // 64)
+    if tiles > 4:
+        return None
+    S = max(1, min(256 // tiles, nchunks))
+    slab = Cout * 9 * Cin
+    if S > 1 and S * slab > ws_elems:
+        S = max(1, ws_elems // slab)
+    per = -(-nchunks // S)
+    return KP, RC, cpi, -(-nchunks // per), per
+
+
+def pick_splitk(M, N, K, tiles, ws_elems, slots=512, t_ktile_us=1.8):
+    """pick_splitk of gemm_bf16.hip: the slab count of a mode-2 product [M, N] over K (padded) pixels"""
+    ktiles = K // 64
+    if tiles >= 200 or ktiles < 32:
+        return 1
+    slab_us = M * N * 8.0 / 4.0e6
+    best, best_t = 1, 1e30
+    for s in range(1, 1025):
+        if ktiles // s < 8 or s * M * N > ws_elems:
+            break
+        waves = -(-tiles * s // slots)
+        t = waves * -(-ktiles // s) * t_ktile_us + (s * slab_us if s > 1 else 0.0)
+        if t < best_t - 1e-9:
+            best, best_t = s, t
+    return best
+
+
+def judge_conv(J, op, shape, r, t, outs, names=("y", "dx", "dw"), pixels=0):
+    """y and implicit-GEMM dx: Judge.ulp, k = 1, FLOOR_GEMM x S; dw: Judge.rel, R = the pixels"""
+    for n in names:
+        o = outs.get(n)
+        if n == "dw":
+            J.rel(op, shape, n, o, r[n], t[n], r["S_dw"].clamp_min(TINY), pixels)
+        else:
+            J.ulp(op, shape, n, o, r[n], t[n], FLOOR_GEMM * r["S_" + n])
+
+
+def judge_bn(J, op, shape, r, t, outs, R, fwd=("y", "running_mean", "running_var"), bwd=()):
+    for n in fwd + bwd:
+        o = outs.get(n)
+        if n == "y":
+            J.ulp(op, shape, n, o, r[n], t[n], FLOOR_BN_Y * r["S_y"])
+        elif n == "dx":
+            J.ulp(op, shape, n, o, r[n], t[n], FLOOR_BN_DX * r["S_dx"])
+        else:
+            J.rel(op, shape, n, o, r[n], t[n], r[n + "_scale"].clamp_min(TINY), R)

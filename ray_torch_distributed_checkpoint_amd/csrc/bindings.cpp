@@ -44,6 +44,7 @@ int rtdc_xent(const void* logits, void* dlogits, const int64_t* target, float* l
 // (rtdc_adamw, rtdc_sgd: declared with their argument structs in kernels/args.h)
 int rtdc_optim_step_advance(long long* count, hipStream_t st);
 int rtdc_f32_to_bf16(const float* x, void* y, long long n, hipStream_t st);
+int rtdc_bf16_to_f32(const void* x, float* y, long long n, float scale, hipStream_t st);
 int rtdc_f32_to_bf16_t(const float* x, void* y, int R, int C, hipStream_t st);
 int rtdc_bf16_transpose_multi(const void* const* src, void* const* dst, const int* R, const int* C, int n,
                               void* jobs_dev, hipStream_t st);
@@ -543,6 +544,14 @@ static void optim_step_advance(Tensor count) {
 }
 static void f32_to_bf16(Tensor x, Tensor y) {
   check_rc(rtdc_f32_to_bf16(x.data_ptr<float>(), y.data_ptr(), (long long)x.numel(), cur_stream()), "f32_to_bf16");
+}
+// y = float(x) * scale: the widening the gradient reducer applies to a bf16 bucket after its collective
+static void bf16_to_f32(Tensor x, Tensor y, double scale) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(), "bf16_to_f32: contiguous bf16 GPU source");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kFloat && y.is_contiguous() && y.numel() == x.numel(),
+              "bf16_to_f32: contiguous fp32 GPU destination of x.numel()");
+  check_rc(rtdc_bf16_to_f32(x.data_ptr(), y.data_ptr<float>(), (long long)x.numel(), (float)scale, cur_stream()),
+           "bf16_to_f32");
 }
 // dst[i] = src[i]^T for bf16 [R, C] -> [C, R] matrices in one launch; `jobs` is a uint8 device
 // buffer of >= bf16_transpose_jobs_bytes() (the job table, uploaded on the current stream)
@@ -1310,6 +1319,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("skip_ptr") = 0, py::arg("clip_ptr") = 0);
   m.def("optim_step_advance", &optim_step_advance);
   m.def("f32_to_bf16", &f32_to_bf16);
+  m.def("bf16_to_f32", &bf16_to_f32, py::arg("x"), py::arg("y"), py::arg("scale") = 1.0);
   m.def("f32_to_bf16_t", &f32_to_bf16_t);
   m.def("bf16_transpose_multi", &bf16_transpose_multi);
   m.def("bf16_transpose_jobs_bytes", &rtdc_bf16_transpose_jobs_bytes);

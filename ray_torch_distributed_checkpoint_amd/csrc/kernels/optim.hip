@@ -75,20 +75,36 @@ __global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ ch
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const Chunk c = chunks[ci];
     const float decay = c.decay ? (1.f - lr * wd) : 1.f;
+    // One definition of the element update for the vector and the scalar path, with the fused
+    // multiply-adds written out and contraction off (as in adamw_bf16state_kernel below): left to
+    // the compiler, the vector copy became v = fma(b2, v, ((1 - b2) gr) gr) and the scalar copy
+    // v = fma(gr, (1 - b2) gr, b2 v), so a chunk cut at an odd offset changed exp_avg_sq in the
+    // last bit.  The fusions are the ones the vector path compiled to: every element of an
+    // aligned chunk keeps its bits but the last len & 3 (the scalar tail), which now follow them.
+    // Measured against the build before: profiles/optim_aligned_vs_parent.txt.
+    auto upd = [&](float gv, float& pe, float& me, float& ve) {
+#pragma clang fp contract(off)
+      const float gr = gv * gs;
+      me = fmaf(1.f - b1, gr, b1 * me);
+      ve = fmaf(b2, ve, ((1.f - b2) * gr) * gr);
+      const float denom = sqrtf(ve) / bc2_sqrt + eps;
+      pe = fmaf(pe, decay, -(step_size * me / denom));
+    };
+    // 16-B accesses only where both offsets allow them: a chunk cut at an odd offset (a deferred-
+    // tail piece, a ZeRO-1 shard boundary) takes the scalar path, as in the two kernels below
+    const bool vec = (c.start & 3) == 0 && (c.sstart & 3) == 0;
     for (int i = threadIdx.x * 4; i < c.len; i += 256 * 4) {
       const long long o = c.start + i, so = c.sstart + i;
-      if (i + 4 <= c.len) {
+      if (vec && i + 4 <= c.len) {
         f32x4 pp = *(f32x4*)(p + o), gg = *(const f32x4*)(g + o);
         f32x4 mm = *(f32x4*)(m + so), vv = *(f32x4*)(v + so);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float gr = gg[e] * gs;
-          float pe = pp[e] * decay;
-          mm[e] = b1 * mm[e] + (1.f - b1) * gr;
-          vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
-          const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-          pe -= step_size * mm[e] / denom;
+          float pe = pp[e], me = mm[e], ve = vv[e];
+          upd(gg[e], pe, me, ve);
           pp[e] = pe;
+          mm[e] = me;
+          vv[e] = ve;
         }
         *(f32x4*)(p + o) = pp;
         *(f32x4*)(m + so) = mm;
@@ -97,13 +113,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ ch
       } else {
         for (int e = 0; e < 4 && i + e < c.len; ++e) {
           const long long oe = o + e, se = so + e;
-          const float gr = g[oe] * gs;
-          float pe = p[oe] * decay;
-          m[se] = b1 * m[se] + (1.f - b1) * gr;
-          v[se] = b2 * v[se] + (1.f - b2) * gr * gr;
-          const float denom = sqrtf(v[se]) / bc2_sqrt + eps;
-          pe -= step_size * m[se] / denom;
+          float pe = p[oe], me = m[se], ve = v[se];
+          upd(g[oe], pe, me, ve);
           p[oe] = pe;
+          m[se] = me;
+          v[se] = ve;
           if (shadow) shadow[oe] = f2bf(pe);
         }
       }
@@ -226,14 +240,18 @@ __global__ __launch_bounds__(256) void sgd_kernel(const Chunk* __restrict__ chun
   for (int ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const Chunk c = chunks[ci];
     const float w = c.decay ? wd : 0.f;
+    // the fused multiply-adds written out and contraction off, as in the AdamW kernels: left to the
+    // compiler, the vector copy became d = fma(gs, g, w p) and the scalar copy d = fma(w, p, gs g), so
+    // with weight decay a chunk cut at an odd offset changed the last bit.  The fusions are the ones
+    // the vector path compiled to.
     auto upd = [&](float gv, float& pe, float& b) {
-      float d = gv * gs;
-      d += w * pe;
+#pragma clang fp contract(off)
+      float d = fmaf(gs, gv, w * pe);
       if (momentum != 0.f) {
-        b = first ? d : momentum * b + (1.f - dampening) * d;
-        d = nesterov ? d + momentum * b : b;
+        b = first ? d : fmaf(momentum, b, (1.f - dampening) * d);
+        d = nesterov ? fmaf(momentum, b, d) : b;
       }
-      pe -= lr * d;
+      pe = fmaf(-lr, d, pe);
     };
     const bool vec = (c.start & 3) == 0 && (c.sstart & 3) == 0;
     // 4 elements per lane and iteration (16-B loads of p, g and the momentum buffer)

@@ -46,6 +46,11 @@ The CNN section (the last) does the same for the ResNet path - cnn.hip, the impl
 convolution modes, conv3x3_wgrad_kernel and the statistics epilogues of gemm_bf16.hip: `conv_ref`,
 `bn_ref` and the pool references, the index formulas of the kernels that only move data, the
 generators (randn, offset, planted) and the CNN_* tables; tests/test_cnn_ulp_gpu.py runs the kernels.
+
+The optimizer section (the last) does it for optim.hip and the arithmetic of elementwise.hip: `adamw_ref`
+and `sgd_ref` (one step in the kernels' order, every scalar rounded to fp32 as a launcher receives it),
+`optim_inputs` and the chunk tables, `embed_ref` / `embed_bwd_ref`, and the dropout mask from the Philox
+twin of ops/random.py; tests/test_optim_ulp_gpu.py and tests/test_elementwise_ulp_gpu.py run the kernels.
 """
 from __future__ import annotations
 
@@ -1780,3 +1785,357 @@ def judge_bn(J, op, shape, r, t, outs, R, fwd=("y", "running_mean", "running_var
             J.ulp(op, shape, n, o, r[n], t[n], FLOOR_BN_DX * r["S_dx"])
         else:
             J.rel(op, shape, n, o, r[n], t[n], r[n + "_scale"].clamp_min(TINY), R)
+
+
+# ------------------------------------------------------------------------------- optimizers, embedding, dropout
+# optim.hip (adamw_kernel, adamw_bf16state_kernel's parameter, sgd_kernel) and the arithmetic of
+# elementwise.hip (embedding, dropout, ReLU-dropout) under the first yardstick: every output is fp32
+# (or one bf16 rounding of an fp32 value) and a short chain of fp32 operations per element.
+# * `adamw_ref` / `sgd_ref`: ONE step written out in the kernels' order.  Every scalar argument is
+#   rounded to fp32 first, as the launcher receives it (`bc1 = 1 - b1**step` and `bc2_sqrt` as
+#   optim/fused.py computes them, in Python doubles, then rounded); what the kernel derives from
+#   them (grad_scale x coef, 1 - lr wd, lr / bc1, 1 - b1 ...) is computed in `dtype`, so those
+#   roundings are the kernel's error, not the reference's.  They return the new p and state and S,
+#   the sum of |terms| of each: |p decay| + |update| for AdamW's p, |b1 m| + |(1 - b1) gr| for m, v
+#   itself (nothing cancels); SGD is linear in its leaves p, g and buf, so its S is the same chain
+#   over the absolute values.  `normal`: every intermediate is a normal number or exactly zero
+#   (the twin asserts it on the CPU: no result depends on how a device treats denormals).
+# * R, the fp32 roundings of the kernel's chain per output, counted from the statements of
+#   adamw_kernel / sgd_kernel (quoted at OPTIM_R).
+# * `optim_inputs`: p with one exact zero per aligned quad (there the new p is the update itself,
+#   judged in its own last place), g = randn x exp(4 randn) with planted runs of exact zeros and of
+#   +-2^-30 and +-2^-27, where eps = 1e-8 dominates AdamW's denominator.  A multi-step case keeps g
+#   and takes m, v / buf from the kernel's previous launch: m then never cancels (b1 m and
+#   (1 - b1) gr have one sign).  With a fresh gradient every step they cancel on some element of
+#   100 k to 2^-16, and the update there - the whole of p where p = 0 - has that many fewer good
+#   bits in ANY fp32 evaluation, the twin's included: an input condition, not a kernel property.
+# * `embed_ref` / `embed_bwd_ref`, `dropout_keep` (the mask from ops/random.py's Philox twin),
+#   `dropout_ref`, `relu_dropout_ref`.
+ADAMW_MUTANTS = ("eps_inside", "coupled_wd", "decay_flag_ignored", "coef_dropped", "bc_step_off_by_one")
+SGD_MUTANTS = ("nesterov_off", "first_dampened", "wd_after_momentum", "grad_scale_on_wd")
+# `upd` of adamw_kernel, one definition for the scalar and the vector branch, and what precedes it:
+#   gs = grad_scale * clip[1]                                  1
+#   gr = gv * gs                                               1
+#   me = fmaf(1.f - b1, gr, b1 * me)                           3   -> m: 5 with gs, gr
+#   ve = fmaf(b2, ve, ((1.f - b2) * gr) * gr)                  4   -> v: 6 with gs, gr
+#   denom = sqrtf(ve) / bc2_sqrt + eps                         3
+#   decay = 1.f - lr * wd ; step_size = lr / bc1               3
+#   pe = fmaf(pe, decay, -(step_size * me / denom))            3   -> p: 18
+# `upd` of sgd_kernel:
+#   gs ; d = fmaf(gs, gv, w * pe)                              3
+#   b = fmaf(momentum, b, (1.f - dampening) * d)               3   -> buf: 6
+#   d = fmaf(momentum, b, d) ; pe = fmaf(-lr, d, pe)           2   -> p: 8
+# OPTIM_R_TORCH: the same chains in separate torch operations, every product and sum rounded
+# (`_torch_update` of optim/fused.py, whose scalars are Python doubles rounded once by the operation).
+OPTIM_R = {"adamw": {"p": 18, "m": 5, "v": 6}, "sgd": {"p": 8, "buf": 6}}
+OPTIM_R_TORCH = {"adamw": {"p": 21, "m": 6, "v": 7}, "sgd": {"p": 12, "buf": 8}}
+OPTIM_SGD_OPTIONS = [(0.0, 0.0, False, 0.0), (0.9, 0.0, False, 0.05), (0.9, 0.5, False, 0.0), (0.9, 0.0, True, 0.05)]
+OPTIM_LR = 1e-3
+
+
+def _normal(*xs) -> bool:
+    return all(bool(((x == 0) | (x.abs() >= TINY)).all()) for x in xs if x is not None)
+
+
+def _scalars(dtype, dev, *vals, f32=True):
+    return [torch.tensor(_f32(v) if f32 else v, dtype=dtype, device=dev) for v in vals]
+
+
+def adamw_ref(dtype, p, g, m, v, decay_mask, lr, b1, b2, eps, wd, step, grad_scale, coef=None, mutant="",
+              f32_scalars=True):
+    """one AdamW step; m / v may be bf16 (the bf16-state kernel widens what it stored); coef: the clip
+    coefficient the kernel read (None: no clip pointer); f32_scalars=False leaves the scalars the doubles
+    they are (the cross-check against torch.optim in float64)"""
+    dev = p.device
+    t = step + 1 if mutant == "bc_step_off_by_one" else step
+    sd = dtype if f32_scalars else F64   # what is derived from the scalars: in the kernel's fp32, or in doubles
+    lr_, b1_, b2_, eps_, wd_, gsc, cf = _scalars(sd, dev, lr, b1, b2, eps, wd, grad_scale,
+                                                 1.0 if coef is None else coef, f32=f32_scalars)
+    bc1, bc2s = _scalars(sd, dev, 1 - b1 ** t, math.sqrt(1 - b2 ** t), f32=f32_scalars)
+    one = torch.ones((), dtype=sd, device=dev)
+    gs = gsc if mutant == "coef_dropped" else gsc * cf
+    b1_, b2_, eps_, wd_, bc2s, gs, dk, c1, c2, ss, one = (x.to(dtype) for x in (
+        b1_, b2_, eps_, wd_, bc2s, gs, one - lr_ * wd_, one - b1_, one - b2_, lr_ / bc1, one))
+    p_, g_, m_, v_ = (x.to(dtype) for x in (p, g, m, v))
+    mask = torch.ones_like(decay_mask, dtype=torch.bool) if mutant == "decay_flag_ignored" else decay_mask.bool()
+    gr = g_ * gs
+    if mutant == "coupled_wd":   # torch.optim.Adam's L2 term instead of the decoupled decay
+        gr = gr + torch.where(mask, wd_ * p_, torch.zeros_like(p_))
+        decay = one.expand_as(p_)
+    else:
+        decay = torch.where(mask, dk, one)
+    pd = p_ * decay
+    a, b = b1_ * m_, c1 * gr
+    mn = a + b
+    c, d1 = b2_ * v_, c2 * gr
+    d = d1 * gr
+    vn = c + d
+    rt = vn.sqrt()
+    q = rt / bc2s
+    denom = (rt + eps_) / bc2s if mutant == "eps_inside" else q + eps_
+    num = ss * mn
+    upd = num / denom
+    pn = pd - upd
+    return {"p": pn, "m": mn, "v": vn, "S_p": pd.abs() + upd.abs(), "S_m": a.abs() + b.abs(), "S_v": vn,
+            "normal": _normal(gr, pd, a, b, mn, c, d1, d, vn, rt, q, denom, num, upd, pn)}
+
+
+def sgd_ref(dtype, p, g, buf, decay_mask, lr, momentum, dampening, wd, nesterov, first, grad_scale, coef=None,
+            mutant="", f32_scalars=True):
+    """one SGD step (the comment above sgd_kernel); buf is None and stays None when momentum == 0"""
+    dev = p.device
+    sd = dtype if f32_scalars else F64
+    lr_, mom, damp, wd_, gsc, cf = _scalars(sd, dev, lr, momentum, dampening, wd, grad_scale,
+                                            1.0 if coef is None else coef, f32=f32_scalars)
+    one = torch.ones((), dtype=sd, device=dev)
+    lr_, mom, wd_, gs, undamp = (x.to(dtype) for x in (lr_, mom, wd_, gsc * cf, one - damp))
+    p_, g_ = p.to(dtype), g.to(dtype)
+    w = torch.where(decay_mask.bool(), wd_, torch.zeros((), dtype=dtype, device=dev))
+    d0 = g_ * gs
+    wp = w * p_ * gs if mutant == "grad_scale_on_wd" else w * p_
+    seen = [d0, wp]
+
+    def chain(d0, wp, b0):
+        late = mutant == "wd_after_momentum"
+        d = d0 if late else d0 + wp
+        b = None
+        if momentum != 0:
+            if first:
+                b = undamp * d if mutant == "first_dampened" else d
+            else:
+                x, y = mom * b0, undamp * d
+                b = x + y
+                seen.extend((x, y))
+            if nesterov and mutant != "nesterov_off":
+                z = mom * b
+                seen.append(z)
+                d = d + z
+            else:
+                d = b
+            seen.append(b)
+        if late:
+            d = d + wp
+        e = lr_ * d
+        seen.extend((d, e))
+        return b, e
+
+    b0 = None if (momentum == 0 or first) else buf.to(dtype)
+    bn, e = chain(d0, wp, b0)
+    values = list(seen)
+    bS, eS = chain(d0.abs(), wp.abs(), None if b0 is None else b0.abs())
+    pn = p_ - e
+    return {"p": pn, "buf": bn, "S_p": p_.abs() + eS, "S_buf": bS, "normal": _normal(pn, *values)}
+
+
+def optim_planted(n, dev="cpu"):
+    """(zeros, 2^-30, 2^-27) masks of the planted gradient runs: five elements each in every 97 (a
+    prime period, so the runs meet every alignment and every chunk of a table)"""
+    r = torch.arange(n, device=dev) % 97
+    return r < 5, (r >= 30) & (r < 35), (r >= 60) & (r < 65)
+
+
+def optim_inputs(n, seed=0, state=None, dev="cpu"):
+    """p, g (fp32) and the state: zeros (first step) or `state`, the kernel's own previous output
+    ({"m", "v"} or {"buf"}), taken as it is"""
+    gen = torch.Generator().manual_seed(1000 + seed)
+    p = torch.randn(n, generator=gen)
+    g = torch.randn(n, generator=gen) * torch.exp(4 * torch.randn(n, generator=gen))
+    i = torch.arange(n)
+    p[(i & 3) == ((i >> 2) & 3)] = 0.0   # one exact zero per aligned quad, on every lane in turn
+    sign = torch.where((i & 1) == 0, 1.0, -1.0)
+    z, s30, s27 = optim_planted(n)
+    g[z] = 0.0
+    g[s30] = sign[s30] * 2.0 ** -30
+    g[s27] = sign[s27] * 2.0 ** -27
+    c = {"p": p.to(dev), "g": g.to(dev)}
+    for k in ("m", "v", "buf"):
+        c[k] = torch.zeros(n, device=dev) if state is None or k not in state else state[k]
+    return c
+
+
+OPTIM_LENS = (1, 3, 4, 5, 7, 63, 64, 65, 1027)
+
+
+def optim_table_rows():
+    """the chunk table of tests/test_optim_ulp_gpu.py as [(start, len, sstart, decay)], and the elements it
+    spans: aligned starts, odd-offset pieces, the compact state layout, a full chunk and one of 16384 - 3,
+    mixed decay flags, gaps between the chunks"""
+    rows, at = [], 0
+
+    def add(s, ln, so):
+        rows.append((s, ln, so, (len(rows) * 5 // 3) % 2))
+
+    for ln in OPTIM_LENS:
+        add(at, ln, at)
+        at += (ln + 63) // 64 * 64
+    for off in (1, 2, 3, 5, 6, 7):   # what chunk_table_splits emits: a piece that starts anywhere
+        for ln in (1, 3, 4, 5, 64, 1027 - off):
+            add(at + off, ln, at + off)
+            at += 1152
+    # the state of these lives elsewhere (ZeRO-1: shards back to back); (20000, 1922): `vec` false through
+    # sstart alone; (24002, 2180): through start alone
+    for s, ln, so in ((4096, 1027, 0), (8192 + 64, 65, 1088), (12288, 7, 1216), (16384, 640, 1280),
+                      (20000, 256, 1922), (24002, 256, 2180)):
+        add(at + s, ln, at + so)
+    at += 24320
+    add(at, 16384, at)
+    at += 16384 + 64
+    add(at, 16384 - 3, at)
+    return rows, at + 16384
+
+
+def optim_many_rows():
+    """5000 chunks: more than the 4096 blocks the grid is capped at"""
+    lens = [8, 5, 64, 3]
+    return [(64 * i, lens[i % 4], 64 * i, int(i % 3 == 0)) for i in range(5000)], 64 * 5000
+
+
+def optim_rows_index(rows, n_p, n_s):
+    """(flat p / g / shadow indices, state indices, decay flag) of every element of the table, in table
+    order; checks first that the chunks lie inside the buffers and do not overlap"""
+    pi, si, dm = [], [], []
+    for s, ln, so, d in rows:
+        assert ln > 0 and 0 <= s and s + ln <= n_p and 0 <= so and so + ln <= n_s, (s, ln, so)
+        pi.append(torch.arange(s, s + ln))
+        si.append(torch.arange(so, so + ln))
+        dm.append(torch.full((ln,), bool(d)))
+    pi, si, dm = torch.cat(pi), torch.cat(si), torch.cat(dm)
+    assert pi.unique().numel() == pi.numel() and si.unique().numel() == si.numel()
+    return pi, si, dm
+
+
+OPTIM_CLASS_SHAPES = [(64, 33), (7,), (1027,), (3, 5, 9), (16384 + 5,)]
+OPTIM_CLASS_MAX_NORM = 0.5
+
+
+def optim_class_inputs(seed=0):
+    """flat p and g for the parameters of OPTIM_CLASS_SHAPES (the FusedAdamW / FusedSGD tests): p is
+    optim_inputs', g is randn x exp(1.5 randn) with only the zero runs planted.  Not optim_inputs' g: with
+    max_grad_norm = 0.5 the clip coefficient is max_norm / |g|, and exp(4 randn) puts the norm near 1e8, so
+    the 2^-30 run times a coefficient of 5e-9 squares to 2^-115 and (1 - b2) times that is a denormal - the
+    twin condition (every intermediate normal or zero) cannot hold.  Here the norm is about 1e3 and every
+    gr^2 stays above 1e-30; tests/test_ulp_cpu.py holds the twin conditions on these inputs too."""
+    total = sum(math.prod(s) for s in OPTIM_CLASS_SHAPES)
+    gen = torch.Generator().manual_seed(seed)
+    g = torch.randn(total, generator=gen) * torch.exp(1.5 * torch.randn(total, generator=gen))
+    g[optim_planted(total)[0]] = 0.0
+    return {"p": optim_inputs(total, seed)["p"], "g": g}
+
+
+def optim_class_grad_factor(k):
+    """the gradient of step k is g times this: one sign on every step (see the head of this section)"""
+    return 1.0 + 0.5 * k
+
+
+def judge_adamw(J, shape, r, t, outs, names=("p", "m", "v"), R=OPTIM_R):
+    """r, t: adamw_ref in float64 / float32 over the elements judged; R: OPTIM_R, counted from `upd` of
+    adamw_kernel (OPTIM_R_TORCH for the CPU path)"""
+    for n in names:
+        J.rel("adamw", shape, n, outs.get(n), r[n], t[n], r["S_" + n].clamp_min(TINY), R["adamw"][n])
+
+
+def judge_sgd(J, shape, r, t, outs, R=OPTIM_R):
+    """R: OPTIM_R, counted from `upd` of sgd_kernel; no buffer without momentum"""
+    for n in ("p", "buf"):
+        if r[n] is not None:
+            J.rel("sgd", shape, n, outs.get(n), r[n], t[n], r["S_" + n].clamp_min(TINY), R["sgd"][n])
+
+
+# -- embedding
+EMBED_WIDTHS = (8, 128, 520, 1024)   # 1 lane of 64 busy; 16; the column loop twice (8 lanes the second time); twice, full
+EMBED_BT = ((1, 1), (3, 5), (2, 37))
+EMBED_V = 50
+
+
+def embed_inputs(B, T, D, seed=0, dev="cpu"):
+    gen = torch.Generator().manual_seed(2000 + seed)
+    idx = torch.randint(0, EMBED_V, (B, T), generator=gen)
+    flat = idx.view(-1)
+    flat[0] = EMBED_V - 1
+    flat[-1] = 0 if flat.numel() > 1 else EMBED_V - 1
+    wte = torch.randn(EMBED_V, D, generator=gen).to(BF16)
+    wpe = torch.randn(T, D, generator=gen).to(BF16)
+    return {"idx": idx.to(dev), "wte": wte.to(dev), "wpe": wpe.to(dev)}
+
+
+def embed_ref(dtype, idx, wte, wpe, T):
+    """out[t] = wte[idx[t]] + wpe[t % T] over the flattened tokens"""
+    flat = idx.reshape(-1)
+    out = wte.to(dtype)[flat]
+    if wpe is not None:
+        out = out + wpe.to(dtype)[torch.arange(flat.numel(), device=flat.device) % T]
+    return out
+
+
+def embed_bwd_inputs(D, distinct, seed=0, dev="cpu"):
+    """B = 2, T = 64: ids from 7 values (runs of about 18 that cross the 4-token blocks), or all distinct;
+    V = 160 rows, so most rows are used by no token"""
+    B, T, V = 2, 64, 160
+    gen = torch.Generator().manual_seed(3000 + seed)
+    if distinct:
+        idx = torch.randperm(V, generator=gen)[:B * T].view(B, T)
+    else:
+        idx = torch.tensor([3, 17, 18, 64, 100, 158, 159])[torch.randint(0, 7, (B, T), generator=gen)]
+    dout = torch.randn(B, T, D, generator=gen).to(BF16)
+    dwte0 = torch.randn(V, D, generator=gen)
+    dwpe0 = torch.randn(T, D, generator=gen)
+    return {"idx": idx.to(dev), "dout": dout.to(dev), "dwte0": dwte0.to(dev), "dwpe0": dwpe0.to(dev), "V": V}
+
+
+def embed_bwd_ref(dtype, idx, dout, dwte0, dwpe0, acc_wte, acc_wpe):
+    """dwte (+)= index_add of dout rows by token id, dwpe (+)= sum over the batch; S: the sum of |terms|,
+    the prior content included; `used`: the rows some token uses; `run`: the longest run of one id"""
+    B, T = idx.shape
+    V, D = dwte0.shape
+    flat = idx.reshape(-1)
+    do = dout.to(dtype).reshape(B * T, D)
+    zero = torch.zeros(V, D, dtype=dtype, device=dout.device)
+    dwte, S_wte = zero.index_add(0, flat, do), zero.index_add(0, flat, do.abs())
+    dwpe, S_wpe = do.view(B, T, D).sum(0), do.abs().view(B, T, D).sum(0)
+    if acc_wte:
+        dwte, S_wte = dwte + dwte0.to(dtype), S_wte + dwte0.to(dtype).abs()
+    if acc_wpe:
+        dwpe, S_wpe = dwpe + dwpe0.to(dtype), S_wpe + dwpe0.to(dtype).abs()
+    count = torch.bincount(flat, minlength=V)
+    return {"dwte": dwte, "dwpe": dwpe, "S_dwte": S_wte, "S_dwpe": S_wpe, "used": count > 0, "run": int(count.max())}
+
+
+# -- dropout
+DROPOUT_SIZES = (1, 3, 5, 1027, 8192 * 1024 + 5)   # the last: the grid is capped at 8192 blocks, a second sweep
+_keep_words: dict = {}
+
+
+def dropout_words(seed, counter, n):
+    """the uint32 word of each of n elements: element 4 q + e takes word e of
+    philox4x32(seed, 0, counter + q); cached (int64 tensor on the CPU)"""
+    import numpy as np
+
+    from ray_torch_distributed_checkpoint_amd.ops.random import philox4x32
+
+    key = (seed, counter, n)
+    if key not in _keep_words:
+        q = np.arange((n + 3) // 4, dtype=np.uint64) + np.uint64(counter)
+        _keep_words.clear()   # (one at a time: the large case holds 8.4 M words)
+        _keep_words[key] = torch.from_numpy(philox4x32(seed, 0, q).reshape(-1)[:n].astype(np.int64))
+    return _keep_words[key]
+
+
+def dropout_keep(seed, counter, n, p):
+    """keep = (r >> 8) * 2^-24 >= float32(p): both sides exact in float64"""
+    return (dropout_words(seed, counter, n) >> 8).double() * 2.0 ** -24 >= _f32(p)
+
+
+def dropout_ref(dtype, x, keep, p):
+    """y = keep ? x / (1 - p) : 0, p the fp32 number the kernel holds (the kernel multiplies by 1.f / (1.f - p))"""
+    one, p_ = _scalars(dtype, x.device, 1.0, p)
+    xs = x.to(dtype)
+    y = xs * (one / (one - p_)) if dtype == F32 else xs / (one - p_)
+    return torch.where(keep, y, torch.zeros_like(y))
+
+
+def relu_dropout_ref(dtype, h, keep, p, dy=None):
+    """forward (dy None): h m; backward: dy m; m = (keep and h > 0) ? 1 / (1 - p) : 0, and 1 at p = 0"""
+    one, p_ = _scalars(dtype, h.device, 1.0, p)
+    scale = one / (one - p_) if p > 0 else one
+    src = (h if dy is None else dy).to(dtype)
+    return torch.where(keep & (h > 0), src * scale, torch.zeros_like(src))

@@ -68,10 +68,9 @@ def main():
         ws = torch.empty(_bwd_ws_elems(nw, D2), device=dev)
         dg, db, dxs = (torch.empty(D2, device=dev) for _ in range(3))
         if rms:
-            fn = lambda: ext.rmsnorm_bwd(dy, x2, g2, rstd, dres, dx, ws, dg, None, nw, False)  # noqa: E731
+            fn = lambda: ext.rmsnorm_bwd(dy, x2, g2, rstd, dres, dx, ws, dg, nw)  # noqa: E731
         else:
-            fn = lambda: ext.layernorm_bwd(dy, x2, g2, mean, rstd, dres, dx, ws, dg, db, dxs, nw, False,  # noqa: E731
-                                           False)
+            fn = lambda: ext.layernorm_bwd(dy, x2, g2, mean, rstd, dres, dx, ws, dg, db, dxs, nw, False)  # noqa: E731
         us = timeit(fn)
         print(json.dumps({"bwd": name, "M": M2, "D": D2, "us": round(us, 1),
                           "TBps": round(4 * M2 * D2 * 2 / us / 1e6, 2)}), flush=True)

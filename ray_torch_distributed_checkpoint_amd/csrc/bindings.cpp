@@ -29,10 +29,9 @@ int rtdc_rmsnorm_fwd(const void* x, const void* g, void* y, float* rstd, int M, 
                      hipStream_t st);
 int rtdc_layernorm_bwd(const void* dy, const void* x, const void* g, const float* mean, const float* rstd,
                        const void* dres, void* dx, float* ws, float* dg, float* db, float* dxsum, int M, int D,
-                       int nwaves, int accumulate, hipStream_t st, int* nblk_out);
+                       int nwaves, hipStream_t st, int* nblk_out);
 int rtdc_rmsnorm_bwd(const void* dy, const void* x, const void* g, const float* rstd, const void* dres,
-                     void* dx, float* ws, float* dg, float* dxsum, int M, int D, int nwaves, int accumulate,
-                     hipStream_t st);
+                     void* dx, float* ws, float* dg, int M, int D, int nwaves, hipStream_t st);
 int rtdc_colsum(const void* X, int M, int N, int ld, float* ws, int nblk, float* out, int accumulate,
                 int is_bf16, hipStream_t st);
 int rtdc_colsum_partial(const void* X, int M, int N, int ld, float* ws, int nblk, int is_bf16, hipStream_t st);
@@ -302,7 +301,7 @@ static void rmsnorm_fwd(Tensor x, Tensor g, Tensor y, Tensor rstd, double eps) {
 // dbeta, colsum(dx)); returns nblk, and the caller reduces them later (colsum_multi).  Else 0.
 static int64_t layernorm_bwd(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor rstd, c10::optional<Tensor> dres,
                              Tensor dx, Tensor ws, Tensor dg, Tensor db, c10::optional<Tensor> dxsum, int64_t nwaves,
-                             bool accumulate, bool defer) {
+                             bool defer) {
   const int D = (int)x.size(-1), M = (int)(x.numel() / D);
   const int nz = 2 + (dxsum.has_value() ? 1 : 0);
   TORCH_CHECK(ws.numel() >= nz * (nwaves / 4 + 64) * D, "layernorm_bwd workspace too small");
@@ -311,19 +310,17 @@ static int64_t layernorm_bwd(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor 
   check_rc(rtdc_layernorm_bwd(dy.data_ptr(), x.data_ptr(), g.data_ptr(), mean.data_ptr<float>(),
                               rstd.data_ptr<float>(), ptr_or_null(dres), dx.data_ptr(), ws.data_ptr<float>(),
                               dg.data_ptr<float>(), db.data_ptr<float>(), (float*)ptr_or_null(dxsum), M, D,
-                              (int)nwaves, accumulate, cur_stream(), defer ? &nblk : nullptr),
+                              (int)nwaves, cur_stream(), defer ? &nblk : nullptr),
            "layernorm_bwd");
   return defer ? nblk : 0;
 }
 static void rmsnorm_bwd(Tensor dy, Tensor x, Tensor g, Tensor rstd, c10::optional<Tensor> dres, Tensor dx,
-                        Tensor ws, Tensor dg, c10::optional<Tensor> dxsum, int64_t nwaves, bool accumulate) {
+                        Tensor ws, Tensor dg, int64_t nwaves) {
   const int D = (int)x.size(-1), M = (int)(x.numel() / D);
-  const int nz = 1 + (dxsum.has_value() ? 1 : 0);
-  TORCH_CHECK(ws.numel() >= nz * (nwaves / 4 + 64) * D, "rmsnorm_bwd workspace too small");
-  if (dxsum.has_value()) TORCH_CHECK(dxsum->numel() >= D && dxsum->scalar_type() == at::kFloat, "dxsum: fp32 [D]");
+  TORCH_CHECK(ws.numel() >= (nwaves / 4 + 64) * D, "rmsnorm_bwd workspace too small");
   check_rc(rtdc_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), g.data_ptr(), rstd.data_ptr<float>(), ptr_or_null(dres),
-                            dx.data_ptr(), ws.data_ptr<float>(), dg.data_ptr<float>(), (float*)ptr_or_null(dxsum), M,
-                            D, (int)nwaves, accumulate, cur_stream()),
+                            dx.data_ptr(), ws.data_ptr<float>(), dg.data_ptr<float>(), M, D, (int)nwaves,
+                            cur_stream()),
            "rmsnorm_bwd");
 }
 static void colsum_partial(Tensor X, int64_t M, int64_t N, int64_t ld, Tensor ws, int64_t nblk) {

@@ -94,51 +94,87 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const bf16_t* __restrict_
   }
 }
 
+// A lane's chunk of VW bf16: 16 B (VW = 8) or 8 B (VW = 4), as the backward kernel loads, unpacks
+// and stores it.  The 16-B chunk goes in by reference and through unpack8bf, the 8-B one by value:
+// the kernel's row loop is compiled with floating-point contraction on, which multiply-adds the
+// compiler fuses there follows details like these, and the bits of dx and of its column sums
+// follow the fusing (profiles/norm_bwd_merge.md: a by-value 16-B chunk changed them at D >= 2048).
+template <int VW>
+struct BfChunk;
+template <>
+struct BfChunk<8> {
+  using raw = uint4;
+  static __device__ __forceinline__ void unpack(const uint4& q, float* v) {
+    unpack8bf(u32x4{q.x, q.y, q.z, q.w}, v);
+  }
+  static __device__ __forceinline__ void store(bf16_t* p, const float* v) { st8(p, v); }
+};
+template <>
+struct BfChunk<4> {
+  using raw = uint2;
+  static __device__ __forceinline__ void unpack(uint2 q, float* v) {
+    v[0] = __uint_as_float(q.x << 16);
+    v[1] = __uint_as_float(q.x & 0xffff0000u);
+    v[2] = __uint_as_float(q.y << 16);
+    v[3] = __uint_as_float(q.y & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void store(bf16_t* p, const float* v) {
+    *(uint2*)p = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+  }
+};
+
 // dxhat = dy*g ; dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat*xhat))   (LayerNorm)
 // dx = rstd * (dxhat - xhat * mean(dxhat*xhat))                                  (RMSNorm)
 // CS: also the column sums of dx itself (the residual-stream gradient this kernel produces is
 // the output gradient of the block's residual projection, whose bias gradient is exactly that
 // colsum - computed here on the way out instead of re-reading dx in a separate reduction).
 // Partial rows per block: ws_dg [nblk][D], ws_db = ws_dg + nblk*D, ws_cs = ws_db + nblk*D.
-template <int CPL, bool RMS, bool CS>
+// VW: elements per lane chunk.  8 (16-B chunks) for every width; 4 (8-B chunks) for widths whose
+// 16-B chunk count is not a multiple of 64 (GPT-2: D = 768 -> 96 chunks of 8, so the 16-B form
+// leaves half the lanes idle in its second chunk and carries [2][8] accumulators; 192 chunks of
+// 4 = 3 per lane, every lane busy, [3][4] accumulators: fewer VGPRs, more waves per SIMD for this
+// latency-bound stream).  Same math, same per-block partial rows.
+template <int VW, int CPL, bool RMS, bool CS>
 __global__ __launch_bounds__(256) void norm_bwd_kernel(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
     const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx, float* __restrict__ ws_dg,
     float* __restrict__ ws_db, float* __restrict__ ws_cs, int M, int D) {
+  using Chunk = BfChunk<VW>;
+  using raw_t = typename Chunk::raw;
   const int lane = threadIdx.x & 63;
   const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nw = gridDim.x * 4;
-  const int nch = D >> 3;
-  float adg[CPL][8], adb[CPL][8], acs[CS ? CPL : 1][8];
+  const int nch = D >> (VW == 8 ? 3 : 2);
+  float adg[CPL][VW], adb[CPL][VW], acs[CS ? CPL : 1][VW];
 #pragma unroll
   for (int i = 0; i < CPL; ++i)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) adg[i][e] = adb[i][e] = 0.f;
+    for (int e = 0; e < VW; ++e) adg[i][e] = adb[i][e] = 0.f;
 #pragma unroll
   for (int i = 0; i < (CS ? CPL : 1); ++i)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) acs[i][e] = 0.f;
+    for (int e = 0; e < VW; ++e) acs[i][e] = 0.f;
 
-  float gg[CPL][8];
+  float gg[CPL][VW];
 #pragma unroll
   for (int i = 0; i < CPL; ++i) {
     const int c = lane + 64 * i;
-    if (c < nch) ld8(g + c * 8, gg[i]);
+    if (c < nch) Chunk::unpack(*(const raw_t*)(g + c * VW), gg[i]);
   }
 
   // rows are software-pipelined: the next row's x / dy / dres (and its statistics) are in
   // flight while this row is reduced and written (a wave owns M/nw rows in sequence)
-  uint4 px[CPL], pd[CPL], pr[CPL];
+  raw_t px[CPL], pd[CPL], pr[CPL];
   float pmean = 0.f, prstd = 0.f;
   auto fetch = [&](int r) {
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
       const int c = lane + 64 * i;
       if (c < nch) {
-        px[i] = *(const uint4*)(x + (long long)r * D + c * 8);
-        pd[i] = *(const uint4*)(dy + (long long)r * D + c * 8);
-        if (dres) pr[i] = *(const uint4*)(dres + (long long)r * D + c * 8);
+        px[i] = *(const raw_t*)(x + (long long)r * D + c * VW);
+        pd[i] = *(const raw_t*)(dy + (long long)r * D + c * VW);
+        if (dres) pr[i] = *(const raw_t*)(dres + (long long)r * D + c * VW);
       }
     }
     pmean = RMS ? 0.f : mean_in[r];
@@ -148,7 +184,7 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(
   for (int row = gw; row < M; row += nw) {
     const float mean = pmean;
     const float rstd = prstd;
-    uint4 cx[CPL], cd[CPL], rraw[CPL];
+    raw_t cx[CPL], cd[CPL], rraw[CPL];
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
       cx[i] = px[i];
@@ -156,17 +192,17 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(
       rraw[i] = pr[i];
     }
     if (row + nw < M) fetch(row + nw);
-    float xh[CPL][8], dxh[CPL][8];
+    float xh[CPL][VW], dxh[CPL][VW];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
       const int c = lane + 64 * i;
       if (c < nch) {
-        float xv[8], dv[8];
-        unpack8bf(u32x4{cx[i].x, cx[i].y, cx[i].z, cx[i].w}, xv);
-        unpack8bf(u32x4{cd[i].x, cd[i].y, cd[i].z, cd[i].w}, dv);
+        float xv[VW], dv[VW];
+        Chunk::unpack(cx[i], xv);
+        Chunk::unpack(cd[i], dv);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < VW; ++e) {
           xh[i][e] = (xv[e] - mean) * rstd;
           dxh[i][e] = dv[e] * gg[i][e];
           s1 += dxh[i][e];
@@ -183,22 +219,15 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(
     for (int i = 0; i < CPL; ++i) {
       const int c = lane + 64 * i;
       if (c < nch) {
-        float o[8], r[8];
-        if (dres) {
-          const uint32_t w[4] = {rraw[i].x, rraw[i].y, rraw[i].z, rraw[i].w};
+        float o[VW], r[VW];
+        if (dres) Chunk::unpack(rraw[i], r);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            r[2 * k] = __uint_as_float(w[k] << 16);
-            r[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < VW; ++e) {
           o[e] = rstd * (dxh[i][e] - m1 - xh[i][e] * m2);
           if (dres) o[e] += r[e];
           if constexpr (CS) acs[i][e] += o[e];
         }
-        st8(dxr + c * 8, o);
+        Chunk::store(dxr + c * VW, o);
       }
     }
   }
@@ -212,149 +241,14 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(
       for (int i = 0; i < CPL; ++i) {
         const int c = lane + 64 * i;
         if (c < nch) {
-          // 16-B LDS accesses (scalar ones at a 32-B lane stride were 8-way bank conflicts)
+          // 16-B LDS accesses (scalar ones at a lane stride of a whole chunk were 8-way (VW = 8)
+          // and 4-way (VW = 4) bank conflicts)
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            red_acc4(red, c * 2 + h, adg[i] + 4 * h, w);
-            if (!RMS) red_acc4(red, D / 4 + c * 2 + h, adb[i] + 4 * h, w);
-            if constexpr (CS) red_acc4(red, KCS * D / 4 + c * 2 + h, acs[i] + 4 * h, w);
+          for (int h = 0; h < VW / 4; ++h) {
+            red_acc4(red, c * (VW / 4) + h, adg[i] + 4 * h, w);
+            if (!RMS) red_acc4(red, D / 4 + c * (VW / 4) + h, adb[i] + 4 * h, w);
+            if constexpr (CS) red_acc4(red, KCS * D / 4 + c * (VW / 4) + h, acs[i] + 4 * h, w);
           }
-        }
-      }
-    }
-    __syncthreads();
-  }
-  for (int d = threadIdx.x; d < D; d += 256) {
-    ws_dg[(long long)blockIdx.x * D + d] = red[d];
-    if (!RMS) ws_db[(long long)blockIdx.x * D + d] = red[D + d];
-    if constexpr (CS) ws_cs[(long long)blockIdx.x * D + d] = red[KCS * D + d];
-  }
-}
-
-// The same backward with 8-B (4-element) lane chunks, for widths whose 16-B chunk count is not
-// a multiple of 64 (GPT-2: D = 768 -> 96 chunks of 8, so the 16-B form leaves half the lanes
-// idle in its second chunk and carries [2][8] accumulators; here 192 chunks of 4 = 3 per lane,
-// every lane busy, [3][4] accumulators: fewer VGPRs, more waves per SIMD for this latency-bound
-// stream).  Same math, same per-block partial rows.
-__device__ __forceinline__ void ld4b(const bf16_t* p, float* v) {
-  const uint2 q = *(const uint2*)p;
-  v[0] = __uint_as_float(q.x << 16);
-  v[1] = __uint_as_float(q.x & 0xffff0000u);
-  v[2] = __uint_as_float(q.y << 16);
-  v[3] = __uint_as_float(q.y & 0xffff0000u);
-}
-__device__ __forceinline__ void unpack4(uint2 q, float* v) {
-  v[0] = __uint_as_float(q.x << 16);
-  v[1] = __uint_as_float(q.x & 0xffff0000u);
-  v[2] = __uint_as_float(q.y << 16);
-  v[3] = __uint_as_float(q.y & 0xffff0000u);
-}
-
-template <int CPL, bool RMS, bool CS>
-__global__ __launch_bounds__(256) void norm_bwd4_kernel(
-    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
-    const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-    const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx, float* __restrict__ ws_dg,
-    float* __restrict__ ws_db, float* __restrict__ ws_cs, int M, int D) {
-  const int lane = threadIdx.x & 63;
-  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int nw = gridDim.x * 4;
-  const int nch = D >> 2;
-  float adg[CPL][4], adb[CPL][4], acs[CS ? CPL : 1][4];
-#pragma unroll
-  for (int i = 0; i < CPL; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) adg[i][e] = adb[i][e] = 0.f;
-#pragma unroll
-  for (int i = 0; i < (CS ? CPL : 1); ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acs[i][e] = 0.f;
-
-  float gg[CPL][4];
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) ld4b(g + c * 4, gg[i]);
-  }
-  uint2 px[CPL], pd[CPL], pr[CPL];
-  float pmean = 0.f, prstd = 0.f;
-  auto fetch = [&](int r) {
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        px[i] = *(const uint2*)(x + (long long)r * D + c * 4);
-        pd[i] = *(const uint2*)(dy + (long long)r * D + c * 4);
-        if (dres) pr[i] = *(const uint2*)(dres + (long long)r * D + c * 4);
-      }
-    }
-    pmean = RMS ? 0.f : mean_in[r];
-    prstd = rstd_in[r];
-  };
-  if (gw < M) fetch(gw);
-  for (int row = gw; row < M; row += nw) {
-    const float mean = pmean;
-    const float rstd = prstd;
-    uint2 cx[CPL], cd[CPL], rraw[CPL];
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      cx[i] = px[i];
-      cd[i] = pd[i];
-      rraw[i] = pr[i];
-    }
-    if (row + nw < M) fetch(row + nw);
-    float xh[CPL][4], dxh[CPL][4];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        float xv[4], dv[4];
-        unpack4(cx[i], xv);
-        unpack4(cd[i], dv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          xh[i][e] = (xv[e] - mean) * rstd;
-          dxh[i][e] = dv[e] * gg[i][e];
-          s1 += dxh[i][e];
-          s2 += dxh[i][e] * xh[i][e];
-          adg[i][e] += dv[e] * xh[i][e];
-          adb[i][e] += dv[e];
-        }
-      }
-    }
-    const float m1 = RMS ? 0.f : wave_sum(s1) / D;
-    const float m2 = wave_sum(s2) / D;
-    bf16_t* dxr = dx + (long long)row * D;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        float o[4], r[4];
-        if (dres) unpack4(rraw[i], r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          o[e] = rstd * (dxh[i][e] - m1 - xh[i][e] * m2);
-          if (dres) o[e] += r[e];
-          if constexpr (CS) acs[i][e] += o[e];
-        }
-        *(uint2*)(dxr + c * 4) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
-      }
-    }
-  }
-  extern __shared__ float red[];
-  constexpr int KCS = RMS ? 1 : 2;
-  const int wv = threadIdx.x >> 6;
-  for (int w = 0; w < 4; ++w) {
-    if (wv == w) {
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nch) {
-          // 16-B LDS accesses (scalar ones at a 16-B lane stride were 4-way bank conflicts)
-          red_acc4(red, c, adg[i], w);
-          if (!RMS) red_acc4(red, D / 4 + c, adb[i], w);
-          if constexpr (CS) red_acc4(red, KCS * D / 4 + c, acs[i], w);
         }
       }
     }
@@ -411,12 +305,13 @@ __global__ __launch_bounds__(256) void colsum_ws_kernel(const float* __restrict_
 // (bitwise reproducible).  The two-launch form (W -> W/32 -> 1) paid a second launch and a
 // kernel-boundary drain per reduction (~50 per GPT-2 step).
 constexpr int kWideU = 12, kWideMaxRows = 4096;
-__global__ __launch_bounds__(1024) void colsum_wide_kernel(const float* __restrict__ ws, OutPtrs outs, int W, int D,
-                                                          int accumulate, long long ws_z) {
+// The calling 1024-thread block reduces columns [d0, d0 + 64) of one job: out[d] (+)= sum_w ws[w][d].
+// The one body of colsum_wide_kernel and colsum_multi_kernel.
+__device__ __forceinline__ void colsum_wide_cols(const float* __restrict__ ws, float* out, int W, int D, int d0,
+                                                 bool accumulate) {
   __shared__ float part[16][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  ws += blockIdx.z * ws_z;
-  const int d = blockIdx.x * 64 + lane;
+  const int d = d0 + lane;
   float acc = 0.f;
   if (d < D) {
     for (int w0 = wv; w0 < W; w0 += 16 * kWideU) {
@@ -436,16 +331,22 @@ __global__ __launch_bounds__(1024) void colsum_wide_kernel(const float* __restri
     float t = part[0][lane];
 #pragma unroll
     for (int i = 1; i < 16; ++i) t += part[i][lane];
-    float* o = outs.p[blockIdx.z] + d;
+    float* o = out + d;
     *o = accumulate ? *o + t : t;
   }
+}
+
+// z = independent reductions batched into one launch: ws + z*ws_z [W][D] -> outs.p[z]
+__global__ __launch_bounds__(1024) void colsum_wide_kernel(const float* __restrict__ ws, OutPtrs outs, int W, int D,
+                                                          int accumulate, long long ws_z) {
+  colsum_wide_cols(ws + blockIdx.z * ws_z, outs.p[blockIdx.z], W, D, blockIdx.x * 64, accumulate);
 }
 
 // Deferred column-sum reductions of one backward window in ONE launch (ops/gemm.py: the bias /
 // LayerNorm-parameter gradients of two layers flushed with their grouped weight gradients):
 // job j = ws_j [W_j][D_j] partial rows -> out_j [D_j]; block b works on 64 columns of the job
-// whose block range holds b.  Per job the body, and so the summation order, is
-// colsum_wide_kernel's: the result is bitwise the non-deferred one.
+// whose block range holds b.  Per job it runs colsum_wide_cols, the very function
+// colsum_wide_kernel runs, so the result is bitwise the non-deferred one by construction.
 constexpr int kMultiJobs = 32;
 struct ColsumJobs {
   const float* ws[kMultiJobs];
@@ -459,38 +360,12 @@ struct ColsumJobs {
 static_assert(sizeof(ColsumJobs) <= 4096, "kernel argument segment");
 
 __global__ __launch_bounds__(1024) void colsum_multi_kernel(ColsumJobs jobs) {
-  __shared__ float part[16][64];
   const int b = blockIdx.x;
   int j = 0;
 #pragma unroll
   for (int i = 1; i < kMultiJobs; ++i) j += (i < jobs.n && b >= jobs.start[i]) ? 1 : 0;
   j = __builtin_amdgcn_readfirstlane(j);
-  const float* __restrict__ ws = jobs.ws[j];
-  const int W = jobs.W[j], D = jobs.D[j];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int d = (b - jobs.start[j]) * 64 + lane;
-  float acc = 0.f;
-  if (d < D) {
-    for (int w0 = wv; w0 < W; w0 += 16 * kWideU) {
-      float v[kWideU];
-#pragma unroll
-      for (int u = 0; u < kWideU; ++u) {
-        const int w = w0 + 16 * u;
-        v[u] = w < W ? ws[(long long)w * D + d] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kWideU; ++u) acc += v[u];
-    }
-  }
-  part[wv][lane] = acc;
-  __syncthreads();
-  if (wv == 0 && d < D) {
-    float t = part[0][lane];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) t += part[i][lane];
-    float* o = jobs.out[j] + d;
-    *o = ((jobs.accumulate >> j) & 1) ? *o + t : t;
-  }
+  colsum_wide_cols(jobs.ws[j], jobs.out[j], jobs.W[j], jobs.D[j], (b - jobs.start[j]) * 64, (jobs.accumulate >> j) & 1);
 }
 
 static bool colsum_wide_enabled() {
@@ -595,10 +470,41 @@ static int launch_norm_fwd(const void* x, const void* g, const void* b, void* y,
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// ws layout: [nz][nblk][D] partials (dgamma | dbeta | colsum(dx)) | nz x [64][D] level-2 rows,
-// nz = (RMS ? 1 : 2) + (dxsum != nullptr).  dxsum is always written (never accumulated).
-// resident 256-thread blocks of a norm_bwd_kernel variant on this device (cached per variant)
-template <int C, bool RMS, bool CS>
+// The norm_bwd_kernel instantiation that runs a width, handed to f as a Kernel<...> tag: the one
+// place that picks it, so the occupancy query and the launch (both inside f) name the same kernel.
+// Returns f's result, 1 for an unsupported width.
+template <auto K>
+struct Kernel {
+  static constexpr auto fn = K;
+};
+template <int VW, int CPL, bool RMS, typename F>
+static int with_norm_bwd_cs(bool cs, F& f) {
+  if constexpr (!RMS) {  // (RMSNorm never takes the dx column sums)
+    if (cs) return f(Kernel<norm_bwd_kernel<VW, CPL, RMS, true>>{});
+  }
+  return f(Kernel<norm_bwd_kernel<VW, CPL, RMS, false>>{});
+}
+template <bool RMS, typename F>
+static int with_norm_bwd_kernel(int D, bool cs, F f) {
+  static int vw4_env = -1;
+  if (vw4_env < 0) {
+    const char* e = getenv("RTDC_NORM_BWD_VW4");
+    vw4_env = (e && e[0] == '0') ? 0 : 1;
+  }
+  // 8-B chunks when they fill every lane (D/4 a multiple of 64) and 16-B ones would not, up to 4
+  // chunks per lane: D/4 = 64 * odd and <= 256, so D is 256 or 768 and a lane owns 1 or 3 chunks
+  if (vw4_env && (D / 8) % 64 != 0 && (D / 4) % 64 == 0 && D / 4 <= 64 * 4)
+    return D / 4 == 64 ? with_norm_bwd_cs<4, 1, RMS>(cs, f) : with_norm_bwd_cs<4, 3, RMS>(cs, f);
+  const int cpl = (D / 8 + 63) / 64;
+  if (cpl <= 1) return with_norm_bwd_cs<8, 1, RMS>(cs, f);
+  if (cpl <= 2) return with_norm_bwd_cs<8, 2, RMS>(cs, f);
+  if (cpl <= 4) return with_norm_bwd_cs<8, 4, RMS>(cs, f);
+  if (cpl <= 8) return with_norm_bwd_cs<8, 8, RMS>(cs, f);
+  return 1;
+}
+
+// resident 256-thread blocks of kernel K on this device (cached per kernel)
+template <auto K>
 static int resident_blocks(size_t lds) {
   static int cus = 0, occ = 0;
   static size_t occ_lds = ~(size_t)0;
@@ -609,107 +515,46 @@ static int resident_blocks(size_t lds) {
       cus = 256;
   }
   if (lds != occ_lds) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, norm_bwd_kernel<C, RMS, CS>, 256, lds) != hipSuccess ||
-        occ <= 0)
-      occ = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, K, 256, lds) != hipSuccess || occ <= 0) occ = 1;
     occ_lds = lds;
   }
   return cus * occ;
 }
 
-template <bool RMS, bool CS>
-static int resident_blocks4(size_t lds, int cpl4) {
-  static int cus = 0;
-  static int occ[5] = {0, 0, 0, 0, 0};
-  static size_t occ_lds[5] = {~(size_t)0, ~(size_t)0, ~(size_t)0, ~(size_t)0, ~(size_t)0};
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  if (cpl4 < 1 || cpl4 > 4) return cus;
-  if (lds != occ_lds[cpl4]) {
-    hipError_t e = hipErrorInvalidValue;
-    int o = 0;
-    if (cpl4 == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, norm_bwd4_kernel<1, RMS, CS>, 256, lds);
-    if (cpl4 == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, norm_bwd4_kernel<2, RMS, CS>, 256, lds);
-    if (cpl4 == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, norm_bwd4_kernel<3, RMS, CS>, 256, lds);
-    if (cpl4 == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, norm_bwd4_kernel<4, RMS, CS>, 256, lds);
-    occ[cpl4] = (e != hipSuccess || o <= 0) ? 1 : o;
-    occ_lds[cpl4] = lds;
-  }
-  return cus * occ[cpl4];
-}
-
+// ws layout: [nz][nblk][D] partials (dgamma | dbeta | colsum(dx)) | nz x [64][D] level-2 rows,
+// nz = (RMS ? 1 : 2) + (dxsum != nullptr).  The outputs are written, never accumulated.
 template <bool RMS>
 static int launch_norm_bwd(const void* dy, const void* x, const void* g, const float* mean,
                            const float* rstd, const void* dres, void* dx, float* ws, float* dg,
-                           float* db, float* dxsum, int M, int D, int nwaves, int accumulate, hipStream_t st,
+                           float* db, float* dxsum, int M, int D, int nwaves, hipStream_t st,
                            int* nblk_out = nullptr) {
   if (D % 8 != 0 || nwaves % 4 != 0) return 1;
-  const int cpl = (D / 8 + 63) / 64;
   const bool cs = dxsum != nullptr;
   const int nz = (RMS ? 1 : 2) + (cs ? 1 : 0);
   const size_t lds = (size_t)nz * D * sizeof(float);
   if (lds > 160 * 1024) return 1;
-  static int vw4_env = -1;
-  if (vw4_env < 0) {
-    const char* e = getenv("RTDC_NORM_BWD_VW4");
-    vw4_env = (e && e[0] == '0') ? 0 : 1;
-  }
-  // 8-B chunks when they fill every lane (D/4 a multiple of 64) and 16-B ones would not
-  const bool vw4 = vw4_env && (D / 8) % 64 != 0 && (D / 4) % 64 == 0 && D / 4 <= 64 * 4;
-  // one wave of blocks: a grid past the resident block slots leaves a partial second wave
-  // (GPT-2: 1024 blocks on 768 slots ran 0.94 ms/step of LayerNorm backward, 768 blocks 0.67)
-#define RB(C) (cs ? resident_blocks<C, RMS, true>(lds) : resident_blocks<C, RMS, false>(lds))
-  const int cpl4 = (D / 4) / 64;
-  const int slots = vw4 ? (cs ? resident_blocks4<RMS, true>(lds, cpl4) : resident_blocks4<RMS, false>(lds, cpl4))
-                        : cpl <= 1 ? RB(1) : cpl <= 2 ? RB(2) : cpl <= 4 ? RB(4) : RB(8);
-#undef RB
-  const int nblk = nwaves / 4 < slots ? nwaves / 4 : slots;
-  dim3 grid(nblk), block(256);
-  const long long part = (long long)nblk * D;
-  float* ws_dg = ws;
-  float* ws_db = ws + part;
-  float* ws_cs = ws + (RMS ? 1 : 2) * part;
-  float* tmp = ws + nz * part;
-#define L(C, CS)                                                                              \
-  hipLaunchKernelGGL((norm_bwd_kernel<C, RMS, CS>), grid, block, lds, st, (const bf16_t*)dy,   \
-                     (const bf16_t*)x, (const bf16_t*)g, mean, rstd, (const bf16_t*)dres,     \
-                     (bf16_t*)dx, ws_dg, ws_db, ws_cs, M, D)
-#define LC(C) \
-  if (cs) L(C, true); else L(C, false)
-#define L4(C, CS)                                                                             \
-  hipLaunchKernelGGL((norm_bwd4_kernel<C, RMS, CS>), grid, block, lds, st, (const bf16_t*)dy,  \
-                     (const bf16_t*)x, (const bf16_t*)g, mean, rstd, (const bf16_t*)dres,     \
-                     (bf16_t*)dx, ws_dg, ws_db, ws_cs, M, D)
-  if (vw4) {
-    if (cpl4 == 1) { if (cs) L4(1, true); else L4(1, false); }
-    else if (cpl4 == 2) { if (cs) L4(2, true); else L4(2, false); }
-    else if (cpl4 == 3) { if (cs) L4(3, true); else L4(3, false); }
-    else { if (cs) L4(4, true); else L4(4, false); }
-  } else if (cpl <= 1) { LC(1); }
-  else if (cpl <= 2) { LC(2); }
-  else if (cpl <= 4) { LC(4); }
-  else if (cpl <= 8) { LC(8); }
-  else return 1;
-#undef LC
-#undef L
-#undef L4
+  int nblk = 0;
+  const int rc = with_norm_bwd_kernel<RMS>(D, cs, [&](auto k) {
+    // one wave of blocks: a grid past the resident block slots leaves a partial second wave
+    // (GPT-2: 1024 blocks on 768 slots ran 0.94 ms/step of LayerNorm backward, 768 blocks 0.67)
+    constexpr auto kernel = decltype(k)::fn;
+    const int slots = resident_blocks<kernel>(lds);
+    nblk = nwaves / 4 < slots ? nwaves / 4 : slots;
+    const long long part = (long long)nblk * D;
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), lds, st, (const bf16_t*)dy, (const bf16_t*)x,
+                       (const bf16_t*)g, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, ws, ws + part,
+                       ws + (RMS ? 1 : 2) * part, M, D);
+    return 0;
+  });
+  if (rc) return rc;
   if (nblk_out) {  // deferred: the caller reduces the [nz][nblk][D] partials (rtdc_colsum_multi)
     *nblk_out = nblk;
     return hipGetLastError() == hipSuccess ? 0 : 2;
   }
-  // one reduction launch pair for all of them; the colsum of dx is never accumulated, so it
-  // gets its own pair when dgamma/dbeta accumulate
-  if (!cs || !accumulate) {
-    OutPtrs o = RMS ? outs1(dg, cs ? dxsum : nullptr) : outs1(dg, db, cs ? dxsum : nullptr);
-    colsum_ws_reduce(ws, nblk, D, tmp, o, accumulate, st, nz, part);
-  } else {
-    colsum_ws_reduce(ws, nblk, D, tmp, RMS ? outs1(dg) : outs1(dg, db), accumulate, st, nz - 1, part);
-    colsum_ws_reduce(ws_cs, nblk, D, tmp, outs1(dxsum), 0, st, 1, part);
-  }
+  // one reduction launch (pair) for all of them
+  const long long part = (long long)nblk * D;
+  const OutPtrs o = RMS ? outs1(dg) : outs1(dg, db, dxsum);
+  colsum_ws_reduce(ws, nblk, D, ws + nz * part, o, 0, st, nz, part);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -724,17 +569,16 @@ extern "C" int rtdc_rmsnorm_fwd(const void* x, const void* g, void* y, float* rs
 extern "C" int rtdc_layernorm_bwd(const void* dy, const void* x, const void* g, const float* mean,
                                   const float* rstd, const void* dres, void* dx, float* ws,
                                   float* dg, float* db, float* dxsum, int M, int D, int nwaves,
-                                  int accumulate, hipStream_t st, int* nblk_out) {
-  return launch_norm_bwd<false>(dy, x, g, mean, rstd, dres, dx, ws, dg, db, dxsum, M, D, nwaves,
-                                accumulate, st, nblk_out);
+                                  hipStream_t st, int* nblk_out) {
+  return launch_norm_bwd<false>(dy, x, g, mean, rstd, dres, dx, ws, dg, db, dxsum, M, D, nwaves, st, nblk_out);
 }
 extern "C" int rtdc_rmsnorm_bwd(const void* dy, const void* x, const void* g, const float* rstd,
-                                const void* dres, void* dx, float* ws, float* dg, float* dxsum, int M,
-                                int D, int nwaves, int accumulate, hipStream_t st) {
-  return launch_norm_bwd<true>(dy, x, g, nullptr, rstd, dres, dx, ws, dg, nullptr, dxsum, M, D, nwaves,
-                               accumulate, st);
+                                const void* dres, void* dx, float* ws, float* dg, int M, int D, int nwaves,
+                                hipStream_t st) {
+  return launch_norm_bwd<true>(dy, x, g, nullptr, rstd, dres, dx, ws, dg, nullptr, nullptr, M, D, nwaves, st);
 }
-// out[D] (+)= sum of W partial rows ws[W][D] (tmp: 64 * D floats of scratch)
+// out[D] (+)= sum of W partial rows ws[W][D] (tmp: 64 * D floats of scratch); called by the GEMM
+// launcher (gemm_bf16.hip) on the partial rows its gelu-backward epilogue leaves
 extern "C" int rtdc_colsum_rows(const float* ws, int W, int D, float* tmp, float* out, int accumulate,
                                 hipStream_t st) {
   colsum_ws_reduce(ws, W, D, tmp, outs1(out), accumulate, st);
@@ -762,9 +606,9 @@ extern "C" int rtdc_colsum_multi(const float* const* ws, float* const* out, cons
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// stage 1 only (the partial rows ws [nblk][N]); the reduction is deferred to rtdc_colsum_multi
-extern "C" int rtdc_colsum_partial(const void* X, int M, int N, int ld, float* ws, int nblk, int is_bf16,
-                                   hipStream_t st) {
+// stage 1 of a column sum: the partial rows ws [nblk][N] of X [M][N]
+static void launch_colsum_partial(const void* X, int M, int N, int ld, float* ws, int nblk, int is_bf16,
+                                  hipStream_t st) {
   const bool vec = N % 8 == 0 && ld % 8 == 0;
   const int rpb = (M + nblk - 1) / nblk;
   dim3 grid(nblk, (N + 511) / 512), block(256);
@@ -775,22 +619,19 @@ extern "C" int rtdc_colsum_partial(const void* X, int M, int N, int ld, float* w
     if (vec) CS(float, true); else CS(float, false);
   }
 #undef CS
+}
+
+// stage 1 only; the reduction is deferred to rtdc_colsum_multi
+extern "C" int rtdc_colsum_partial(const void* X, int M, int N, int ld, float* ws, int nblk, int is_bf16,
+                                   hipStream_t st) {
+  launch_colsum_partial(X, M, N, ld, ws, nblk, is_bf16, st);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 extern "C" int rtdc_colsum(const void* X, int M, int N, int ld, float* ws, int nblk, float* out,
                            int accumulate, int is_bf16, hipStream_t st) {
   // ws: [nblk][N] partials followed by [64][N] level-2 rows
-  const bool vec = N % 8 == 0 && ld % 8 == 0;
-  const int rpb = (M + nblk - 1) / nblk;
-  dim3 grid(nblk, (N + 511) / 512), block(256);
-#define CS(T, V) hipLaunchKernelGGL((colsum_partial_kernel<T, V>), grid, block, 0, st, (const T*)X, M, N, ld, rpb, ws)
-  if (is_bf16) {
-    if (vec) CS(bf16_t, true); else CS(bf16_t, false);
-  } else {
-    if (vec) CS(float, true); else CS(float, false);
-  }
-#undef CS
+  launch_colsum_partial(X, M, N, ld, ws, nblk, is_bf16, st);
   colsum_ws_reduce(ws, nblk, N, ws + (long long)nblk * N, outs1(out), accumulate, st);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

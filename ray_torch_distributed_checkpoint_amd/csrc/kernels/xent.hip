@@ -487,21 +487,22 @@ __global__ __launch_bounds__(NT) void xent_reg_kernel(const bf16_t* logits, bf16
 using namespace rtdc;
 
 // register-resident launch for bf16 rows of at most NT*NCH*8 columns (returns false if none fits)
+template <bool AUX>
 static bool launch_xent_reg(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
                             int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index,
-                            hipStream_t st) {
+                            XentAux<AUX> aux, hipStream_t st) {
   if (ld % 8 != 0 || getenv("RTDC_XENT_TWO_PASS")) return false;
-#define XR(NT, NCH)                                                                                          \
-  if (ld <= NT * NCH * 8) {                                                                                 \
-    if (argmax)                                                                                              \
-      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, true>), dim3(M), dim3(NT), 0, st, (const bf16_t*)logits,  \
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,   \
-                         XentAux<false>{});                                                                   \
-    else                                                                                                     \
-      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, false>), dim3(M), dim3(NT), 0, st, (const bf16_t*)logits, \
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,   \
-                         XentAux<false>{});                                                                   \
-    return true;                                                                                             \
+#define XR(NT, NCH)                                                                                        \
+  if (ld <= NT * NCH * 8) {                                                                               \
+    if (argmax)                                                                                            \
+      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, true, AUX>), dim3(M), dim3(NT), 0, st,                  \
+                         (const bf16_t*)logits, (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld,     \
+                         grad_scale, ignore_index, aux);                                                   \
+    else                                                                                                   \
+      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, false, AUX>), dim3(M), dim3(NT), 0, st,                 \
+                         (const bf16_t*)logits, (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld,     \
+                         grad_scale, ignore_index, aux);                                                   \
+    return true;                                                                                           \
   }
   // NT x NCH x 8 columns; one wave per SIMD per block so several blocks share a CU and one
   // block's write phase overlaps the next block's loads (GPT-2: 256 x 25)
@@ -515,127 +516,70 @@ static bool launch_xent_reg(const void* logits, void* dlogits, const int64_t* ta
   return false;
 }
 
-extern "C" int rtdc_xent(const void* logits, void* dlogits, const int64_t* target, float* loss,
-                         float* lse, int64_t* argmax, int M, int V, int ld, float grad_scale,
-                         int ignore_index, int is_bf16, hipStream_t st) {
-  dim3 grid(M), block(256);
+// AUX = false: the plain kernels; AUX = true: the ones with label smoothing / z-loss (the caller
+// routes eps = z = 0 with no ce to rtdc_xent)
+template <bool AUX>
+static int launch_xent(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
+                       int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index, int is_bf16,
+                       XentAux<AUX> aux, hipStream_t st) {
   const bool vec = (ld % 8 == 0);
-  if (is_bf16 && launch_xent_reg(logits, dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
-                                 st))
+  if (is_bf16 && launch_xent_reg<AUX>(logits, dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
+                                      aux, st))
     return hipGetLastError() == hipSuccess ? 0 : 2;
+#define XK(T, VEC)                                                                                          \
+  hipLaunchKernelGGL((xent_kernel<T, VEC, AUX>), dim3(M), dim3(256), 0, st, (const T*)logits, (T*)dlogits, \
+                     target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, aux)
   if (is_bf16) {
-    if (vec)
-      hipLaunchKernelGGL((xent_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)logits,
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
-                         XentAux<false>{});
-    else
-      hipLaunchKernelGGL((xent_kernel<bf16_t, false>), grid, block, 0, st, (const bf16_t*)logits,
-                         (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
-                         XentAux<false>{});
+    if (vec) XK(bf16_t, true); else XK(bf16_t, false);
   } else {
-    if (vec)
-      hipLaunchKernelGGL((xent_kernel<float, true>), grid, block, 0, st, (const float*)logits,
-                         (float*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, XentAux<false>{});
-    else
-      hipLaunchKernelGGL((xent_kernel<float, false>), grid, block, 0, st, (const float*)logits,
-                         (float*)dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, XentAux<false>{});
+    if (vec) XK(float, true); else XK(float, false);
   }
+#undef XK
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// the same ladder for the kernels with label smoothing / z-loss (the caller routes eps = z = 0
-// with no ce to rtdc_xent: the plain instantiations)
-static bool launch_xent_reg_aux(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
-                                int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index, float eps,
-                                float z, float* ce, hipStream_t st) {
-  if (ld % 8 != 0 || getenv("RTDC_XENT_TWO_PASS")) return false;
-  const XentAux<true> aux{eps, z, ce};
-#define XR(NT, NCH)                                                                                            \
-  if (ld <= NT * NCH * 8) {                                                                                   \
-    if (argmax)                                                                                                \
-      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, true, true>), dim3(M), dim3(NT), 0, st,                     \
-                         (const bf16_t*)logits, (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld,         \
-                         grad_scale, ignore_index, aux);                                                       \
-    else                                                                                                       \
-      hipLaunchKernelGGL((xent_reg_kernel<NT, NCH, false, true>), dim3(M), dim3(NT), 0, st,                    \
-                         (const bf16_t*)logits, (bf16_t*)dlogits, target, loss, lse, argmax, M, V, ld,         \
-                         grad_scale, ignore_index, aux);                                                       \
-    return true;                                                                                               \
-  }
-  XR(256, 4)
-  XR(256, 8)
-  XR(256, 16)
-  XR(256, 25)
-  XR(512, 16)
-  XR(1024, 16)
-#undef XR
-  return false;
+extern "C" int rtdc_xent(const void* logits, void* dlogits, const int64_t* target, float* loss,
+                         float* lse, int64_t* argmax, int M, int V, int ld, float grad_scale,
+                         int ignore_index, int is_bf16, hipStream_t st) {
+  return launch_xent<false>(logits, dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, is_bf16,
+                            XentAux<false>{}, st);
 }
 
 extern "C" int rtdc_xent_aux(const void* logits, void* dlogits, const int64_t* target, float* loss, float* lse,
                              int64_t* argmax, int M, int V, int ld, float grad_scale, int ignore_index, float eps,
                              float z, float* ce, int is_bf16, hipStream_t st) {
   if (M < 1 || V < 1 || ld < V || !(eps >= 0.f && eps < 1.f) || !(z >= 0.f)) return 1;
-  const bool vec = (ld % 8 == 0);
-  if (is_bf16 && launch_xent_reg_aux(logits, dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index,
-                                     eps, z, ce, st))
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  const XentAux<true> aux{eps, z, ce};
-#define XA(T, VEC)                                                                                         \
-  hipLaunchKernelGGL((xent_kernel<T, VEC, true>), dim3(M), dim3(256), 0, st, (const T*)logits, (T*)dlogits, \
-                     target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, aux)
-  if (is_bf16) {
-    if (vec) XA(bf16_t, true); else XA(bf16_t, false);
-  } else {
-    if (vec) XA(float, true); else XA(float, false);
-  }
-#undef XA
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return launch_xent<true>(logits, dlogits, target, loss, lse, argmax, M, V, ld, grad_scale, ignore_index, is_bf16,
+                           XentAux<true>{eps, z, ce}, st);
 }
 
 // ---- loss finalisation without ATen reductions: one block sums the per-row losses and counts
 // the non-ignored targets in a fixed order; out[0] = mean loss, out[1] = divisor (count clamped
 // to >= 1, or the caller's fixed divisor when target is null).
 namespace rtdc {
+// CE: the rows of plain cross-entropy `ce` are summed in the same fixed order next to the loss
+// rows, out[2] = sum ce / n (ce is not read otherwise)
+template <bool CE>
 __global__ __launch_bounds__(1024) void xent_finalize_kernel(const float* __restrict__ loss,
+                                                            const float* __restrict__ ce,
                                                             const int64_t* __restrict__ target, int M, float fixed_n,
                                                             int ignore, float* __restrict__ out) {
   __shared__ float red[16];
   float s = 0.f, c = 0.f;
+  [[maybe_unused]] float e = 0.f;
   for (int i = threadIdx.x; i < M; i += 1024) {
     s += loss[i];
+    if constexpr (CE) e += ce[i];
     if (target) c += target[i] != ignore ? 1.f : 0.f;
   }
   s = block_sum<1024>(s, red);
   c = block_sum<1024>(c, red);
+  if constexpr (CE) e = block_sum<1024>(e, red);
   if (threadIdx.x == 0) {
     const float n = target ? fmaxf(c, 1.f) : fixed_n;
     out[0] = s / n;
     out[1] = n;
-  }
-}
-
-// the same with the rows of plain cross-entropy `ce` summed in the same fixed order next to the
-// loss rows: out[2] = sum ce / n
-__global__ __launch_bounds__(1024) void xent_finalize_ce_kernel(const float* __restrict__ loss,
-                                                               const float* __restrict__ ce,
-                                                               const int64_t* __restrict__ target, int M,
-                                                               float fixed_n, int ignore, float* __restrict__ out) {
-  __shared__ float red[16];
-  float s = 0.f, c = 0.f, e = 0.f;
-  for (int i = threadIdx.x; i < M; i += 1024) {
-    s += loss[i];
-    e += ce[i];
-    if (target) c += target[i] != ignore ? 1.f : 0.f;
-  }
-  s = block_sum<1024>(s, red);
-  c = block_sum<1024>(c, red);
-  e = block_sum<1024>(e, red);
-  if (threadIdx.x == 0) {
-    const float n = target ? fmaxf(c, 1.f) : fixed_n;
-    out[0] = s / n;
-    out[1] = n;
-    out[2] = e / n;
+    if constexpr (CE) out[2] = e / n;
   }
 }
 
@@ -698,7 +642,8 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
 
 extern "C" int rtdc_xent_finalize(const float* loss, const int64_t* target, int M, float fixed_n, int ignore, float* out,
                                   hipStream_t st) {
-  hipLaunchKernelGGL(rtdc::xent_finalize_kernel, dim3(1), dim3(1024), 0, st, loss, target, M, fixed_n, ignore, out);
+  hipLaunchKernelGGL(rtdc::xent_finalize_kernel<false>, dim3(1), dim3(1024), 0, st, loss, (const float*)nullptr, target,
+                     M, fixed_n, ignore, out);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -706,7 +651,7 @@ extern "C" int rtdc_xent_finalize(const float* loss, const int64_t* target, int 
 extern "C" int rtdc_xent_finalize_ce(const float* loss, const float* ce, const int64_t* target, int M, float fixed_n,
                                      int ignore, float* out, hipStream_t st) {
   if (!ce) return 1;
-  hipLaunchKernelGGL(rtdc::xent_finalize_ce_kernel, dim3(1), dim3(1024), 0, st, loss, ce, target, M, fixed_n, ignore,
+  hipLaunchKernelGGL(rtdc::xent_finalize_kernel<true>, dim3(1), dim3(1024), 0, st, loss, ce, target, M, fixed_n, ignore,
                      out);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
@@ -716,15 +661,15 @@ extern "C" int rtdc_xent_alpha(const float* g, const float* den, float* out, hip
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-extern "C" int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* target, const float* lse,
-                             const float* g, const float* den, int M, int V, int ignore_index, int is_bf16,
-                             hipStream_t st) {
-  if (M < 1 || V < 1) return 1;
+template <bool AUX>
+static int launch_xent_bwd(const void* logits, void* dlogits, const int64_t* target, const float* lse, const float* g,
+                           const float* den, int M, int V, int ignore_index, int is_bf16, rtdc::XentAux<AUX> aux,
+                           hipStream_t st) {
   // 16 B per lane only where every row starts 16-B aligned (a contiguous view may start anywhere)
   const bool vec = V % 8 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
-#define XB(T, VEC)                                                                                              \
-  hipLaunchKernelGGL((rtdc::xent_bwd_kernel<T, VEC>), dim3(M), dim3(256), 0, st, (const T*)logits, (T*)dlogits, \
-                     target, lse, g, den, M, V, ignore_index, rtdc::XentAux<false>{})
+#define XB(T, VEC)                                                                                       \
+  hipLaunchKernelGGL((rtdc::xent_bwd_kernel<T, VEC, AUX>), dim3(M), dim3(256), 0, st, (const T*)logits,  \
+                     (T*)dlogits, target, lse, g, den, M, V, ignore_index, aux)
   if (is_bf16) {
     if (vec) XB(bf16_t, true); else XB(bf16_t, false);
   } else {
@@ -734,20 +679,18 @@ extern "C" int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* t
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+extern "C" int rtdc_xent_bwd(const void* logits, void* dlogits, const int64_t* target, const float* lse,
+                             const float* g, const float* den, int M, int V, int ignore_index, int is_bf16,
+                             hipStream_t st) {
+  if (M < 1 || V < 1) return 1;
+  return launch_xent_bwd<false>(logits, dlogits, target, lse, g, den, M, V, ignore_index, is_bf16,
+                                rtdc::XentAux<false>{}, st);
+}
+
 extern "C" int rtdc_xent_bwd_aux(const void* logits, void* dlogits, const int64_t* target, const float* lse,
                                  const float* g, const float* den, int M, int V, int ignore_index, float eps, float z,
                                  int is_bf16, hipStream_t st) {
   if (M < 1 || V < 1 || !(eps >= 0.f && eps < 1.f) || !(z >= 0.f)) return 1;
-  const bool vec = V % 8 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
-  const rtdc::XentAux<true> aux{eps, z, nullptr};
-#define XB(T, VEC)                                                                                        \
-  hipLaunchKernelGGL((rtdc::xent_bwd_kernel<T, VEC, true>), dim3(M), dim3(256), 0, st, (const T*)logits,  \
-                     (T*)dlogits, target, lse, g, den, M, V, ignore_index, aux)
-  if (is_bf16) {
-    if (vec) XB(bf16_t, true); else XB(bf16_t, false);
-  } else {
-    if (vec) XB(float, true); else XB(float, false);
-  }
-#undef XB
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return launch_xent_bwd<true>(logits, dlogits, target, lse, g, den, M, V, ignore_index, is_bf16,
+                               rtdc::XentAux<true>{eps, z, nullptr}, st);
 }

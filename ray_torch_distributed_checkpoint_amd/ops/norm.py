@@ -91,7 +91,7 @@ class _LayerNorm(torch.autograd.Function):
             # partial rows into a buffer of their own, reduced with the deferred window (gemm.py)
             part = torch.empty(len(outs) * (nw // 4 + 64) * D, dtype=torch.float32, device=xc.device)
             nblk = gpu_ext().layernorm_bwd(dy.contiguous(), xc, ws, mean, rstd, dres, dx, part, dg, db, dxsum, nw,
-                                           False, True)
+                                           True)
             rows = part[: len(outs) * nblk * D].view(len(outs), nblk * D)
             done = [G._WG.add_job(rows[z], nblk, D, o, accs[z]) for z, o in enumerate(outs)]
             if not all(done):
@@ -102,8 +102,7 @@ class _LayerNorm(torch.autograd.Function):
                                        [nblk] * done.count(False), [D] * done.count(False),
                                        [int(a) for a, d in zip(accs, done) if not d])
         else:
-            gpu_ext().layernorm_bwd(dy.contiguous(), xc, ws, mean, rstd, dres, dx, wsp, dg, db, dxsum, nw, False,
-                                    False)
+            gpu_ext().layernorm_bwd(dy.contiguous(), xc, ws, mean, rstd, dres, dx, wsp, dg, db, dxsum, nw, False)
         if dxsum is not None:
             G.offer_colsum(dx, dxsum)
         return dx, dg, db, None, None, None
@@ -138,7 +137,7 @@ class _RMSNorm(torch.autograd.Function):
         if dg is None:
             dg = torch.empty(D, dtype=torch.float32, device=xc.device)
         dres = dpass.contiguous() if dpass is not None else None
-        gpu_ext().rmsnorm_bwd(dy.contiguous(), xc, ws, rstd, dres, dx, wsp, dg, None, nw, False)
+        gpu_ext().rmsnorm_bwd(dy.contiguous(), xc, ws, rstd, dres, dx, wsp, dg, nw)
         return dx, dg, None, None
 
 

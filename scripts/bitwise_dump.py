@@ -2,8 +2,13 @@
 (RTDC_EXT_SO=<path>) can be compared bitwise - the check behind every "bitwise equal" A/B record
 in profiles/.
 
-    python scripts/bitwise_dump.py attn|norm|resnet|gemm OUT.pt
+    python scripts/bitwise_dump.py attn|norm|colsum|xent|resnet|gemm OUT.pt
     python scripts/bitwise_dump.py compare A.pt B.pt
+
+`norm`, `colsum` and `xent` call the native entry points at small shapes that reach every
+instantiation and launcher branch (profiles/norm_bwd_merge.md); `norm` and `colsum` are run once more
+with RTDC_NORM_BWD_VW4=0 RTDC_COLSUM_WIDE=0.  `norm` also runs ops/norm.py, so against a build whose
+norm bindings differ it is run from that build's own checkout, with this file dropped in.
 
 `attn` runs every instantiation of the flash kernels at small shapes (all three rows-per-wave knobs
 at 1 and at 2, head splits, plain and document-masked, every output), then three large default
@@ -90,10 +95,67 @@ def attn():
     return out
 
 
+def _nargs(fn):
+    """positional arguments of a binding, from its pybind11 signature line"""
+    return fn.__doc__.splitlines()[0].count(": ")
+
+
+def _norm_variants(out):
+    """Every norm_bwd_kernel instantiation through layernorm_bwd / rmsnorm_bwd: D over every width
+    branch (8-B form: 256, 768), M = 1, 5, 67 on 16 waves (a wave owns up to 5 rows) and 9001 x 768 on
+    the default waves (grid capped at the resident slots); with and without dres and, for LayerNorm,
+    the dx column sums; reduced at once, and deferred (the partial rows, then colsum_multi).  Keeps
+    every output and the raw partial-row workspace [nz][nblk][D].  An older build's bindings still
+    take `accumulate` (False) and, for RMSNorm, `dxsum` (None): passed only where the binding has them."""
+    from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+
+    ext = gpu_ext()
+    old_ln, old_rms = _nargs(ext.layernorm_bwd) == 14, _nargs(ext.rmsnorm_bwd) == 11
+    cases = [(M, D, 16) for D in (8, 200, 256, 512, 520, 768, 1024, 2048, 4096) for M in (1, 5, 67)] + [(9001, 768, 4096)]
+    for M, D, nw in cases:
+        g = torch.Generator().manual_seed(1000 * D + M)
+        x, dy, dres = ((torch.randn(M, D, generator=g) * 2).bfloat16().cuda() for _ in range(3))
+        gam = (1 + 0.1 * torch.randn(D, generator=g)).bfloat16().cuda()
+        bet = (0.1 * torch.randn(D, generator=g)).bfloat16().cuda()
+        nblk_max = nw // 4
+        for rms in (False, True):
+            y, mean, rstd = torch.zeros_like(x), torch.zeros(M, device="cuda"), torch.zeros(M, device="cuda")
+            if rms:
+                ext.rmsnorm_fwd(x, gam, y, rstd, 1e-5)
+            else:
+                ext.layernorm_fwd(x, gam, bet, y, mean, rstd, 1e-5)
+            for dr in (None, dres):
+                for cs in ((False,) if rms else (False, True)):
+                    for defer in ((False,) if rms else (False, True)):
+                        nz = (1 if rms else 2) + cs
+                        ws = torch.zeros(nz * (nblk_max + 64) * D, device="cuda")
+                        dx = torch.zeros_like(x)
+                        dg, db, dxs = (torch.zeros(D, device="cuda") for _ in range(3))
+                        if rms:
+                            ext.rmsnorm_bwd(dy, x, gam, rstd, dr, dx, ws, dg, *((None, nw, False) if old_rms else (nw,)))
+                            nblk = 0
+                        else:
+                            nblk = ext.layernorm_bwd(dy, x, gam, mean, rstd, dr, dx, ws, dg, db, dxs if cs else None, nw,
+                                                     *((False, defer) if old_ln else (defer,)))
+                        res = {"dx": dx, "ws": ws.clone()}
+                        if defer:
+                            assert 1 <= nblk <= nblk_max
+                            outs = [dg, db] + ([dxs] if cs else [])
+                            rows = ws[: nz * nblk * D].view(nz, nblk * D)
+                            ext.colsum_multi([rows[z] for z in range(nz)], outs, [nblk] * nz, [D] * nz, [0] * nz)
+                            res["nblk"] = nblk
+                        res.update(dgamma=dg, dbeta=db, dxsum=dxs, y=y, mean=mean, rstd=rstd)
+                        torch.cuda.synchronize()
+                        name = f"{'rms' if rms else 'ln'}.M{M}.D{D}.{'dres' if dr is not None else 'plain'}" \
+                               f"{'.colsum' if cs else ''}{'.defer' if defer else ''}"
+                        out[name] = {k: v.cpu() if torch.is_tensor(v) else v for k, v in res.items()}
+
+
 def norm():
     from ray_torch_distributed_checkpoint_amd.ops.norm import layer_norm, rms_norm
 
     out = {}
+    _norm_variants(out)
     for kind, M, D in [("rms", 2048, 4096), ("ln", 512, 4096), ("rms", 1024, 1024), ("ln", 4096, 768),
                        ("ln", 256, 2048)]:
         torch.manual_seed(M + D)
@@ -105,6 +167,83 @@ def norm():
         torch.cuda.synchronize()
         out[f"{kind}_{M}x{D}"] = (y.detach().cpu(), x.grad.cpu(), w.grad.cpu(),
                                   b.grad.cpu() if b.grad is not None else torch.zeros(1))
+    return out
+
+
+def colsum():
+    """G.colsum (stage 1 + the reduction: vector loads at N % 8 == 0, scalar ones at N = 200 on a
+    padded row), written and accumulated, bf16 and fp32; colsum_partial; and one colsum_multi launch of
+    5 jobs of mixed (W, D), W = 1 and W = 4096 among them, two of them accumulating."""
+    from ray_torch_distributed_checkpoint_amd.ops import gemm as G
+    from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+
+    ext, out = gpu_ext(), {}
+    for dt in (torch.bfloat16, torch.float32):
+        for N in (8, 200, 768, 2304):
+            for M in (64, 4096, 16384):
+                g = torch.Generator().manual_seed(N + M)
+                X = torch.randn(M, N, generator=g).to(dt).cuda()
+                o = torch.zeros(N, device="cuda")
+                G.colsum(X, out=o)
+                acc = o.clone()
+                G.colsum(X, out=acc, accumulate=True)
+                nblk = min(256, max(1, M // 64))
+                ws = torch.zeros(nblk * N, device="cuda")
+                ext.colsum_partial(X, M, N, N, ws, nblk)
+                case = {"sum": o, "acc": acc, "partial": ws}
+                if N == 200:  # rows padded to 203 elements: never the vector form
+                    Xp = torch.randn(M, 203, generator=g).to(dt).cuda()
+                    op = torch.zeros(N, device="cuda")
+                    G.colsum(Xp[:, :N], out=op)
+                    case["strided"] = op
+                torch.cuda.synchronize()
+                out[f"{str(dt)[6:]}.M{M}.N{N}"] = {k: v.cpu() for k, v in case.items()}
+    g = torch.Generator().manual_seed(5)
+    jobs = [(1, 768), (4096, 200), (67, 8), (192, 2304), (1000, 50)]
+    wss = [torch.randn(W * D, generator=g).cuda() for W, D in jobs]
+    outs = [torch.randn(D, generator=g).cuda() for _, D in jobs]
+    ext.colsum_multi(wss, outs, [W for W, _ in jobs], [D for _, D in jobs], [0, 1, 0, 1, 0])
+    torch.cuda.synchronize()
+    out["multi"] = {f"job{j}": o.cpu() for j, o in enumerate(outs)}
+    return out
+
+
+def xent():
+    """xent (plain, and label smoothing 0.1 with z-loss 1e-4; with and without argmax / lse) at one
+    (V, ld) per launcher branch (tests/ulp.py XENT_ARMS), both xent_finalize entries (with and without
+    the ce rows, counted and fixed divisor) and both xent_bwd entries on the dense [M, V] logits."""
+    from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+    from tests import ulp as U
+
+    ext, out = gpu_ext(), {}
+    for dtype, V, ld, arm in U.XENT_ARMS:
+        for planted in (False, True):
+            c = U.xent_inputs(dtype, V, ld, planted, dev="cuda")
+            M = c["logits"].shape[0]
+            for eps, z in ((0.0, 0.0), (0.1, 1e-4)):
+                case = {}
+                for with_arg in (False, True):
+                    dl = torch.zeros_like(c["logits"])
+                    loss, ce = torch.zeros(M, device="cuda"), torch.zeros(M, device="cuda")
+                    lse = torch.zeros(M, device="cuda") if with_arg else None
+                    am = torch.zeros(M, dtype=torch.int64, device="cuda") if with_arg else None
+                    ext.xent(c["logits"], dl, c["target"], loss, lse, am, M, V, ld, 1.0 / 7, U.IGNORE_INDEX, eps, z, ce)
+                    fin = torch.zeros(2, 2, 3, device="cuda")
+                    for i, (tg, n) in enumerate(((c["target"], 0.0), (None, 4.0))):
+                        ext.xent_finalize(loss, tg, n, fin[i][0])
+                        ext.xent_finalize(loss, tg, n, fin[i][1], ce)
+                    case["arg" if with_arg else "noarg"] = {"grad": dl, "loss": loss, "ce": ce, "lse": lse, "argmax": am,
+                                                            "finalize": fin}
+                dense = c["logits"][:, :V].contiguous()
+                lse = torch.logsumexp(dense.float(), 1)
+                dlb = torch.zeros_like(dense)
+                ext.xent_bwd(dense, dlb, c["target"], lse, torch.full((1,), 3.0, device="cuda"),
+                             torch.full((1,), 7.0, device="cuda"), U.IGNORE_INDEX, eps, z)
+                case["bwd"] = dlb
+                torch.cuda.synchronize()
+                name = f"{str(dtype)[6:]}.V{V}.ld{ld}.{'planted' if planted else 'randn'}.{'aux' if eps else 'plain'}"
+                out[name] = {k: ({a: (b.cpu() if b is not None else 0) for a, b in v.items()} if isinstance(v, dict)
+                                 else v.cpu()) for k, v in case.items()}
     return out
 
 
@@ -294,5 +433,6 @@ if __name__ == "__main__":
             print("MISMATCH", k)
         print(f"{len(a)} cases, {n} values compared, {len(bad)} mismatches")
         sys.exit(1 if bad else 0)
-    family = {"attn": attn, "norm": norm, "resnet": resnet, "gemm": gemm, "optim": optim}[sys.argv[1]]
+    family = {"attn": attn, "norm": norm, "colsum": colsum, "xent": xent, "resnet": resnet, "gemm": gemm,
+              "optim": optim}[sys.argv[1]]
     torch.save(family(*sys.argv[3:]), sys.argv[2])

@@ -28,6 +28,8 @@ Launcher branch -> the case that reaches it (check against the `if` ladders of t
                 16-B form CPL 1  D = 8, 200, 512   CPL 2  D = 520, 1024   CPL 4  D = 2048   CPL 8  D = 4096
                 else (D = 8192): refused;   CS true / false: with / without the dx column sums
                 row loop (fetch(row + nw)): M = 67 at 16 waves, D = 256, 768, 1024, 2048;
+                RTDC_NORM_BWD_VW4=0 (D = 256, 768 in the 16-B form: idle lanes, a partial chunk) and
+                RTDC_COLSUM_WIDE=0 (colsum_ws_kernel): a fresh child process, both knobs are read once;
                 grid capped at the resident slots: (M, D) = (9001, 768), (4101, 4096)
   attn_softmax  CPL 1  T = 8, 64     CPL 2  T = 520, 1024     CPL 4  T = 1032, 2048     CPL 8  T = 4096
                 else (T = 4104): refused;  causal and not, with and without lse, in and out of place
@@ -35,6 +37,10 @@ Launcher branch -> the case that reaches it (check against the `if` ladders of t
                 rope: Dh 16 / 64 / 128 (1, 4, 8 chunks per head), rotated and copied heads, tok % T wraps
                 (the second iteration of rope's stride loop needs 67 M elements and is not reached)
 """
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -85,11 +91,10 @@ def _norm_bwd(c, fwd, rms, want_sum):
     dg, db = (torch.full((D,), float("nan"), dtype=F32, device=DEV) for _ in range(2))
     dxsum = torch.full((D,), float("nan"), dtype=F32, device=DEV) if want_sum else None
     if rms:
-        _ext().rmsnorm_bwd(c["dy"], x, c["g"], fwd["rstd"], c["dres"], dx, ws, dg, dxsum, nw, False)
+        _ext().rmsnorm_bwd(c["dy"], x, c["g"], fwd["rstd"], c["dres"], dx, ws, dg, nw)
         out = {"dx": dx, "dgamma": dg}
     else:
-        _ext().layernorm_bwd(c["dy"], x, c["g"], fwd["mean"], fwd["rstd"], c["dres"], dx, ws, dg, db, dxsum, nw, False,
-                             False)
+        _ext().layernorm_bwd(c["dy"], x, c["g"], fwd["mean"], fwd["rstd"], c["dres"], dx, ws, dg, db, dxsum, nw, False)
         out = {"dx": dx, "dgamma": dg, "dbeta": db}
     if want_sum and not rms:
         out["dxsum"] = dxsum
@@ -136,6 +141,41 @@ def test_norm_backward_row_loop(monkeypatch, rms, M, D, waves):
             U.judge_norm(J, op, (M, D, "dres" if dres else "", "colsum" if want_sum else ""), c, 1e-5, rms,
                          {**fwd, **bw}, rows_per_wave=-(-M // nw))
     J.check()
+
+
+def _knobs_off_child():
+    """what test_norm_backward_knobs_off runs in its child process"""
+    from ray_torch_distributed_checkpoint_amd.ops import norm as N
+
+    assert os.environ["RTDC_NORM_BWD_VW4"] == "0" and os.environ["RTDC_COLSUM_WIDE"] == "0" and N._BWD_WAVES == 16
+    J = U.Judge()
+    for rms in (False, True):
+        for M, D in ((67, 256), (67, 768)):
+            for dres in (False, True):
+                c = U.norm_inputs(M, D, dres=dres, dev=DEV)
+                fwd = _norm_fwd(c, 1e-5, rms)
+                for want_sum in ((False,) if rms else (False, True)):
+                    bw, nw = _norm_bwd(c, fwd, rms, want_sum)
+                    assert nw == 16
+                    U.judge_norm(J, "rmsnorm" if rms else "layernorm",
+                                 (M, D, "dres" if dres else "", "colsum" if want_sum else "", "knobs off"), c, 1e-5, rms,
+                                 {**fwd, **bw}, rows_per_wave=-(-M // nw))
+    J.check()
+
+
+def test_norm_backward_knobs_off():
+    """RTDC_NORM_BWD_VW4=0 and RTDC_COLSUM_WIDE=0, which the library reads once per process, so in a
+    fresh child: D = 256 and 768 go through the 16-B form (64 and 32 of a chunk row's lanes idle, the
+    `c < nch` guard on a partial chunk) and every reduction through the two-launch colsum_ws_kernel;
+    LayerNorm and RMSNorm at M = 67 on 16 waves, with and without dres and the dx column sums,
+    judged as test_norm_backward_row_loop judges them"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, RTDC_NORM_BWD_VW4="0", RTDC_COLSUM_WIDE="0", RTDC_NORM_BWD_WAVES="16", PYTHONPATH=root)
+    r = subprocess.run([sys.executable, "-c", "from tests.test_row_kernels_gpu import _knobs_off_child as f; f()"],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count("ULP ") >= 12 * 2  # 12 backward calls, dx and dgamma at the least of each
 
 
 class _Producer(torch.autograd.Function):

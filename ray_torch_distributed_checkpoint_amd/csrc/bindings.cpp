@@ -8,6 +8,8 @@
 #include <ATen/hip/HIPContext.h>
 #include <pybind11/stl.h>
 
+#include <climits>
+
 #include "kernels/args.h"
 #include "runtime/ckpt_engine.cpp"
 #include "runtime/reducer.cpp"
@@ -323,8 +325,21 @@ static void rmsnorm_bwd(Tensor dy, Tensor x, Tensor g, Tensor rstd, c10::optiona
                             cur_stream()),
            "rmsnorm_bwd");
 }
+// what colsum and colsum_partial share: X is a bf16 / fp32 GPU matrix [M][N] with row stride ld whose storage
+// covers every row from its pointer (a view may start inside a row), ws an fp32 workspace of ws_rows x N
+static void check_colsum(const char* op, const Tensor& X, int64_t M, int64_t N, int64_t ld, const Tensor& ws,
+                         int64_t nblk, int64_t ws_rows) {
+  TORCH_CHECK(X.is_cuda() && ws.is_cuda(), op, ": X and ws must be GPU tensors");
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 || X.scalar_type() == at::kFloat, op, ": X must be bf16 or fp32");
+  TORCH_CHECK(M >= 1 && N >= 1 && nblk >= 1 && ld >= N && M <= INT_MAX && ld <= INT_MAX && nblk <= INT_MAX, op,
+              ": need M, N, nblk >= 1 and ld >= N");
+  const int64_t have = (int64_t)(X.storage().nbytes() / X.element_size()) - X.storage_offset();
+  TORCH_CHECK(have >= (M - 1) * ld + N, op, ": X holds fewer than (M - 1) * ld + N elements");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= ws_rows * N, op,
+              ": workspace must be contiguous fp32 of >= ", ws_rows, " x N elements");
+}
 static void colsum_partial(Tensor X, int64_t M, int64_t N, int64_t ld, Tensor ws, int64_t nblk) {
-  TORCH_CHECK(ws.numel() >= nblk * N && ws.scalar_type() == at::kFloat, "colsum_partial workspace too small");
+  check_colsum("colsum_partial", X, M, N, ld, ws, nblk, nblk);
   check_rc(rtdc_colsum_partial(X.data_ptr(), (int)M, (int)N, (int)ld, ws.data_ptr<float>(), (int)nblk,
                                X.scalar_type() == at::kBFloat16, cur_stream()),
            "colsum_partial");
@@ -355,7 +370,9 @@ static void colsum_multi(std::vector<Tensor> ws, std::vector<Tensor> out, std::v
 }
 static void colsum(Tensor X, int64_t M, int64_t N, int64_t ld, Tensor ws, int64_t nblk, Tensor out,
                    bool accumulate) {
-  TORCH_CHECK(ws.numel() >= (nblk + 64) * N, "colsum workspace too small");
+  check_colsum("colsum", X, M, N, ld, ws, nblk, nblk + 64);   // [nblk][N] partials + [64][N] level-2 rows
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= N,
+              "colsum: out must be a contiguous fp32 GPU tensor of >= N elements");
   check_rc(rtdc_colsum(X.data_ptr(), (int)M, (int)N, (int)ld, ws.data_ptr<float>(), (int)nblk,
                        out.data_ptr<float>(), accumulate, X.scalar_type() == at::kBFloat16, cur_stream()),
            "colsum");

@@ -8,6 +8,7 @@
 // float atomics).
 #include "gemm_common.h"
 
+#include <cstdint>
 #include <cstdlib>
 
 namespace rtdc {
@@ -354,7 +355,7 @@ struct ColsumJobs {
   int W[kMultiJobs];
   int D[kMultiJobs];
   int start[kMultiJobs + 1];
-  int accumulate;  // bit j: out_j += sum
+  unsigned accumulate;  // bit j: out_j += sum
   int n;
 };
 static_assert(sizeof(ColsumJobs) <= 4096, "kernel argument segment");
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(1024) void colsum_multi_kernel(ColsumJobs jobs) {
 #pragma unroll
   for (int i = 1; i < kMultiJobs; ++i) j += (i < jobs.n && b >= jobs.start[i]) ? 1 : 0;
   j = __builtin_amdgcn_readfirstlane(j);
-  colsum_wide_cols(jobs.ws[j], jobs.out[j], jobs.W[j], jobs.D[j], (b - jobs.start[j]) * 64, (jobs.accumulate >> j) & 1);
+  colsum_wide_cols(jobs.ws[j], jobs.out[j], jobs.W[j], jobs.D[j], (b - jobs.start[j]) * 64, (jobs.accumulate >> j) & 1u);
 }
 
 static bool colsum_wide_enabled() {
@@ -597,7 +598,7 @@ extern "C" int rtdc_colsum_multi(const float* const* ws, float* const* out, cons
     jobs.W[i] = W[i];
     jobs.D[i] = D[i];
     jobs.start[i] = blocks;
-    if (accumulate[i]) jobs.accumulate |= 1 << i;
+    if (accumulate[i]) jobs.accumulate |= 1u << i;
     blocks += (D[i] + 63) / 64;
   }
   jobs.start[n] = blocks;
@@ -609,7 +610,8 @@ extern "C" int rtdc_colsum_multi(const float* const* ws, float* const* out, cons
 // stage 1 of a column sum: the partial rows ws [nblk][N] of X [M][N]
 static void launch_colsum_partial(const void* X, int M, int N, int ld, float* ws, int nblk, int is_bf16,
                                   hipStream_t st) {
-  const bool vec = N % 8 == 0 && ld % 8 == 0;
+  // the 16-B loads need the pointer aligned too (a view that starts inside a row is not)
+  const bool vec = N % 8 == 0 && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
   const int rpb = (M + nblk - 1) / nblk;
   dim3 grid(nblk, (N + 511) / 512), block(256);
 #define CS(T, V) hipLaunchKernelGGL((colsum_partial_kernel<T, V>), grid, block, 0, st, (const T*)X, M, N, ld, rpb, ws)

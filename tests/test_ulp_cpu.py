@@ -26,7 +26,11 @@
   over, with every intermediate a normal number or zero; in float64 both references equal torch.optim.AdamW /
   SGD to 1e-12; `_torch_update` of FusedAdamW and FusedSGD (the CPU paths) is judged like a kernel; five
   AdamW and four SGD errors each leave the allowance; the whole-tensor yardstick of
-  tests/test_kernels_gpu.py accepts two of them at lr = 1e-3 and six, `eps_inside` among them, at 2^-15.
+  tests/test_kernels_gpu.py accepts two of them at lr = 1e-3 and six, `eps_inside` among them, at 2^-15;
+* reductions (the last section): on every `offset` case of the REDUCE_* tables the fp32 twin of the column-sum and
+  loss-finalize references, and the fp64 twin of the grad-norm sums against math.fsum, stay under their ceilings;
+  eight deliberate errors (U.REDUCE_MUTANTS) are each caught at every case where the mutated path is live - on
+  `ints` by a single differing bit, on `offset` by the allowance.
 """
 import pytest
 import torch
@@ -1110,3 +1114,188 @@ def test_dropout_mask_twin_and_references():
             J.rel("relu_dropout", (n, p, dy is not None), "y", None, r, t, r.abs().clamp_min(U.TINY), 3)
     assert U.relu_dropout_ref(F32, h, torch.ones(n, dtype=torch.bool), 0.0).equal(torch.relu(h))
     J.check()
+
+
+# ------------------------------------------------------------------------------- reductions
+def _reduce_jobs(gen, table, dtype, seed=0, base_fill=None):
+    """colsum_multi_ref jobs of a (W, D, accumulate) table; `base` is what the output holds before the launch"""
+    jobs = []
+    for j, (W, D, acc) in enumerate(table):
+        ws = U.reduce_gen(gen, (W, D), seed + 2 * j)
+        base = U.reduce_gen(gen, (D,), seed + 2 * j + 1) if acc or base_fill is None else torch.full((D,), base_fill)
+        jobs.append((ws, W, D, base, bool(acc)))
+    return jobs
+
+
+def _jobs_abs(jobs):
+    return [(ws.abs(), W, D, base.abs(), acc) for ws, W, D, base, acc in jobs]
+
+
+def test_reduce_generators_and_helpers():
+    """`ints` holds no zero and stays inside its bound; the partial reference puts every row into exactly one
+    block and leaves the blocks past M exactly 0; the counted R of the tables; `clip_ref` on its branches"""
+    v = U.reduce_gen("ints", (4160, 7), 1)
+    assert v.dtype == F32 and v.abs().min() == 1 and v.abs().max() == 64 and 4160 * 64 < 2 ** 24
+    assert torch.equal(v.bfloat16().float(), v)
+    g = U.reduce_gen("ints", (1000,), 2, bound=1 << 10)
+    assert g.abs().max() <= 1 << 10 and (1 << 20) * 16384 < 2 ** 53
+    for M, nblk, N, ld in U.reduce_partial_cases():
+        X = U.reduce_partial_input("ints", F32, M, N, ld, seed=M)
+        p = U.colsum_partial_ref(F64, X, M, N, ld, nblk)
+        assert p.shape == (nblk, N) and not p.isnan().any()
+        assert torch.equal(p.sum(0), X[:, :N].double().sum(0))
+        rpb = U.reduce_rpb(M, nblk)
+        assert not p[-(-M // rpb):].any()
+    assert [U.reduce_R_partial(M, nb) for M, nb in U.REDUCE_PARTIAL_MN] == [1, 1, 1, 5, 17]
+    assert [U.reduce_R_wide(W) for W in (1, 16, 17, 192, 193, 4096)] == [1, 1, 2, 12, 13, 256]
+    assert [U.reduce_ws_plan(W) for W in U.REDUCE_KNOBS_OFF_W + U.REDUCE_TWO_LAUNCH_W] == \
+        [(1, 1), (1, 17), (1, 63), (2, 32), (6, 33), (64, 65), (64, 65)]
+    assert U.reduce_R_ws(4097) == 17 + 16 and U.reduce_R_ws(63) == 16
+    assert 63 * 65 < 4097 <= 64 * 65 and 5 * 33 < 193   # the last stage-1 block is partial
+    assert U.clip_ref(4.0, 3.0, 1.0) == (6.0, U._f32(U._f32(1.0) / 6.000001))
+    assert U.clip_ref(4.0, 1.0, 5.0) == (2.0, 1.0) and U.clip_ref(0.0, 1.0, 1.0) == (0.0, 1.0)
+    t, c = U.clip_ref(float("nan"), 1.0, 1.0)
+    assert t != t and c != c
+    assert U.clip_ref(float("inf"), 1.0, 1.0) == (float("inf"), 0.0)
+    assert U.ulp_f32(1.0) == 2.0 ** -23 and U.ulp_f32(1.99) == 2.0 ** -23 and U.ulp_f32(0.75) == 2.0 ** -24
+    rows, n = U.gradnorm_chunks()
+    assert sorted({(s & 3, ln) for s, ln in rows}) == sorted((k, ln) for ln in U.REDUCE_GRADNORM_LENS for k in range(4))
+    assert all(a[0] + a[1] < b[0] for a, b in zip(rows, rows[1:])) and rows[-1][0] + rows[-1][1] <= n
+
+
+def test_twin_reductions():
+    """on every `offset` case of the REDUCE_* tables the fp32 twin (fp64 for the grad-norm sums) stays under its
+    ceiling"""
+    J = U.Judge()
+    for dtype in (U.BF16, F32):
+        for M, nblk, N, ld in U.reduce_partial_cases():
+            X = U.reduce_partial_input("offset", dtype, M, N, ld, seed=N)
+            a = (M, N, ld, nblk)
+            J.rel("colsum_part", (str(dtype)[6:],) + a, "ws", None, U.colsum_partial_ref(F64, X, *a),
+                  U.colsum_partial_ref(F32, X, *a), U.colsum_partial_ref(F64, X.abs(), *a).clamp_min(U.TINY),
+                  U.reduce_R_partial(M, nblk))
+    for W in U.REDUCE_WIDE_W + U.REDUCE_TWO_LAUNCH_W:
+        for D in U.REDUCE_WIDE_D:
+            for acc in (False, True):
+                (job,) = _reduce_jobs("offset", [(W, D, acc)], F32, seed=W + D)
+                (sc,) = U.colsum_multi_ref(F64, _jobs_abs([job]))
+                for name, R in (("wide", U.reduce_R_wide(W)), ("ws", U.reduce_R_ws(W))):
+                    J.rel("colsum_" + name, (W, D, acc), "out", None, U.colsum_rows_ref(F64, *job),
+                          U.colsum_rows_ref(F32, *job), sc, R + acc)
+    for table in (U.REDUCE_MULTI_5, U.REDUCE_MULTI_32):
+        jobs = _reduce_jobs("offset", table, F32, seed=9)
+        for j, (r, t, sc) in enumerate(zip(U.colsum_multi_ref(F64, jobs), U.colsum_multi_ref(F32, jobs),
+                                           U.colsum_multi_ref(F64, _jobs_abs(jobs)))):
+            J.rel("colsum_multi", (len(table), j) + table[j], "out", None, r, t, sc, U.reduce_R_wide(table[j][0]) + table[j][2])
+    rows, n = U.gradnorm_chunks()
+    g = U.reduce_gen("offset", (n,), 3)
+    ex, tw = U.gradnorm_partial_exact(g, rows), U.gradnorm_partial_ref(F64, g, rows)
+    for i, (s, ln) in enumerate(rows):
+        J.rel64("gradnorm_part", (s & 3, ln), "partial", None, ex[i], tw[i], ex[i], U.reduce_R_gradnorm(ln))
+    for k in U.REDUCE_FINALIZE_N[1:]:
+        p = U.reduce_gen("offset", (k,), k, F64).square()
+        ex = torch.tensor(U.fsum64(p), dtype=F64)
+        J.rel64("gradnorm_fin", (k,), "local", None, ex, p.sum(), ex, U.reduce_R_finalize(k))
+    for M in U.REDUCE_XENT_M:
+        loss, ce = U.reduce_gen("offset", (M,), M), U.reduce_gen("offset", (M,), M + 1)
+        for form in U.REDUCE_XENT_FORMS:
+            tg = U.xent_finalize_targets(M, form)
+            a = (loss, ce, tg, M + 2.0)
+            r = U.xent_finalize_ref(F64, *a)
+            J.rel("xent_finalize", (M, form), "out", None, r, U.xent_finalize_ref(F32, *a),
+                  U.xent_finalize_scale(loss, ce, r[1]), U.reduce_R_finalize(M) + 1)
+    J.check()
+
+
+def _reduce_caught(gen, m, r, t, scale, R, rel64=False):
+    """the float64 mutant m, taken for a kernel output: on `ints` it is not the reference bit for bit, on
+    `offset` it is outside the allowance (a NaN is caught by both)"""
+    if gen == "ints":
+        assert torch.equal(t.double(), r.double())   # the honest twin is exact
+        return not torch.equal(m.double(), r.double())
+    allow = (U.allow_f64 if rel64 else U.allow_f32)(U.rel_err(t, r, scale), R)
+    mk = m if rel64 else m.float()
+    return not U.rel_err(mk, r, scale) <= allow
+
+
+@pytest.mark.parametrize("gen", U.REDUCE_GENS)
+@pytest.mark.parametrize("mutant", ["drop_last_row", "no_min", "pad_read"])
+def test_mutant_colsum_partial(mutant, gen):
+    """live: everywhere / where nblk x rpb > M (a block's range leaves the matrix) / where ld > N"""
+    live = 0
+    for dtype in (U.BF16, F32):
+        for M, nblk, N, ld in U.reduce_partial_cases():
+            rpb = U.reduce_rpb(M, nblk)
+            if (mutant == "no_min" and nblk * rpb == M) or (mutant == "pad_read" and ld == N):
+                continue
+            live += 1
+            X = U.reduce_partial_input(gen, dtype, M, N, ld, seed=N + M, extra_rows=nblk * rpb - M, pad=1.0)
+            a = (M, N, ld, nblk)
+            r, t = U.colsum_partial_ref(F64, X, *a), U.colsum_partial_ref(F32, X, *a)
+            sc = U.colsum_partial_ref(F64, X.abs(), *a).clamp_min(U.TINY)
+            m = U.colsum_partial_ref(F64, X, *a, mutant=mutant)
+            assert _reduce_caught(gen, m, r, t, sc, U.reduce_R_partial(M, nblk)), (mutant, dtype, a)
+            assert not _reduce_caught(gen, t.double(), r, t, sc, U.reduce_R_partial(M, nblk))
+    assert live == {"drop_last_row": 210, "no_min": 168, "pad_read": 140}[mutant]
+
+
+@pytest.mark.parametrize("gen", U.REDUCE_GENS)
+def test_mutant_colsum_accumulate_and_jobs(gen):
+    """`acc_ignored` at every accumulating case of the wide / two-launch table and every accumulating job of the
+    two job tables; `job_shift` at every job of both tables"""
+    for W in U.REDUCE_WIDE_W + U.REDUCE_TWO_LAUNCH_W:
+        for D in U.REDUCE_WIDE_D:
+            (job,) = _reduce_jobs(gen, [(W, D, 1)], F32, seed=W + D)
+            (sc,) = U.colsum_multi_ref(F64, _jobs_abs([job]))
+            r, t = U.colsum_rows_ref(F64, *job), U.colsum_rows_ref(F32, *job)
+            m = U.colsum_rows_ref(F64, *job, mutant="acc_ignored")
+            R = max(U.reduce_R_wide(W), U.reduce_R_ws(W)) + 1
+            assert _reduce_caught(gen, m, r, t, sc, R), (W, D)
+    for table in (U.REDUCE_MULTI_5, U.REDUCE_MULTI_32):
+        jobs = _reduce_jobs(gen, table, F32, seed=9, base_fill=float("nan"))
+        r, t, sc = U.colsum_multi_ref(F64, jobs), U.colsum_multi_ref(F32, jobs), U.colsum_multi_ref(F64, _jobs_abs(jobs))
+        for mutant in ("acc_ignored", "job_shift"):
+            m = U.colsum_multi_ref(F64, jobs, mutant=mutant)
+            for j, (W, D, acc) in enumerate(table):
+                if mutant == "job_shift" or acc:
+                    assert _reduce_caught(gen, m[j], r[j], t[j], sc[j], U.reduce_R_wide(W) + acc), (mutant, len(table), j)
+    (one,) = _reduce_jobs(gen, [(17, 64, 1)], F32)   # a single job has no neighbour: `job_shift` is not live
+    assert torch.equal(U.colsum_multi_ref(F64, [one], mutant="job_shift")[0], U.colsum_multi_ref(F64, [one])[0])
+
+
+@pytest.mark.parametrize("gen", U.REDUCE_GENS)
+def test_mutant_gradnorm_partial(gen):
+    """`tail_dropped` at every chunk on the vector path (start & 3 == 0) whose length is no multiple of 4;
+    `f32_acc` at every chunk on `offset`.  `ints` is blind to `f32_acc` by construction wherever the sum stays
+    below 2^24 - integer squares add exactly in fp32 too - so it is not asked to catch it."""
+    rows, n = U.gradnorm_chunks()
+    g = U.reduce_gen(gen, (n,), 3, bound=1 << 10)
+    ex, tw = U.gradnorm_partial_exact(g, rows), U.gradnorm_partial_ref(F64, g, rows)
+    tail, acc32 = U.gradnorm_partial_ref(F64, g, rows, mutant="tail_dropped"), U.gradnorm_partial_ref(F32, g, rows)
+    live = 0
+    for i, (s, ln) in enumerate(rows):
+        R = U.reduce_R_gradnorm(ln)
+        assert not _reduce_caught(gen, tw[i], ex[i], tw[i], ex[i], R, rel64=True)
+        if s % 4 == 0 and ln % 4:
+            live += 1
+            assert _reduce_caught(gen, tail[i], ex[i], tw[i], ex[i], R, rel64=True), (s, ln)
+        else:
+            assert torch.equal(tail[i], tw[i])
+        if gen == "offset":
+            assert _reduce_caught(gen, acc32[i].double(), ex[i], tw[i], ex[i], R, rel64=True), (s, ln)
+    assert live == 7
+
+
+@pytest.mark.parametrize("gen", U.REDUCE_GENS)
+def test_mutant_xent_finalize_no_clamp(gen):
+    """live where every target is ignored (the count is 0): at every M"""
+    for M in U.REDUCE_XENT_M:
+        loss, ce = U.reduce_gen(gen, (M,), M), U.reduce_gen(gen, (M,), M + 1)
+        for form in U.REDUCE_XENT_FORMS:
+            a = (loss, ce, U.xent_finalize_targets(M, form), M + 2.0)
+            r, t, m = U.xent_finalize_ref(F64, *a), U.xent_finalize_ref(F32, *a), U.xent_finalize_ref(F64, *a, mutant="no_clamp")
+            sc = U.xent_finalize_scale(loss, ce, r[1])
+            if form == "all_ignored":
+                assert r[1] == 1 and _reduce_caught("offset", m, r, t, sc, U.reduce_R_finalize(M) + 1), M
+            else:
+                assert torch.equal(m, r)

@@ -51,6 +51,11 @@ The optimizer section (the last) does it for optim.hip and the arithmetic of ele
 and `sgd_ref` (one step in the kernels' order, every scalar rounded to fp32 as a launcher receives it),
 `optim_inputs` and the chunk tables, `embed_ref` / `embed_bwd_ref`, and the dropout mask from the Philox
 twin of ops/random.py; tests/test_optim_ulp_gpu.py and tests/test_elementwise_ulp_gpu.py run the kernels.
+
+The reductions section (the last) covers the stand-alone reduction kernels - the column sums of norm.hip, the
+gradient-norm kernels of optim.hip, the loss finalisation of xent.hip: references that mirror each kernel's
+partition, an integer generator on which every summation order is exact (the kernel must match bit for bit) and
+an offset one judged by `Judge.rel` / `Judge.rel64`; tests/test_reduce_ulp_gpu.py runs the kernels.
 """
 from __future__ import annotations
 
@@ -2139,3 +2144,243 @@ def relu_dropout_ref(dtype, h, keep, p, dy=None):
     scale = one / (one - p_) if p > 0 else one
     src = (h if dy is None else dy).to(dtype)
     return torch.where(keep & (h > 0), src * scale, torch.zeros_like(src))
+
+
+# ------------------------------------------------------------------------------- reductions
+# The stand-alone reduction kernels: colsum_partial_kernel, colsum_ws_kernel, colsum_wide_kernel and
+# colsum_multi_kernel (norm.hip), gradnorm_partial / finalize / combine_kernel (optim.hip), xent_finalize_kernel
+# and xent_alpha_kernel (xent.hip).  A reference here mirrors a kernel's PARTITION - which rows, columns, chunk
+# elements and jobs land in which output - and not its summation order: in float64 it is the reference, in
+# float32 the twin.  Two generators:
+# * `ints`: non-zero integers small enough that every partial and total sum is exactly representable in the
+#   kernel's accumulator (fp32: |x| <= 64 and rows x 64 < 2^24, the tables stop at 4160 rows; the fp64 grad-norm
+#   sums: |x| <= 2^10, squares <= 2^20, 2^14 of them).  Any summation order is then exact, so a kernel must equal
+#   the float64 reference bit for bit, and one dropped, duplicated or misplaced element changes the result
+#   (no element is zero).
+# * `offset`: randn + 1, judged with `Judge.rel` against the fp64 sum of |terms| with `allow_f32(twin, R)`, R the
+#   terms a lane adds serially (the reduce_R_* helpers, each counted from the kernel named next to it).  The
+#   grad-norm kernels sum in fp64: `Judge.rel64`, the same form with 2^-53 for 2^-24, against `math.fsum` of the
+#   squares (the product of two fp32 numbers is exact in fp64), the twin being torch's float64 sum.
+# tests/test_ulp_cpu.py holds the twin condition and the mutants, tests/test_reduce_ulp_gpu.py runs the kernels.
+REDUCE_MUTANTS = ("drop_last_row", "no_min", "pad_read", "tail_dropped", "acc_ignored", "job_shift", "no_clamp",
+                  "f32_acc")
+REDUCE_GENS = ("ints", "offset")
+TWIN_REL64_CEIL = 2.0 ** -47   # the fp64 twin: the same 2^6 roundings as TWIN_REL_CEIL allows in fp32
+
+REDUCE_PARTIAL_MN = ((1, 1), (3, 8), (9, 8), (67, 4), (261, 4))   # (M, nblk): (3, 8) and (9, 8) leave empty blocks
+REDUCE_PARTIAL_N = (8, 72, 100, 7, 512, 520, 1032)                # 100 and 7: the scalar arm
+REDUCE_PARTIAL_PAD = (0, 8, 3)                                    # ld - N; 3 forces the scalar arm
+REDUCE_WIDE_W = (1, 15, 16, 17, 191, 192, 193, 385, 4096)         # 16 waves, 16 * kWideU = 192 rows a step
+REDUCE_WIDE_D = (1, 63, 64, 65, 200)
+REDUCE_TWO_LAUNCH_W = (4097, 4160)                                # > kWideMaxRows: S = 64 stage-1 blocks of R = 65
+REDUCE_KNOBS_OFF_W = (1, 17, 63, 64, 193)                         # RTDC_COLSUM_WIDE=0: S = 1, 1, 1, 2, 6
+REDUCE_MULTI_5 = ((192, 65, 0), (1, 1, 1), (17, 64, 1), (4096, 200, 0), (3, 130, 1))   # (W, D, accumulate)
+REDUCE_MULTI_32 = tuple((5, 8 + j, int(j % 2 == 1 or j == 31)) for j in range(32))
+REDUCE_GRADNORM_LENS = (1, 2, 3, 4, 5, 1023, 1024, 1025, 4099, 16384)
+REDUCE_FINALIZE_N = (0, 1, 1023, 1024, 1025, 5000)
+REDUCE_GRAD_SCALES = (1.0, 0.125, 3.0)
+REDUCE_WORLDS = (1, 2, 8)
+REDUCE_XENT_M = (1, 1023, 1024, 1025, 3000)
+REDUCE_XENT_FORMS = ("some_ignored", "none_ignored", "all_ignored", "fixed_n")
+
+
+def reduce_rpb(M, nblk):
+    """rows per block of launch_colsum_partial: rpb = (M + nblk - 1) / nblk"""
+    return -(-M // nblk)
+
+
+def reduce_R_partial(M, nblk):
+    """colsum_partial_kernel: `for (r = r0 + wv; r < r1; r += 4)` - a lane adds every 4th row of its block"""
+    return -(-reduce_rpb(M, nblk) // 4)
+
+
+def reduce_R_wide(W):
+    """colsum_wide_cols: wave wv adds rows wv, wv + 16, ... into one accumulator"""
+    return -(-W // 16)
+
+
+def reduce_ws_plan(W):
+    """colsum_ws_reduce without the wide kernel -> (S, R): S = clamp(W / 32, 1, 64) stage-1 blocks of R rows"""
+    S = min(64, max(1, W // 32))
+    return S, -(-W // S)
+
+
+def reduce_R_ws(W):
+    """colsum_ws_kernel: the 4 waves stride the R rows of a block (`w = r0 + wv`, steps of 4); two stages
+    (S > 1) add the S stage-1 rows the same way"""
+    S, R = reduce_ws_plan(W)
+    return -(-R // 4) + (-(-S // 4) if S > 1 else 0)
+
+
+def reduce_R_gradnorm(ln):
+    """gradnorm_partial_kernel: lane t takes elements (or quads) t, t + 256, ..."""
+    return -(-ln // 256)
+
+
+def reduce_R_finalize(n):
+    """gradnorm_finalize_kernel / xent_finalize_kernel: `for (i = threadIdx.x; i < n; i += 1024)`"""
+    return -(-n // 1024)
+
+
+def allow_f64(t_rel: float, R: int) -> float:
+    """`allow_f32` for a kernel that accumulates in fp64"""
+    return max(16.0 * t_rel, (R + 16) * 2.0 ** -53)
+
+
+def ulp_f32(v: float) -> float:
+    """the spacing of fp32 numbers in the binade of the normal number v"""
+    return 2.0 ** (math.frexp(abs(v))[1] - 1 - 23)
+
+
+def _judge_rel64(self, op, shape, what, out, ref64, twin, scale, R):
+    t = rel_err(twin, ref64, scale)
+    self._note(op, shape, what, "rel64", None if out is None else rel_err(out, ref64, scale), t, allow_f64(t, R),
+               TWIN_REL64_CEIL)
+
+
+Judge.rel64 = _judge_rel64
+
+
+def reduce_gen(gen, shape, seed, dtype=F32, dev="cpu", bound=64):
+    """`ints`: integers in [-bound, -1] u [1, bound]; `offset`: randn + 1 (rounded to `dtype` once)"""
+    g = torch.Generator().manual_seed(seed)
+    if gen == "ints":
+        v = torch.randint(1, bound + 1, shape, generator=g) * (2 * torch.randint(0, 2, shape, generator=g) - 1)
+        return v.to(dtype).to(dev)
+    assert gen == "offset"
+    return (torch.randn(shape, generator=g, dtype=F64 if dtype == F64 else F32) + 1.0).to(dtype).to(dev)
+
+
+def colsum_partial_ref(dtype, X, M, N, ld, nblk, mutant=""):
+    """-> [nblk][N]: row x = the sum of rows [x rpb, min(M, (x + 1) rpb)) of X[:, :N]; a block past M is exactly
+    0.  X is the 2-D view the kernel is given (its row stride is the kernel's ld; columns >= N are padding).  The
+    `no_min` mutant reads the rows X holds past M, as the kernel would read what follows the matrix."""
+    assert X.dim() == 2 and X.shape[0] >= M and X.shape[1] >= N and ld >= N
+    rpb = reduce_rpb(M, nblk)
+    rows = min(nblk * rpb, X.shape[0]) if mutant == "no_min" else M
+    v = X[:rows, :N].to(dtype)
+    if mutant == "drop_last_row":   # `r < r1 - 1`
+        r = torch.arange(rows, device=X.device)
+        v = v * (~((r % rpb == rpb - 1) | (r == M - 1))).to(dtype)[:, None]
+    if mutant == "pad_read":        # the last column also takes the first padding column
+        v = torch.cat([v[:, :N - 1], v[:, N - 1:] + X[:rows, N:N + 1].to(dtype)], 1)
+    v = torch.cat([v, torch.zeros(nblk * rpb - rows, N, dtype=dtype, device=X.device)])
+    return v.view(nblk, rpb, N).sum(1)
+
+
+def colsum_rows_ref(dtype, ws, W, D, base=None, accumulate=False, mutant=""):
+    """out[d] (+)= sum over the W rows of ws [W][D] (colsum_ws_kernel / colsum_wide_cols); `base` is what out
+    held before the launch"""
+    s = ws[:W, :D].to(dtype).sum(0)
+    return s + base[:D].to(dtype) if accumulate and mutant != "acc_ignored" else s
+
+
+def colsum_multi_ref(dtype, jobs, mutant=""):
+    """jobs [(ws, W, D, base, accumulate)] -> the n outputs of one colsum_multi launch"""
+    outs = [colsum_rows_ref(dtype, *j, mutant=mutant) for j in jobs]
+    if mutant == "job_shift":   # job j's columns land in job j + 1's output (the rest keeps what it held)
+        n, shifted = len(jobs), []
+        for j, job in enumerate(jobs):
+            prev, k = outs[j - 1], min(job[2], jobs[j - 1][2])
+            keep = job[3][:job[2]].to(dtype).clone()
+            keep[:k] = prev[:k]
+            shifted.append(keep)
+        return shifted if n > 1 else outs
+    return outs
+
+
+def gradnorm_chunks(lens=REDUCE_GRADNORM_LENS):
+    """[(start, len)]: every length at start & 3 = 0, 1, 2, 3, gaps of 4 to 7 elements between the chunks;
+    -> the table and the length of the gradient buffer"""
+    rows, at = [], 0
+    for ln in lens:
+        for k in range(4):
+            at = (at + 3) // 4 * 4 + 4 + k
+            rows.append((at, ln))
+            at += ln
+    return rows, at + 5
+
+
+def gradnorm_partial_ref(dtype, g, chunks, mutant=""):
+    """partial[ci] = the sum of squares of chunk ci's elements, squared and added in `dtype` (float64: what the
+    kernel does, the twin of `gradnorm_partial_exact`; float32: the `f32_acc` mutant)"""
+    out = []
+    for s, ln in chunks:
+        if mutant == "tail_dropped" and s % 4 == 0:   # the vector path without `if (i < c.len)`
+            ln -= ln % 4
+        out.append(g[s:s + ln].to(dtype).square().sum())
+    return torch.stack(out)
+
+
+def gradnorm_partial_exact(g, chunks):
+    """the correctly rounded sums (math.fsum of the exact fp64 squares), float64 on the CPU"""
+    gl = g.double().cpu().tolist()
+    return torch.tensor([math.fsum(x * x for x in gl[s:s + ln]) for s, ln in chunks], dtype=F64)
+
+
+def fsum64(v):
+    return math.fsum(v.double().cpu().tolist())
+
+
+def clip_ref(total_sq, grad_scale, max_norm, total=None):
+    """`write_clip` of optim.hip in its fp32 arithmetic -> (total_norm, coef) as Python floats holding fp32
+    values: total = grad_scale * (float)sqrt(sum); c = max_norm / (total + 1e-6f); coef = c < 1 ? c : (c != c ? c
+    : 1).  `total`: take the kernel's own total_norm in place of the first line."""
+    f = lambda x: torch.tensor(x, dtype=F32)   # noqa: E731
+    if total is None:
+        total = f(grad_scale) * torch.tensor(total_sq, dtype=F64).sqrt().float()
+    else:
+        total = f(total)
+    c = f(max_norm) / (total + f(1e-6))
+    coef = c if bool(c < 1) else (c if bool(c != c) else f(1.0))
+    return total.item(), coef.item()
+
+
+def xent_finalize_ref(dtype, loss, ce, target, fixed_n, mutant=""):
+    """out[0] = sum(loss) / n, out[1] = n, out[2] = sum(ce) / n (ce given); n = max(number of targets that are
+    not IGNORE_INDEX, 1), or fixed_n without targets.  In float32 the quotient is the fp32 division the kernel
+    performs; on `ints` its operands are exact, so it is the kernel's result bit for bit."""
+    if target is None:
+        n = torch.tensor(_f32(fixed_n), dtype=dtype, device=loss.device)
+    else:
+        n = (target != IGNORE_INDEX).to(dtype).sum()
+        if mutant != "no_clamp":
+            n = n.clamp_min(1.0)
+    out = [loss.to(dtype).sum() / n, n]
+    if ce is not None:
+        out.append(ce.to(dtype).sum() / n)
+    return torch.stack(out)
+
+
+def xent_finalize_scale(loss, ce, n):
+    """the fp64 sums of |terms| over the divisor, per output (out[1] is a count: exact)"""
+    s = [loss.double().abs().sum() / n, torch.tensor(1.0, dtype=F64, device=loss.device)]
+    if ce is not None:
+        s.append(ce.double().abs().sum() / n)
+    return torch.stack(s).clamp_min(TINY)
+
+
+def xent_finalize_targets(M, form, seed=0, dev="cpu"):
+    """int64 targets for REDUCE_XENT_FORMS (None for `fixed_n`): every third ignored (from row 1 on, so M = 1
+    keeps its row), none, all"""
+    if form == "fixed_n":
+        return None
+    t = torch.randint(0, 1000, (M,), generator=torch.Generator().manual_seed(seed))
+    if form == "some_ignored":
+        t[1::3] = IGNORE_INDEX
+    elif form == "all_ignored":
+        t[:] = IGNORE_INDEX
+    return t.to(dev)
+
+
+def reduce_partial_cases():
+    """(M, nblk, N, ld) of the colsum_partial table"""
+    return [(M, nblk, N, N + pad) for M, nblk in REDUCE_PARTIAL_MN for N in REDUCE_PARTIAL_N for pad in REDUCE_PARTIAL_PAD]
+
+
+def reduce_partial_input(gen, dtype, M, N, ld, seed=0, dev="cpu", extra_rows=0, pad=float("nan")):
+    """X [M + extra_rows][ld] with NaN (or `pad`) in the padding columns; the data of the extra rows is 1"""
+    X = reduce_gen(gen, (M + extra_rows, ld), seed, dtype, dev)
+    X[M:] = 1.0
+    X[:, N:] = pad
+    return X

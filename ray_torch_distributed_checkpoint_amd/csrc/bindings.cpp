@@ -123,6 +123,11 @@ int rtdc_flash_fwd_doc(const void* qkv, void* out, float* lse, const int* doc_st
 int rtdc_flash_bwd_doc(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                        const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv, int Dh, float scale,
                        float* cs_ws, float* part, int qs, hipStream_t st);
+int rtdc_flash_fwd_win(const void* qkv, void* out, float* lse, int window, const int* doc_start, const int* doc_end,
+                       int B, int T, int H, int Hkv, int Dh, float scale, hipStream_t st);
+int rtdc_flash_bwd_win(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                       int window, const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv, int Dh,
+                       float scale, float* cs_ws, float* part, int qs, hipStream_t st);
 int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, const int* doc_start, int ntok, int T,
                   int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st);
 int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st);
@@ -784,6 +789,49 @@ static void flash_bwd_doc(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tenso
                               qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
            "flash_bwd_doc");
 }
+// sliding window (row q attends to its last `window` keys), with or without a document layout:
+// doc_start / doc_end are both given or both None
+static void check_window(const Tensor& qkv, int64_t window, const c10::optional<Tensor>& start,
+                         const c10::optional<Tensor>& end, int64_t B, int64_t T, const char* what) {
+  TORCH_CHECK(window >= 1, what, ": window must be >= 1, got ", window);
+  TORCH_CHECK(start.has_value() == end.has_value(), what, ": doc start / end are given together or not at all");
+  if (start.has_value()) check_docs(qkv, *start, *end, B, T, what);
+}
+static void flash_fwd_win(Tensor qkv, Tensor out, Tensor lse, int64_t window, c10::optional<Tensor> doc_start,
+                          c10::optional<Tensor> doc_end, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh,
+                          double scale) {
+  check_dev(qkv, "qkv");
+  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd_win: contiguous tensors expected");
+  check_window(qkv, window, doc_start, doc_end, B, T, "flash_fwd_win");
+  check_rc(rtdc_flash_fwd_win(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)std::min(window, T),
+                              doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
+                              doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H,
+                              (int)Hkv, (int)Dh, (float)scale, cur_stream()),
+           "flash_fwd_win");
+}
+static void flash_bwd_win(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, int64_t window,
+                          c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end, int64_t B, int64_t T,
+                          int64_t H, int64_t Hkv, int64_t Dh, double scale, c10::optional<Tensor> cs_ws,
+                          c10::optional<Tensor> part, int64_t qs) {
+  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd_win: contiguous tensors expected");
+  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd_win: qs must divide the GQA group size");
+  check_window(qkv, window, doc_start, doc_end, B, T, "flash_bwd_win");
+  if (qs > 1)
+    TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
+                    part->numel() >= qs * B * T * Hkv * 2 * Dh,
+                "flash_bwd_win: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
+  if (cs_ws.has_value())
+    TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
+                    cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
+                "flash_bwd_win: cs_ws fp32 [B*T/16][W]");
+  check_rc(rtdc_flash_bwd_win(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
+                              delta.data_ptr<float>(), dqkv.data_ptr(), (int)std::min(window, T),
+                              doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
+                              doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H,
+                              (int)Hkv, (int)Dh, (float)scale, cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
+                              qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
+           "flash_bwd_win");
+}
 // flags uint8 [B, T] (non-zero: a document starts here; position 0 always does) -> start / end
 static void doc_layout(Tensor flags, Tensor start, Tensor end) {
   TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kByte && flags.is_contiguous() && flags.dim() == 2,
@@ -1360,6 +1408,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_bwd_doc", &flash_bwd_doc, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
         py::arg("delta"), py::arg("dqkv"), py::arg("doc_start"), py::arg("doc_end"), py::arg("B"), py::arg("T"),
         py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
+        py::arg("part") = py::none(), py::arg("qs") = 1);
+  m.def("flash_fwd_win", &flash_fwd_win, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("window"),
+        py::arg("doc_start"), py::arg("doc_end"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Hkv"),
+        py::arg("Dh"), py::arg("scale"));
+  m.def("flash_bwd_win", &flash_bwd_win, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("delta"), py::arg("dqkv"), py::arg("window"), py::arg("doc_start"), py::arg("doc_end"), py::arg("B"),
+        py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
         py::arg("part") = py::none(), py::arg("qs") = 1);
   m.def("doc_layout", &doc_layout);
   m.def("synth_doc_flags", &synth_doc_flags);

@@ -12,7 +12,7 @@
 // columns per 16-lane group).
 //
 // A wave owns G in {1, 2} 16-row groups, so a block (4 waves) covers 64 G query rows or keys; tiles
-// stay 64 rows.  The forward and dQ are one kernel each, a template over <DH, NS, DOC, G>; dK/dV is
+// stay 64 rows.  The forward and dQ are one kernel each, a template over <DH, NS, MASK, G>; dK/dV is
 // still a pair, bwd_dkdv_kernel (G = 1) and bwd_dkdv2_kernel (G = 2), see the note above them.
 //   fwd_kernel     : block = 64 G query rows of one (b, h); K/V tiles of 64 keys streamed
 //                    through LDS by global_load_lds; online softmax in the log2 domain; writes O
@@ -29,13 +29,26 @@
 // Requires T % 64 == 0 and Dh in {64, 128}; G = 2 needs T % 128 == 0.  Which G runs: the
 // launchers at the end of the file (RTDC_FA_FWD / RTDC_FA_DQ / RTDC_FA_DKDV).
 //
-// DOC = true (packed sequences, rtdc_flash_fwd_doc / rtdc_flash_bwd_doc): row q attends to the
+// The mask is the template parameter MASK (MASK_NONE / MASK_DOC / MASK_WIN); in the kernels
+// DOC = (MASK != MASK_NONE) means "the row has a low bound", WIN = (MASK == MASK_WIN) how the
+// bound is made.
+//
+// DOC (packed sequences, rtdc_flash_fwd_doc / rtdc_flash_bwd_doc): row q attends to the
 // keys doc_start[q] <= key <= q of its own document.  The query-row kernels (fwd, dQ) start the
 // key-tile loop at doc_start[first row of the block] / 64 and mask key < doc_start[q] on the
 // tiles that begin before the document of the wave's last row; the key-row kernels (dK/dV) use
 // the equivalent q >= doc_end[key] per key lane and end the query-tile loop with the document
 // of the block's last key.  Everything DOC adds is under `if constexpr (DOC)`: the plain
 // instantiations are the code they were (profiles/attn_doc_mask_isa.txt).
+//
+// WIN (sliding window a.window = W >= 1, rtdc_flash_fwd_win / rtdc_flash_bwd_win): row q attends
+// to its last W keys, inside its document when a layout is given (doc_start / doc_end may be
+// null): lo[q] = max(start[q], q - W + 1), seen by dK/dV as hi[key] = min(end[key], key + W).
+// Both are non-decreasing with lo[q] <= q < hi[q], which is all the DOC loops rely on, so WIN
+// only changes the prologues (row_lo / key_hi: the bound is arithmetic on the row index, and
+// without a layout nothing is loaded) and the loops skip the tiles outside the band as they
+// skip those outside a document.  The plain and DOC instantiations are the code they were
+// (profiles/attn_window_isa.txt).
 //
 // Pipelining (all three loops): the streamed tiles (K/V for fwd and dQ; Q, dO and the 64
 // LSE / delta values of a query block for dK/dV) go through an NS-slot LDS ring with NS-1
@@ -80,12 +93,35 @@ struct Args {
   // part [qs][B*T][Hkv][2*Dh]; dkdv_reduce_kernel sums them in qsub order (deterministic)
   float* part;
   int qs;
+  // WIN kernels only: sliding window, 1 <= window <= T (the launchers clamp); doc_start / doc_end
+  // may then be null (no documents).  (It sits in what was padding after qs: the kernel arguments
+  // of the other kernels keep their size and offsets)
+  int window;
   // document layout of packed sequences (DOC kernels only; ops/attention.py DocLayout): int32
   // [B, T], start[b, t] = first token of t's document, end[b, t] = one past its last.  Both are
   // non-decreasing along t, constant within a document, start[t] <= t < end[t]; never validated
   const int* doc_start;
   const int* doc_end;
 };
+
+// the mask of a pass kernel (template parameter MASK)
+constexpr int MASK_NONE = 0, MASK_DOC = 1, MASK_WIN = 2;
+
+// low bound of row (b, q) / high bound of key (b, key) under MASK_DOC and MASK_WIN.  The null
+// test of the layout pointers is uniform over the grid; q and key may be scalar (the loop bounds
+// of a block) or per lane.
+template <bool WIN>
+__device__ __forceinline__ int row_lo(const Args& a, int b, int q) {
+  if constexpr (!WIN) return a.doc_start[(long long)b * a.T + q];
+  const int lo = max(q - a.window + 1, 0);
+  return a.doc_start ? max(a.doc_start[(long long)b * a.T + q], lo) : lo;
+}
+template <bool WIN>
+__device__ __forceinline__ int key_hi(const Args& a, int b, int key) {
+  if constexpr (!WIN) return a.doc_end[(long long)b * a.T + key];
+  const int hi = min(key + a.window, a.T);
+  return a.doc_end ? min(a.doc_end[(long long)b * a.T + key], hi) : hi;
+}
 
 // column sums over a wave's 16 rows of its stored fragment values v (lane = row (lane & 15) x
 // 4 columns 4g..4g+3 of each 16-column block d): one partial row per 16-row group
@@ -280,8 +316,9 @@ __device__ __forceinline__ void store_rows_bf16(bf16_t* row, const f32x4 (&v)[DT
 // instead of 1252 instructions) - and fwd_kernel<64, 2, false, 1> is GPT-2's production forward.
 
 // ------------------------------------------------------------------------------ forward
-template <int DH, int NS, bool DOC, int G>
+template <int DH, int NS, int MASK, int G>
 __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
+  constexpr bool DOC = MASK != MASK_NONE, WIN = MASK == MASK_WIN;
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, BLK = 64 * G;
   constexpr int TILE = 64 * DH * 2, PER = DH / 16;  // PER: DMA instructions per wave and tile
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];  // K[NS], V[NS]
@@ -306,9 +343,10 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
   tr_lane_offsets<DH>(troff, lane);
   const int nkb = (qb + 1) * G;
   // DOC: the first key tile any row of the block attends to (start is non-decreasing, so the
-  // block's first row has the minimum) - a scalar load, ahead of the prologue DMAs
+  // block's first row has the minimum) - a scalar load, ahead of the prologue DMAs; WIN without
+  // a layout: scalar arithmetic on the block index
   int kb_lo = 0;
-  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BLK]) / BKV;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(row_lo<WIN>(a, b, qb * BLK)) / BKV;
 
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
@@ -325,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
 #pragma unroll
   for (int qg = 0; qg < G; ++qg) {
     mylo[qg] = 0;
-    if constexpr (DOC) mylo[qg] = a.doc_start[(long long)b * a.T + myq[qg]];
+    if constexpr (DOC) mylo[qg] = row_lo<WIN>(a, b, myq[qg]);
   }
 #pragma unroll
   for (int qg = 0; qg < G; ++qg)
@@ -487,15 +525,16 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel(Args a) {
 }
 
 // ------------------------------------------------------------------------------ dK / dV
-// Not merged into one <DH, NS, DOC, G> kernel like the forward and dQ: the two-group body instantiated
+// Not merged into one <DH, NS, MASK, G> kernel like the forward and dQ: the two-group body instantiated
 // with one group at Dh = 128 measured 0.26 - 0.28 % slower than bwd_dkdv_kernel<128> on the Llama
 // backward, outside the parent's run-to-run spread (profiles/attn_merge_ab.md), so both stay as
 // they were.
 // Ring slot = Q tile | dO tile | LSE[64] | delta[64] of one (q-head, q-block) step.  The 512 B
 // of row constants come by DMA as well (waves 0-1: LSE halves, waves 2-3: delta halves, 8
 // lanes x 16 B each), so every wave issues the same DH/16 + 1 DMA instructions per step.
-template <int DH, int NS, bool DOC = false>
+template <int DH, int NS, int MASK = MASK_NONE>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
+  constexpr bool DOC = MASK != MASK_NONE, WIN = MASK == MASK_WIN;
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, TILE = 64 * DH * 2;
   constexpr int STG = 2 * TILE + 512, PER = DH / 16 + 1;
   __shared__ __attribute__((aligned(16))) char smem[NS * STG];
@@ -522,7 +561,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
   // of the block's last key (end is non-decreasing: the block maximum) - a scalar load, ahead of
   // the prologue DMAs
   int nq = nkb - kb;
-  if constexpr (DOC)
+  if constexpr (WIN)  // the band (and the document, if any) of the block's last key
+    nq = (__builtin_amdgcn_readfirstlane(key_hi<true>(a, b, kb * BKV + BKV - 1)) - 1) / BQ - kb + 1;
+  else if constexpr (DOC)
     nq = (__builtin_amdgcn_readfirstlane(a.doc_end[(long long)b * a.T + kb * BKV + BKV - 1]) - 1) / BQ - kb + 1;
   const int total = nq * gper;  // steps over (q-head of this subset, q block)
   const float* rowsrc = wave < 2 ? (const float*)a.lse : a.delta;
@@ -550,7 +591,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
   // DOC: key < start[q] <=> q >= end[key], so the low bound of the query rows' documents is an
   // upper bound on the query row per key lane - symmetric to the causal q < mykey
   int myend = 0;
-  if constexpr (DOC) myend = a.doc_end[(long long)b * a.T + mykey];
+  if constexpr (DOC) myend = key_hi<WIN>(a, b, mykey);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     settle(kf[ks]);
@@ -672,8 +713,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(Args a) {
 // §LDS).  Same ring, row-constant DMA and output contract (incl. the GQA head split).
 // (Dh = 128: 2 x 2 x 8 accumulators + 2 x 2 x 4 K / V fragments need the AGPR half of the
 // register file, so one wave per SIMD)
-template <int DH, int NS, bool DOC = false>
+template <int DH, int NS, int MASK = MASK_NONE>
 __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a) {
+  constexpr bool DOC = MASK != MASK_NONE, WIN = MASK == MASK_WIN;
   constexpr int KS = DH / 32, DT = DH / 16, DB = 2, TILE = 64 * DH * 2, KG = 2, BK2 = 128;
   constexpr int STG = 2 * TILE + 512, PER = DH / 16 + 1;
   __shared__ __attribute__((aligned(16))) char smem[NS * STG];
@@ -701,7 +743,9 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
   const int qb0 = kb * (BK2 / BQ);  // first q block that meets the block's keys
   // DOC: the q-tile loop ends with the document of the block's last key (as bwd_dkdv_kernel)
   int nq = nqb - qb0;
-  if constexpr (DOC)
+  if constexpr (WIN)
+    nq = (__builtin_amdgcn_readfirstlane(key_hi<true>(a, b, kb * BK2 + BK2 - 1)) - 1) / BQ - qb0 + 1;
+  else if constexpr (DOC)
     nq = (__builtin_amdgcn_readfirstlane(a.doc_end[(long long)b * a.T + kb * BK2 + BK2 - 1]) - 1) / BQ - qb0 + 1;
   const int total = nq * gper;
   const float* rowsrc = wave < 2 ? (const float*)a.lse : a.delta;
@@ -732,7 +776,7 @@ __global__ __launch_bounds__(256, DH == 64 ? 2 : 1) void bwd_dkdv2_kernel(Args a
 #pragma unroll
   for (int kg = 0; kg < KG; ++kg) {
     myend[kg] = 0;
-    if constexpr (DOC) myend[kg] = a.doc_end[(long long)b * a.T + mykey[kg]];
+    if constexpr (DOC) myend[kg] = key_hi<WIN>(a, b, mykey[kg]);
   }
 #pragma unroll
   for (int kg = 0; kg < KG; ++kg)
@@ -918,8 +962,9 @@ __global__ __launch_bounds__(256) void dkdv_reduce_kernel(Args a) {
 
 // ------------------------------------------------------------------------------ dQ
 // Block = 64 G query rows of one (b, h), 16 G per wave; same K/V ring as the forward.
-template <int DH, int NS, bool DOC, int G>
+template <int DH, int NS, int MASK, int G>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
+  constexpr bool DOC = MASK != MASK_NONE, WIN = MASK == MASK_WIN;
   constexpr int KS = DH / 32, DT = DH / 16, DB = DT < 4 ? DT : 4, BLK = 64 * G;
   constexpr int TILE = 64 * DH * 2, PER = DH / 16;
   constexpr bool HOIST = DH != 64;  // see stage()
@@ -946,7 +991,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
   const int nkb = (qb + 1) * G;
   // DOC: first key tile of the block's first row (the block minimum), read ahead of the DMAs
   int kb_lo = 0;
-  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(a.doc_start[(long long)b * a.T + qb * BLK]) / BKV;
+  if constexpr (DOC) kb_lo = __builtin_amdgcn_readfirstlane(row_lo<WIN>(a, b, qb * BLK)) / BKV;
 
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
@@ -967,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(Args a) {
     }
     lse2[qg] = a.lse[(long long)bh * a.T + myq[qg]];
     mylo[qg] = 0;
-    if constexpr (DOC) mylo[qg] = a.doc_start[(long long)b * a.T + myq[qg]];
+    if constexpr (DOC) mylo[qg] = row_lo<WIN>(a, b, myq[qg]);
   }
 #pragma unroll
   for (int qg = 0; qg < G; ++qg) {
@@ -1126,14 +1171,14 @@ static int fa_groups(const char* knob, int dflt, int T) {
   return (forced ? forced : dflt) == 2 && T % 128 == 0 ? 2 : 1;
 }
 
-// KERNEL<Dh, 2, DOC, G> on T / (64 G) blocks x NY, on `st`.
+// KERNEL<Dh, 2, MASK, G> on T / (64 G) blocks x NY, on `st`.
 // Ring depth: every kernel is launched with NS = 2.  Measured at Dh = 64 on GPT-2 shapes (B16
 // T1024 H12, benchmarks/attn_bench.py): NS 2 / 3 / 4 = fwd 108 / 113 / 135 us, bwd 285 / 335 /
 // 357 us - every extra slot costs a co-resident block per CU (32 / 48 / 64 KiB of LDS per
 // block), and at these 8-16-step loops occupancy hides more HBM latency than a deeper ring.
 // At Dh = 128 a third slot leaves one block per CU.
 #define FA_LAUNCH_1(KERNEL, DH, G, NY, ARGS) \
-  hipLaunchKernelGGL((KERNEL<DH, 2, DOC, G>), dim3(T / (64 * G), NY), dim3(256), 0, st, ARGS)
+  hipLaunchKernelGGL((KERNEL<DH, 2, MASK, G>), dim3(T / (64 * G), NY), dim3(256), 0, st, ARGS)
 #define FA_LAUNCH(KERNEL, G, NY, ARGS)                        \
   do {                                                        \
     if (Dh == 64 && (G) == 1) FA_LAUNCH_1(KERNEL, 64, 1, NY, ARGS);   \
@@ -1142,14 +1187,22 @@ static int fa_groups(const char* knob, int dflt, int T) {
     else FA_LAUNCH_1(KERNEL, 128, 2, NY, ARGS);                       \
   } while (0)
 
-// DOC = true: the document-masked kernels (doc_start / doc_end set); same dispatch
-template <bool DOC>
+// MASK_DOC: the document-masked kernels (doc_start / doc_end set); MASK_WIN: the sliding-window
+// kernels (window >= 1; doc_start / doc_end both set or both null); same dispatch
+static bool fa_mask_args_ok(int mask, const int* doc_start, const int* doc_end, int window) {
+  if (mask == fa::MASK_DOC) return doc_start != nullptr && doc_end != nullptr;
+  if (mask == fa::MASK_WIN) return window >= 1 && (doc_start == nullptr) == (doc_end == nullptr);
+  return true;
+}
+
+template <int MASK>
 static int flash_fwd_launch(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh, float scale,
-                            const int* doc_start, const int* doc_end, hipStream_t st) {
+                            const int* doc_start, const int* doc_end, int window, hipStream_t st) {
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
-  if (DOC && (doc_start == nullptr || doc_end == nullptr)) return 1;
+  if (!fa_mask_args_ok(MASK, doc_start, doc_end, window)) return 1;
   fa::Args a{};
   a.doc_start = doc_start; a.doc_end = doc_end;
+  a.window = window < T ? window : T;  // (key + window stays far from INT_MAX)
   a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)out; a.lse = lse;
   a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
   // measured (benchmarks/attn_bench.py, before the DMA ring): 32 rows/wave wins at Dh = 128
@@ -1162,23 +1215,31 @@ static int flash_fwd_launch(const void* qkv, void* out, float* lse, int B, int T
 
 extern "C" int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh,
                               float scale, hipStream_t st) {
-  return flash_fwd_launch<false>(qkv, out, lse, B, T, H, Hkv, Dh, scale, nullptr, nullptr, st);
+  return flash_fwd_launch<fa::MASK_NONE>(qkv, out, lse, B, T, H, Hkv, Dh, scale, nullptr, nullptr, 0, st);
 }
 
 // packed sequences: row (b, q) attends to keys doc_start[b, q] <= key <= q (doc_start / doc_end: fa::Args)
 extern "C" int rtdc_flash_fwd_doc(const void* qkv, void* out, float* lse, const int* doc_start, const int* doc_end,
                                   int B, int T, int H, int Hkv, int Dh, float scale, hipStream_t st) {
-  return flash_fwd_launch<true>(qkv, out, lse, B, T, H, Hkv, Dh, scale, doc_start, doc_end, st);
+  return flash_fwd_launch<fa::MASK_DOC>(qkv, out, lse, B, T, H, Hkv, Dh, scale, doc_start, doc_end, 0, st);
+}
+
+// sliding window: row (b, q) attends to keys max(doc_start[b, q], q - window + 1) <= key <= q;
+// doc_start / doc_end are both null (no documents, nothing is loaded) or both set
+extern "C" int rtdc_flash_fwd_win(const void* qkv, void* out, float* lse, int window, const int* doc_start,
+                                  const int* doc_end, int B, int T, int H, int Hkv, int Dh, float scale,
+                                  hipStream_t st) {
+  return flash_fwd_launch<fa::MASK_WIN>(qkv, out, lse, B, T, H, Hkv, Dh, scale, doc_start, doc_end, window, st);
 }
 
 // dQ (it also stores delta), then dK/dV (+ the GQA head-split reduction), all on `st`
-template <bool DOC>
+template <int MASK>
 static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                             void* dqkv, int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws, float* part,
-                            int qs, const int* doc_start, const int* doc_end, hipStream_t st) {
+                            int qs, const int* doc_start, const int* doc_end, int window, hipStream_t st) {
   if (T % 64 != 0 || (Dh != 64 && Dh != 128) || H % Hkv != 0) return 1;
   if (qs < 1 || (H / Hkv) % qs != 0 || (qs > 1 && part == nullptr) || ((Hkv * 2 * Dh) % 4) != 0) return 1;
-  if (DOC && (doc_start == nullptr || doc_end == nullptr)) return 1;
+  if (!fa_mask_args_ok(MASK, doc_start, doc_end, window)) return 1;
   fa::Args a{};
   a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)out; a.dout = (const bf16_t*)dout; a.lse = (float*)lse;
   a.delta = delta;
@@ -1187,6 +1248,7 @@ static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, 
   a.B = B; a.T = T; a.H = H; a.Hkv = Hkv; a.scale = scale; a.xcd_remap = fa_xcd();
   a.part = part; a.qs = qs;
   a.doc_start = doc_start; a.doc_end = doc_end;
+  a.window = window < T ? window : T;
   // dQ first: it also computes the row terms delta = rowsum(dO * O) that dK/dV read.  32 query
   // rows per wave (GPT-2 63 -> 59 us, Llama-3-8B shapes 165 -> 140 us per call,
   // benchmarks/attn_bench.py under rocprofv3) unless RTDC_FA_DQ=1 (16 rows per wave)
@@ -1197,10 +1259,10 @@ static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, 
   const int gdkdv = fa_groups("RTDC_FA_DKDV", Dh == 64 ? 2 : 1, T);
   // (still two kernels, see above them: G picks the kernel, not a template argument)
   const dim3 gkv(T / (64 * gdkdv), B * Hkv * qs);
-  if (gdkdv == 2 && Dh == 64) hipLaunchKernelGGL((fa::bwd_dkdv2_kernel<64, 2, DOC>), gkv, dim3(256), 0, st, a);
-  else if (gdkdv == 2) hipLaunchKernelGGL((fa::bwd_dkdv2_kernel<128, 2, DOC>), gkv, dim3(256), 0, st, a);
-  else if (Dh == 64) hipLaunchKernelGGL((fa::bwd_dkdv_kernel<64, 2, DOC>), gkv, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((fa::bwd_dkdv_kernel<128, 2, DOC>), gkv, dim3(256), 0, st, a);
+  if (gdkdv == 2 && Dh == 64) hipLaunchKernelGGL((fa::bwd_dkdv2_kernel<64, 2, MASK>), gkv, dim3(256), 0, st, a);
+  else if (gdkdv == 2) hipLaunchKernelGGL((fa::bwd_dkdv2_kernel<128, 2, MASK>), gkv, dim3(256), 0, st, a);
+  else if (Dh == 64) hipLaunchKernelGGL((fa::bwd_dkdv_kernel<64, 2, MASK>), gkv, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((fa::bwd_dkdv_kernel<128, 2, MASK>), gkv, dim3(256), 0, st, a);
   if (qs > 1) {
     const int KV = Hkv * 2 * Dh;
     dim3 gr((unsigned)((long long)B * T / 16), (unsigned)((KV / 4 + 255) / 256));
@@ -1213,13 +1275,21 @@ static int flash_bwd_launch(const void* qkv, const void* out, const void* dout, 
 extern "C" int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                               void* dqkv, int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws,
                               float* part, int qs, hipStream_t st) {
-  return flash_bwd_launch<false>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs, nullptr,
-                                 nullptr, st);
+  return flash_bwd_launch<fa::MASK_NONE>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs,
+                                         nullptr, nullptr, 0, st);
 }
 
 extern "C" int rtdc_flash_bwd_doc(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                                   void* dqkv, const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv,
                                   int Dh, float scale, float* cs_ws, float* part, int qs, hipStream_t st) {
-  return flash_bwd_launch<true>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs, doc_start,
-                                doc_end, st);
+  return flash_bwd_launch<fa::MASK_DOC>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs,
+                                        doc_start, doc_end, 0, st);
+}
+
+extern "C" int rtdc_flash_bwd_win(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                                  void* dqkv, int window, const int* doc_start, const int* doc_end, int B, int T,
+                                  int H, int Hkv, int Dh, float scale, float* cs_ws, float* part, int qs,
+                                  hipStream_t st) {
+  return flash_bwd_launch<fa::MASK_WIN>(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs_ws, part, qs,
+                                        doc_start, doc_end, window, st);
 }

@@ -59,9 +59,9 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x, residual, docs=None):
+    def forward(self, x, residual, docs=None, window=None):
         qkv = self.c_attn(x)
-        y = ops.causal_attention(qkv, self.n_head, docs=docs)
+        y = ops.causal_attention(qkv, self.n_head, docs=docs, window=window)
         return self.c_proj(y, residual=residual)
 
 
@@ -83,26 +83,30 @@ class Block(nn.Module):
         self.ln_2 = LayerNorm(cfg.n_embd, cfg.layer_norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, prev_bias=None, docs=None):
+    def forward(self, x, prev_bias=None, docs=None, window=None):
         # the residual stream passes through each LayerNorm so its gradient is summed inside
         # the norm's backward kernel (no separate add of the two branches' gradients); that
         # kernel also reduces the bias gradient of the projection that wrote the stream
         # (prev_bias: the previous block's MLP c_proj, then this block's attention c_proj)
         h, x = self.ln_1(x, passthrough=True, grad_sum_into=prev_bias)
-        x = self.attn(h, residual=x, docs=docs)
+        x = self.attn(h, residual=x, docs=docs, window=window)
         h, x = self.ln_2(x, passthrough=True, grad_sum_into=self.attn.c_proj.bias)
         return self.mlp(h, residual=x)
 
 
 class GPT2(nn.Module):
-    def __init__(self, cfg: GPT2Config, z_loss: float = 0.0, label_smoothing: float = 0.0):
+    def __init__(self, cfg: GPT2Config, z_loss: float = 0.0, label_smoothing: float = 0.0,
+                 sliding_window: int | None = None):
         """z_loss / label_smoothing: the two optional terms of ops.lm_head_cross_entropy, plain
         attributes (not in the config, not in the state_dict; settable later).  With either one
         non-zero `forward(idx, targets)` still returns the optimised loss and leaves the mean
         plain cross-entropy of that forward in `self.last_ce` (a 0-dim device tensor); a forward
-        with both at 0 sets it back to None."""
+        with both at 0 sets it back to None.
+        sliding_window (None = off): a plain attribute like them; every block's attention sees
+        the last `sliding_window` keys only (ops.causal_attention window=)."""
         super().__init__()
         self.cfg = cfg
+        self.sliding_window = sliding_window
         self.z_loss, self.label_smoothing, self.last_ce = z_loss, label_smoothing, None
         self.wte = nn.Parameter(torch.empty(cfg.padded_vocab, cfg.n_embd))
         self.wpe = nn.Parameter(torch.empty(cfg.n_positions, cfg.n_embd))
@@ -136,7 +140,7 @@ class GPT2(nn.Module):
         x = ops.embedding(idx, self.wte, self.wpe)
         prev_bias = None
         for blk in self.h:
-            x = blk(x, prev_bias, docs)
+            x = blk(x, prev_bias, docs, self.sliding_window or None)
             prev_bias = blk.mlp.c_proj.bias
         x = self.ln_f(x, grad_sum_into=prev_bias)
         if targets is not None:

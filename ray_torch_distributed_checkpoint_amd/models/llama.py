@@ -67,11 +67,11 @@ class Attention(nn.Module):
         self.wqkv = nn.Parameter(torch.empty((cfg.n_heads + 2 * cfg.n_kv_heads) * hd, cfg.dim))
         self.wo = nn.Parameter(torch.empty(cfg.dim, cfg.n_heads * hd))
 
-    def forward(self, x, residual, docs=None):
+    def forward(self, x, residual, docs=None, window=None):
         c = self.cfg
         qkv = ops.linear(x, self.wqkv)
         qkv = apply_rope(qkv, c.n_heads, c.n_kv_heads, c.rope_theta, docs=docs)
-        y = ops.causal_attention(qkv, c.n_heads, c.n_kv_heads, docs=docs)
+        y = ops.causal_attention(qkv, c.n_heads, c.n_kv_heads, docs=docs, window=window)
         return ops.linear(y, self.wo, residual=residual)
 
 
@@ -93,22 +93,27 @@ class TransformerBlock(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x, docs=None):
+    def forward(self, x, docs=None, window=None):
         h, x = self.attention_norm(x, passthrough=True)
-        x = self.attention(h, residual=x, docs=docs)
+        x = self.attention(h, residual=x, docs=docs, window=window)
         h, x = self.ffn_norm(x, passthrough=True)
         return self.feed_forward(h, residual=x)
 
 
 class Llama(nn.Module):
-    def __init__(self, cfg: LlamaConfig, device=None, z_loss: float = 0.0, label_smoothing: float = 0.0):
+    def __init__(self, cfg: LlamaConfig, device=None, z_loss: float = 0.0, label_smoothing: float = 0.0,
+                 sliding_window: int | None = None):
         """z_loss / label_smoothing: the two optional terms of ops.lm_head_cross_entropy, plain
         attributes (not in the config, not in the state_dict; settable later).  With either one
         non-zero `forward(idx, targets)` still returns the optimised loss and leaves the mean
         plain cross-entropy of that forward in `self.last_ce` (a 0-dim device tensor); a forward
-        with both at 0 sets it back to None."""
+        with both at 0 sets it back to None.
+        sliding_window (None = off): a plain attribute like them; every block's attention sees
+        the last `sliding_window` keys only (ops.causal_attention window=).  RoPE positions are
+        unchanged: absolute, or per document with docs."""
         super().__init__()
         self.cfg = cfg
+        self.sliding_window = sliding_window
         self.z_loss, self.label_smoothing, self.last_ce = z_loss, label_smoothing, None
         factory = {"device": device} if device is not None else {}
         with torch.device(device) if device is not None else _nullctx():
@@ -140,7 +145,7 @@ class Llama(nn.Module):
         with each document and attention is restricted to the token's own document."""
         x = ops.embedding(idx, self.tok_embeddings)
         for blk in self.layers:
-            x = blk(x, docs)
+            x = blk(x, docs, self.sliding_window or None)
         x = self.norm(x)
         if targets is not None:
             if self.z_loss or self.label_smoothing:

@@ -199,18 +199,23 @@ class _FlashAttention(torch.autograd.Function):
     """Fused causal flash attention (csrc/kernels/attn_flash.hip): no T x T matrix in HBM."""
 
     @staticmethod
-    def forward(ctx, qkv, B, T, H, Hkv, Dh, docs=None):
+    def forward(ctx, qkv, B, T, H, Hkv, Dh, docs=None, window=None):
+        """window (int, 1 <= window < T, or None): the sliding-window kernels, with or without docs."""
         qkv = qkv.contiguous()
         out = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B * H, T), dtype=torch.float32, device=qkv.device)
         scale = 1.0 / math.sqrt(Dh)
-        if docs is None:
+        if window is not None:
+            gpu_ext().flash_fwd_win(qkv, out, lse, window, docs.start if docs is not None else None,
+                                    docs.end if docs is not None else None, B, T, H, Hkv, Dh, scale)
+        elif docs is None:
             gpu_ext().flash_fwd(qkv, out, lse, B, T, H, Hkv, Dh, scale)
         else:
             gpu_ext().flash_fwd_doc(qkv, out, lse, docs.start, docs.end, B, T, H, Hkv, Dh, scale)
         ctx.save_for_backward(qkv, out, lse)
         ctx.dims = (B, T, H, Hkv, Dh, scale)
         ctx.docs = docs  # (int32 layout tensors: no gradient, shared by every layer of the step)
+        ctx.window = window
         return out
 
     @staticmethod
@@ -227,14 +232,18 @@ class _FlashAttention(torch.autograd.Function):
         part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device=qkv.device) if qs > 1 else None
         dout = dout.contiguous()
         docs = ctx.docs
-        if docs is None:
+        if ctx.window is not None:
+            gpu_ext().flash_bwd_win(qkv, out, dout, lse, delta, dqkv, ctx.window,
+                                    docs.start if docs is not None else None,
+                                    docs.end if docs is not None else None, B, T, H, Hkv, Dh, scale, cs, part, qs)
+        elif docs is None:
             gpu_ext().flash_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs)
         else:
             gpu_ext().flash_bwd_doc(qkv, out, dout, lse, delta, dqkv, docs.start, docs.end, B, T, H, Hkv, Dh, scale,
                                     cs, part, qs)
         if cs is not None:
             G.offer_colsum_partials(dqkv, cs)
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def _dkdv_head_split(B: int, T: int, H: int, Hkv: int, device) -> int:
@@ -261,7 +270,13 @@ def flash_supported(T: int, Dh: int) -> bool:
     return T % 64 == 0 and Dh in (64, 128)
 
 
-def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None):
+def window_mask(T: int, window: int, device=None) -> torch.Tensor:
+    """Boolean [T, T]: query q may attend to key k iff q - window < k <= q (its last `window` keys)."""
+    t = torch.arange(T, device=device)
+    return (t[None, :] <= t[:, None]) & (t[None, :] > t[:, None] - window)
+
+
+def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None, window=None):
     C = H * Dh
     q = qkv[..., :C].reshape(B, T, H, Dh).transpose(1, 2)
     k = qkv[..., C:C + Hkv * Dh].reshape(B, T, Hkv, Dh).transpose(1, 2)
@@ -269,7 +284,10 @@ def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None):
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=1)
         v = v.repeat_interleave(H // Hkv, dim=1)
-    if docs is None:
+    if window is not None:  # boolean band mask, inside the document when both are given
+        band = window_mask(T, window, qkv.device)[None, None]
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=band if docs is None else band & docs.mask()[:, None])
+    elif docs is None:
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
     else:  # boolean mask start[q] <= key <= q: the oracle of the document-masked kernels
         o = F.scaled_dot_product_attention(q, k, v, attn_mask=docs.mask()[:, None])
@@ -277,13 +295,23 @@ def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None):
 
 
 def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = None,
-                     docs: DocLayout | None = None) -> torch.Tensor:
+                     docs: DocLayout | None = None, window: int | None = None) -> torch.Tensor:
     """qkv: [B, T, (H + 2*Hkv) * Dh] -> [B, T, H*Dh].  docs (packed sequences): row q attends to
     the keys start[q] <= key <= q of its own document only; it needs the flash path - there is
-    no unmasked fallback.  Without docs any T runs: the composed path pads T to a multiple of 64."""
+    no unmasked fallback.  window (sliding-window attention, None = off): row q attends to its
+    last `window` keys only, max(0, q - window + 1) <= key <= q, within its document when docs is
+    given; window >= T masks nothing and runs the kernels that run without it.  Like docs it needs
+    the flash path on the GPU.  Without docs and window any T runs: the composed path pads T to a
+    multiple of 64."""
     B, T, W = qkv.shape
     Hkv = n_kv_head or n_head
     Dh = W // (n_head + 2 * Hkv)
+    if window is not None:
+        window = int(window)
+        if window < 1:
+            raise ValueError(f"causal_attention: window must be >= 1 (None = off), got {window}")
+        if window >= T:
+            window = None
     if docs is not None:
         if docs.shape != (B, T):
             raise ValueError(f"causal_attention: docs layout is {docs.shape}, qkv is [{B}, {T}, ...]")
@@ -292,8 +320,14 @@ def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = Non
     if qkv.is_cuda:
         require_dtype(qkv, "causal_attention")
     else:
-        return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh, docs)
+        return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh, docs, window)
     impl = os.environ.get("RTDC_ATTN", "flash")
+    if window is not None:
+        if impl != "flash" or not flash_supported(T, Dh):
+            raise RuntimeError(
+                f"causal_attention: a sliding window needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
+                f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
+        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs, window)
     if docs is not None:
         if impl != "flash" or not flash_supported(T, Dh):
             raise RuntimeError(

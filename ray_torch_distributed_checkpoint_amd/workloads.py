@@ -70,6 +70,7 @@ class WorkloadConfig:
     num_classes: int = 10
     max_grad_norm: Optional[float] = None  # clip the global gradient norm inside the fused step (None / 0: off)
     doc_len: Optional[int] = None  # LMs: packed sequences of documents of this mean length (None / 0: off)
+    sliding_window: Optional[int] = None  # LMs: every attention sees its last N keys only (None / 0: off)
     # LMs: dtype the fused AdamW stores exp_avg / exp_avg_sq in: "fp32" | "bf16" (bf16: stochastically
     # rounded with bits keyed by `seed`; a checkpoint resumes into the same setting)
     opt_state_dtype: str = "fp32"
@@ -321,7 +322,9 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     opt = FusedAdamW(model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=clip,
                      state_dtype=getattr(torch, _OPT_STATE_DTYPES[cfg.opt_state_dtype]), rounding_seed=cfg.seed, **sched_kw)
     data = SyntheticTokens(cfg.dataset_size, S, mc.vocab_size, seed=cfg.seed, doc_len=cfg.doc_len or None)
-    # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle)
+    # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle,
+    # under a sliding window too)
+    model.sliding_window = int(cfg.sliding_window) if cfg.sliding_window else None
     if aux:
         model.z_loss, model.label_smoothing = zl, ls  # forward() leaves the plain cross-entropy in last_ce
 
@@ -604,7 +607,8 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    bucket_cap_mb: float = 32.0, zero_stage: int = -1, progress_timeout_s: float | None = 300.0,
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
                    report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
-                   doc_len: int | None = None, opt_state_dtype: str = "fp32", grad_accum_steps: int = 1,
+                   doc_len: int | None = None, sliding_window: int | None = None,
+                   opt_state_dtype: str = "fp32", grad_accum_steps: int = 1,
                    lr_schedule: str = "constant", warmup_steps: int = 0, min_lr_ratio: float = 0.0,
                    lr_total_steps: int | None = None, opt_capturable: bool = False, z_loss: float | None = None,
                    label_smoothing: float | None = None):
@@ -613,7 +617,9 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     gradient norm inside the fused optimizer step (None / 0: off); the report rows then carry
     `grad_norm` / `grad_norms` (pre-clip).  doc_len (LMs): train on packed sequences of synthetic
     documents of that mean length, attention and RoPE positions restricted to each document
-    (None / 0: off; the report rows are unchanged).  opt_state_dtype (LMs): "fp32" | "bf16" - the
+    (None / 0: off; the report rows are unchanged).  sliding_window (LMs): every attention layer
+    sees the last N keys only, within the document under doc_len (None / 0: off; nothing new is
+    checkpointed - a resume passes the same value).  opt_state_dtype (LMs): "fp32" | "bf16" - the
     dtype FusedAdamW stores its moments in (bf16: half the optimizer memory and checkpoint bytes,
     stochastic rounding keyed by `seed`; the report rows are unchanged).  grad_accum_steps = k:
     every optimizer step accumulates k micro-batches in place (optim.GradAccumulator) and applies
@@ -639,12 +645,15 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     if opt_state_dtype not in _OPT_STATE_DTYPES:
         raise ValueError(f"opt_state_dtype must be one of {sorted(_OPT_STATE_DTYPES)}, got {opt_state_dtype!r}")
     check_loss_coeffs(label_smoothing, z_loss)  # (argument errors here, not in the workers)
+    if sliding_window and int(sliding_window) < 1:
+        raise ValueError(f"sliding_window must be >= 1 (None / 0: off), got {sliding_window}")
     if zero_stage < 0:
         zero_stage = default_zero_stage(model, num_workers)
     cfg = WorkloadConfig(model=model, steps=steps, batch_size_per_worker=batch_size_per_worker, seq_len=seq_len,
                          lr=lr, ckpt_every_n_steps=ckpt_every_n_steps, seed=seed, resume_mode=resume_mode,
                          checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
                          max_grad_norm=max_grad_norm or None, doc_len=doc_len or None,
+                         sliding_window=int(sliding_window) if sliding_window else None,
                          opt_state_dtype=opt_state_dtype, grad_accum_steps=int(grad_accum_steps),
                          lr_schedule=lr_schedule, warmup_steps=int(warmup_steps or 0),
                          min_lr_ratio=float(min_lr_ratio or 0.0), lr_total_steps=lr_total_steps or None,
@@ -685,6 +694,8 @@ def main(argv=None):
     ap.add_argument("--doc-len", type=int, default=None,
                     help="LMs: packed sequences of synthetic documents of this mean length, attention and "
                          "RoPE positions per document (default: off)")
+    ap.add_argument("--sliding-window", type=int, default=None,
+                    help="LMs: sliding-window attention, every layer sees its last N keys only (default: off)")
     ap.add_argument("--opt-state-dtype", default="fp32", choices=sorted(_OPT_STATE_DTYPES),
                     help="LMs: dtype of the fused AdamW's stored moments (bf16: stochastically rounded)")
     ap.add_argument("--grad-accum-steps", type=int, default=1,
@@ -711,6 +722,7 @@ def main(argv=None):
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
                          zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len,
+                         sliding_window=a.sliding_window,
                          opt_state_dtype=a.opt_state_dtype, grad_accum_steps=a.grad_accum_steps,
                          lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, min_lr_ratio=a.min_lr_ratio,
                          lr_total_steps=a.lr_total_steps, opt_capturable=a.opt_capturable, z_loss=a.z_loss,

@@ -72,10 +72,14 @@ def plain_name(d):
     # name2_kernel<D, NS[, true]> is name_kernel<D, NS, doc, 2> and name_kernel<D, NS[, true]> is
     # name_kernel<D, NS, doc, 1>; both trees are keyed by the four-argument name (a pair that is
     # still two kernels in both trees lines up under those names as well)
-    m = re.match(r"(.*\bfa::(?:fwd|bwd_dq|bwd_dkdv))(2?)_kernel<(\d+), (\d+)(?:, (true|false))?>(.*)$", d)
+    m = re.match(r"(.*\bfa::(?:fwd|bwd_dq|bwd_dkdv))(2?)_kernel<(\d+), (\d+)(?:, (true|false|\d+))?(?:, (\d+))?>(.*)$",
+                 d)
     if m:
-        return "%s_kernel<%s, %s, %s, %d>%s" % (m.group(1), m.group(3), m.group(4), m.group(5) or "false",
-                                                2 if m.group(2) else 1, m.group(6))
+        # the mask switch was a bool (false / true = documents) before it became the int MASK
+        # (0 none, 1 documents, 2 sliding window): 0 / 1 are listed under the bool's names
+        mask = {"0": "false", "1": "true", "2": "window"}.get(m.group(5) or "0", m.group(5))
+        return "%s_kernel<%s, %s, %s, %d>%s" % (m.group(1), m.group(3), m.group(4), mask,
+                                                2 if m.group(2) else int(m.group(6) or 1), m.group(7))
     while True:
         n = re.sub(r", false>", ">", d)
         if n == d:

@@ -5,6 +5,7 @@ Llama-3-8B shapes; random operands, one process, interleaved repetitions.
     python benchmarks/attn_bench.py --doc-len T T/8 100 [--only gpt2] [--rounds 7]
     python benchmarks/attn_bench.py --variants default 1,1,1 [--rounds 1]
     python benchmarks/attn_bench.py --window T/8 T/4 T/2 [--only llama8b_t8k] [--rounds 7]
+    python benchmarks/attn_bench.py --dropout 0.1 [--only gpt2] [--rounds 7]
 
 --doc-len L times the document-masked kernels (packed sequences: equal documents of length L, the
 last one shorter when L does not divide T) next to the plain causal kernels on the same shape and
@@ -18,6 +19,10 @@ window's length recorded), three arms per pass: the plain causal kernels, the wi
 the document-mask kernels fed the band as clipped [B, T] arrays (what a window costs without
 kernels of its own).  Next to the times it prints the share of key tiles the band visits, counted
 from the kernels' loop bounds.  It adds a long shape (T = 8192) to the two of --doc-len.
+
+--dropout P times the attention-dropout kernels (flash_fwd_drop / flash_bwd_drop, plain causal
+mask) next to the plain kernels the same way: same buffers, alternating rounds, every timed
+window's length recorded, median / minimum per arm, the plain arm's own spread and the ratio.
 """
 from __future__ import annotations
 
@@ -199,6 +204,57 @@ def window_ab(args):
             print(json.dumps(res), flush=True)
 
 
+def dropout_ab(args):
+    """Plain vs attention-dropout kernels, forward and backward, per shape and probability."""
+    from statistics import median
+
+    from ray_torch_distributed_checkpoint_amd.ops.attention import _dkdv_head_split, attention_dropout_keep
+
+    ext = gpu_ext()
+    for name, B, T, H, Hkv, Dh in SHAPES[:2]:
+        if args.only and name != args.only:
+            continue
+        Wd, scale = (H + 2 * Hkv) * Dh, Dh ** -0.5
+        q_ = (torch.randn(B, T, Wd, device="cuda") * 0.5).bfloat16()
+        o_ = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device="cuda")
+        lse = torch.empty((B * H, T), dtype=torch.float32, device="cuda")
+        dy = torch.randn_like(o_)
+        dqkv = torch.empty_like(q_)
+        delta = torch.empty((B * H, T), dtype=torch.float32, device="cuda")
+        qs = _dkdv_head_split(B, T, H, Hkv, q_.device)
+        part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device="cuda") if qs > 1 else None
+        for p in args.dropout:
+            thr, _ = attention_dropout_keep(p)
+            seed, off = 0x5EED, 12345
+            arms = {
+                "plain_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale),
+                "drop_fwd": lambda: ext.flash_fwd_drop(q_, o_, lse, 0, None, None, thr, seed, off, None, B, T, H, Hkv,
+                                                       Dh, scale),
+                "plain_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part,
+                                                   qs),
+                "drop_bwd": lambda: ext.flash_bwd_drop(q_, o_, dy, lse, delta, dqkv, 0, None, None, thr, seed, off,
+                                                       None, B, T, H, Hkv, Dh, scale, None, part, qs),
+            }
+            # (as --doc-len: windows of at least --window-ms, calibrated on warm calls; an arm's
+            # forward runs right before its backward, which so reads the o / lse of its own mask)
+            reps = {k: max(args.reps, int(1.25 * args.window_ms * 1e-3 / timeit(fn, 100)) + 1) for k, fn in arms.items()}
+            t = {k: [] for k in arms}
+            for _ in range(args.rounds):
+                for kind in ("plain", "drop"):
+                    t[kind + "_fwd"].append(timeit(arms[kind + "_fwd"], reps[kind + "_fwd"]) * 1e6)
+                    t[kind + "_bwd"].append(timeit(arms[kind + "_bwd"], reps[kind + "_bwd"]) * 1e6)
+            res = {"shape": name, "B": B, "T": T, "H": H, "Hkv": Hkv, "Dh": Dh, "dropout_p": p, "thr": thr,
+                   "dkdv_head_split": qs, "reps": reps, "window_ms": args.window_ms, "rounds": args.rounds}
+            for k, v in t.items():
+                res[k + "_us_median"], res[k + "_us_min"] = round(median(v), 2), round(min(v), 2)
+                res[k + "_timed_ms"] = [round(x * reps[k] * 1e-3, 1) for x in v]  # every timed window's length
+            for ph in ("fwd", "bwd"):
+                pm, dm = median(t["plain_" + ph]), median(t["drop_" + ph])
+                res[f"plain_{ph}_spread_pct"] = round(100 * (max(t["plain_" + ph]) - min(t["plain_" + ph])) / pm, 2)
+                res[f"drop_over_plain_{ph}_time"] = round(dm / pm, 3)
+            print(json.dumps(res), flush=True)
+
+
 def variants_ab(args):
     """The forward and the backward kernel calls, timed apart, at each rows-per-wave setting: one
     JSON line per (shape, setting) with the time of every round.  Two builds are compared by running
@@ -250,6 +306,9 @@ def main():
     ap.add_argument("--window", nargs="+", default=None, metavar="W",
                     help="time the sliding-window kernels with a window of W keys (an integer, T or T/<n>; several "
                          "allowed) next to the plain ones and to the document-mask kernels on clipped arrays")
+    ap.add_argument("--dropout", nargs="+", type=float, default=None, metavar="P",
+                    help="time the attention-dropout kernels at probability P (several allowed) next to the plain "
+                         "ones")
     ap.add_argument("--rounds", type=int, default=7, help="--doc-len / --window: alternating plain / masked rounds")
     ap.add_argument("--window-ms", type=float, default=120.0,
                     help="--doc-len / --window: least length of every timed window (repetitions are scaled to it)")
@@ -262,6 +321,8 @@ def main():
         return doc_mask_ab(args)
     if args.window:
         return window_ab(args)
+    if args.dropout:
+        return dropout_ab(args)
     if args.variants:
         return variants_ab(args)
     for name, B, T, H, Hkv, Dh in SHAPES:

@@ -128,6 +128,13 @@ int rtdc_flash_fwd_win(const void* qkv, void* out, float* lse, int window, const
 int rtdc_flash_bwd_win(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                        int window, const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv, int Dh,
                        float scale, float* cs_ws, float* part, int qs, hipStream_t st);
+int rtdc_flash_fwd_drop(const void* qkv, void* out, float* lse, int window, const int* doc_start, const int* doc_end,
+                        int thr, unsigned long long seed, unsigned long long offset, const long long* off_dev, int B,
+                        int T, int H, int Hkv, int Dh, float scale, hipStream_t st);
+int rtdc_flash_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                        void* dqkv, int window, const int* doc_start, const int* doc_end, int thr,
+                        unsigned long long seed, unsigned long long offset, const long long* off_dev, int B, int T,
+                        int H, int Hkv, int Dh, float scale, float* cs_ws, float* part, int qs, hipStream_t st);
 int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, const int* doc_start, int ntok, int T,
                   int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st);
 int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st);
@@ -832,6 +839,58 @@ static void flash_bwd_win(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tenso
                               qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
            "flash_bwd_win");
 }
+// attention dropout: window 0 = none, doc_start / doc_end both given or both None; thr in 1..255 (an
+// element is dropped with probability thr / 256); the mask's counter base is offset (+ *off_dev)
+static void check_drop(const Tensor& qkv, int64_t window, const c10::optional<Tensor>& start,
+                       const c10::optional<Tensor>& end, int64_t thr, const c10::optional<Tensor>& off_dev, int64_t B,
+                       int64_t T, const char* what) {
+  TORCH_CHECK(window >= 0, what, ": window must be >= 0 (0 = none), got ", window);
+  TORCH_CHECK(start.has_value() == end.has_value(), what, ": doc start / end are given together or not at all");
+  if (start.has_value()) check_docs(qkv, *start, *end, B, T, what);
+  TORCH_CHECK(thr >= 1 && thr <= 255, what, ": thr must be in 1..255, got ", thr);
+  TORCH_CHECK(!off_dev.has_value() || (off_dev->scalar_type() == at::kLong && off_dev->is_cuda()), what,
+              ": off_dev must be an int64 GPU tensor");
+}
+static void flash_fwd_drop(Tensor qkv, Tensor out, Tensor lse, int64_t window, c10::optional<Tensor> doc_start,
+                           c10::optional<Tensor> doc_end, int64_t thr, uint64_t seed, uint64_t offset,
+                           c10::optional<Tensor> off_dev, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh,
+                           double scale) {
+  check_dev(qkv, "qkv");
+  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd_drop: contiguous tensors expected");
+  check_drop(qkv, window, doc_start, doc_end, thr, off_dev, B, T, "flash_fwd_drop");
+  check_rc(rtdc_flash_fwd_drop(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)std::min(window, T),
+                               doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
+                               doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)thr, seed, offset,
+                               off_dev.has_value() ? (const long long*)off_dev->data_ptr<int64_t>() : nullptr, (int)B,
+                               (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale, cur_stream()),
+           "flash_fwd_drop");
+}
+static void flash_bwd_drop(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, int64_t window,
+                           c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end, int64_t thr, uint64_t seed,
+                           uint64_t offset, c10::optional<Tensor> off_dev, int64_t B, int64_t T, int64_t H,
+                           int64_t Hkv, int64_t Dh, double scale, c10::optional<Tensor> cs_ws,
+                           c10::optional<Tensor> part, int64_t qs) {
+  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd_drop: contiguous tensors expected");
+  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd_drop: qs must divide the GQA group size");
+  check_drop(qkv, window, doc_start, doc_end, thr, off_dev, B, T, "flash_bwd_drop");
+  if (qs > 1)
+    TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
+                    part->numel() >= qs * B * T * Hkv * 2 * Dh,
+                "flash_bwd_drop: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
+  if (cs_ws.has_value())
+    TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
+                    cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
+                "flash_bwd_drop: cs_ws fp32 [B*T/16][W]");
+  check_rc(rtdc_flash_bwd_drop(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
+                               delta.data_ptr<float>(), dqkv.data_ptr(), (int)std::min(window, T),
+                               doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
+                               doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)thr, seed, offset,
+                               off_dev.has_value() ? (const long long*)off_dev->data_ptr<int64_t>() : nullptr, (int)B,
+                               (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
+                               cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
+                               qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
+           "flash_bwd_drop");
+}
 // flags uint8 [B, T] (non-zero: a document starts here; position 0 always does) -> start / end
 static void doc_layout(Tensor flags, Tensor start, Tensor end) {
   TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kByte && flags.is_contiguous() && flags.dim() == 2,
@@ -1415,6 +1474,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_bwd_win", &flash_bwd_win, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
         py::arg("delta"), py::arg("dqkv"), py::arg("window"), py::arg("doc_start"), py::arg("doc_end"), py::arg("B"),
         py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
+        py::arg("part") = py::none(), py::arg("qs") = 1);
+  m.def("flash_fwd_drop", &flash_fwd_drop, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("window"),
+        py::arg("doc_start"), py::arg("doc_end"), py::arg("thr"), py::arg("seed"), py::arg("offset"),
+        py::arg("off_dev"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"));
+  m.def("flash_bwd_drop", &flash_bwd_drop, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("delta"), py::arg("dqkv"), py::arg("window"), py::arg("doc_start"), py::arg("doc_end"),
+        py::arg("thr"), py::arg("seed"), py::arg("offset"), py::arg("off_dev"), py::arg("B"), py::arg("T"),
+        py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
         py::arg("part") = py::none(), py::arg("qs") = 1);
   m.def("doc_layout", &doc_layout);
   m.def("synth_doc_flags", &synth_doc_flags);

@@ -59,9 +59,9 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x, residual, docs=None, window=None):
+    def forward(self, x, residual, docs=None, window=None, dropout_p=0.0):
         qkv = self.c_attn(x)
-        y = ops.causal_attention(qkv, self.n_head, docs=docs, window=window)
+        y = ops.causal_attention(qkv, self.n_head, docs=docs, window=window, dropout_p=dropout_p)
         return self.c_proj(y, residual=residual)
 
 
@@ -83,30 +83,34 @@ class Block(nn.Module):
         self.ln_2 = LayerNorm(cfg.n_embd, cfg.layer_norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, prev_bias=None, docs=None, window=None):
+    def forward(self, x, prev_bias=None, docs=None, window=None, dropout_p=0.0):
         # the residual stream passes through each LayerNorm so its gradient is summed inside
         # the norm's backward kernel (no separate add of the two branches' gradients); that
         # kernel also reduces the bias gradient of the projection that wrote the stream
         # (prev_bias: the previous block's MLP c_proj, then this block's attention c_proj)
         h, x = self.ln_1(x, passthrough=True, grad_sum_into=prev_bias)
-        x = self.attn(h, residual=x, docs=docs, window=window)
+        x = self.attn(h, residual=x, docs=docs, window=window, dropout_p=dropout_p)
         h, x = self.ln_2(x, passthrough=True, grad_sum_into=self.attn.c_proj.bias)
         return self.mlp(h, residual=x)
 
 
 class GPT2(nn.Module):
     def __init__(self, cfg: GPT2Config, z_loss: float = 0.0, label_smoothing: float = 0.0,
-                 sliding_window: int | None = None):
+                 sliding_window: int | None = None, attn_dropout: float = 0.0):
         """z_loss / label_smoothing: the two optional terms of ops.lm_head_cross_entropy, plain
         attributes (not in the config, not in the state_dict; settable later).  With either one
         non-zero `forward(idx, targets)` still returns the optimised loss and leaves the mean
         plain cross-entropy of that forward in `self.last_ce` (a 0-dim device tensor); a forward
         with both at 0 sets it back to None.
         sliding_window (None = off): a plain attribute like them; every block's attention sees
-        the last `sliding_window` keys only (ops.causal_attention window=)."""
+        the last `sliding_window` keys only (ops.causal_attention window=).
+        attn_dropout (0 = off): a plain attribute too; GPT-2's attn_pdrop, dropout on the attention
+        probabilities of every block (ops.causal_attention dropout_p=), active only in train mode.
+        The masks come from ops.default_stream(), whose state the trainer checkpoints."""
         super().__init__()
         self.cfg = cfg
         self.sliding_window = sliding_window
+        self.attn_dropout = attn_dropout
         self.z_loss, self.label_smoothing, self.last_ce = z_loss, label_smoothing, None
         self.wte = nn.Parameter(torch.empty(cfg.padded_vocab, cfg.n_embd))
         self.wpe = nn.Parameter(torch.empty(cfg.n_positions, cfg.n_embd))
@@ -139,8 +143,9 @@ class GPT2(nn.Module):
         row, not of the document): resetting them needs a different embedding backward."""
         x = ops.embedding(idx, self.wte, self.wpe)
         prev_bias = None
+        pdrop = float(self.attn_dropout or 0.0) if self.training else 0.0
         for blk in self.h:
-            x = blk(x, prev_bias, docs, self.sliding_window or None)
+            x = blk(x, prev_bias, docs, self.sliding_window or None, pdrop)
             prev_bias = blk.mlp.c_proj.bias
         x = self.ln_f(x, grad_sum_into=prev_bias)
         if targets is not None:

@@ -67,11 +67,11 @@ class Attention(nn.Module):
         self.wqkv = nn.Parameter(torch.empty((cfg.n_heads + 2 * cfg.n_kv_heads) * hd, cfg.dim))
         self.wo = nn.Parameter(torch.empty(cfg.dim, cfg.n_heads * hd))
 
-    def forward(self, x, residual, docs=None, window=None):
+    def forward(self, x, residual, docs=None, window=None, dropout_p=0.0):
         c = self.cfg
         qkv = ops.linear(x, self.wqkv)
         qkv = apply_rope(qkv, c.n_heads, c.n_kv_heads, c.rope_theta, docs=docs)
-        y = ops.causal_attention(qkv, c.n_heads, c.n_kv_heads, docs=docs, window=window)
+        y = ops.causal_attention(qkv, c.n_heads, c.n_kv_heads, docs=docs, window=window, dropout_p=dropout_p)
         return ops.linear(y, self.wo, residual=residual)
 
 
@@ -93,16 +93,16 @@ class TransformerBlock(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x, docs=None, window=None):
+    def forward(self, x, docs=None, window=None, dropout_p=0.0):
         h, x = self.attention_norm(x, passthrough=True)
-        x = self.attention(h, residual=x, docs=docs, window=window)
+        x = self.attention(h, residual=x, docs=docs, window=window, dropout_p=dropout_p)
         h, x = self.ffn_norm(x, passthrough=True)
         return self.feed_forward(h, residual=x)
 
 
 class Llama(nn.Module):
     def __init__(self, cfg: LlamaConfig, device=None, z_loss: float = 0.0, label_smoothing: float = 0.0,
-                 sliding_window: int | None = None):
+                 sliding_window: int | None = None, attn_dropout: float = 0.0):
         """z_loss / label_smoothing: the two optional terms of ops.lm_head_cross_entropy, plain
         attributes (not in the config, not in the state_dict; settable later).  With either one
         non-zero `forward(idx, targets)` still returns the optimised loss and leaves the mean
@@ -110,10 +110,14 @@ class Llama(nn.Module):
         with both at 0 sets it back to None.
         sliding_window (None = off): a plain attribute like them; every block's attention sees
         the last `sliding_window` keys only (ops.causal_attention window=).  RoPE positions are
-        unchanged: absolute, or per document with docs."""
+        unchanged: absolute, or per document with docs.
+        attn_dropout (0 = off): a plain attribute too; dropout on the attention probabilities of
+        every block (ops.causal_attention dropout_p=), active only in train mode.  The masks come
+        from ops.default_stream(), whose state the trainer checkpoints."""
         super().__init__()
         self.cfg = cfg
         self.sliding_window = sliding_window
+        self.attn_dropout = attn_dropout
         self.z_loss, self.label_smoothing, self.last_ce = z_loss, label_smoothing, None
         factory = {"device": device} if device is not None else {}
         with torch.device(device) if device is not None else _nullctx():
@@ -144,8 +148,9 @@ class Llama(nn.Module):
         """docs (ops.DocLayout, packed sequences): in every block the rotary positions restart
         with each document and attention is restricted to the token's own document."""
         x = ops.embedding(idx, self.tok_embeddings)
+        pdrop = float(self.attn_dropout or 0.0) if self.training else 0.0
         for blk in self.layers:
-            x = blk(x, docs, self.sliding_window or None)
+            x = blk(x, docs, self.sliding_window or None, pdrop)
         x = self.norm(x)
         if targets is not None:
             if self.z_loss or self.label_smoothing:

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from . import gemm as G
 from ._ext import gpu_ext, require_dtype
+from .random import PhiloxStream, default_stream, philox4x32
 
 
 def _qkv_layout(B, T, H, Hkv, Dh):
@@ -199,13 +200,20 @@ class _FlashAttention(torch.autograd.Function):
     """Fused causal flash attention (csrc/kernels/attn_flash.hip): no T x T matrix in HBM."""
 
     @staticmethod
-    def forward(ctx, qkv, B, T, H, Hkv, Dh, docs=None, window=None):
-        """window (int, 1 <= window < T, or None): the sliding-window kernels, with or without docs."""
+    def forward(ctx, qkv, B, T, H, Hkv, Dh, docs=None, window=None, drop=None):
+        """window (int, 1 <= window < T, or None): the sliding-window kernels, with or without docs.
+        drop (None, or (thr, seed, offset, device_base)): the dropout kernels, under any mask; the
+        backward regenerates the mask from the same stream position."""
         qkv = qkv.contiguous()
         out = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B * H, T), dtype=torch.float32, device=qkv.device)
         scale = 1.0 / math.sqrt(Dh)
-        if window is not None:
+        if drop is not None:
+            thr, seed, offset, base = drop
+            gpu_ext().flash_fwd_drop(qkv, out, lse, window or 0, docs.start if docs is not None else None,
+                                     docs.end if docs is not None else None, thr, seed, offset, base,
+                                     B, T, H, Hkv, Dh, scale)
+        elif window is not None:
             gpu_ext().flash_fwd_win(qkv, out, lse, window, docs.start if docs is not None else None,
                                     docs.end if docs is not None else None, B, T, H, Hkv, Dh, scale)
         elif docs is None:
@@ -216,6 +224,7 @@ class _FlashAttention(torch.autograd.Function):
         ctx.dims = (B, T, H, Hkv, Dh, scale)
         ctx.docs = docs  # (int32 layout tensors: no gradient, shared by every layer of the step)
         ctx.window = window
+        ctx.drop = drop
         return out
 
     @staticmethod
@@ -232,7 +241,13 @@ class _FlashAttention(torch.autograd.Function):
         part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device=qkv.device) if qs > 1 else None
         dout = dout.contiguous()
         docs = ctx.docs
-        if ctx.window is not None:
+        if ctx.drop is not None:
+            thr, seed, offset, base = ctx.drop
+            gpu_ext().flash_bwd_drop(qkv, out, dout, lse, delta, dqkv, ctx.window or 0,
+                                     docs.start if docs is not None else None,
+                                     docs.end if docs is not None else None, thr, seed, offset, base,
+                                     B, T, H, Hkv, Dh, scale, cs, part, qs)
+        elif ctx.window is not None:
             gpu_ext().flash_bwd_win(qkv, out, dout, lse, delta, dqkv, ctx.window,
                                     docs.start if docs is not None else None,
                                     docs.end if docs is not None else None, B, T, H, Hkv, Dh, scale, cs, part, qs)
@@ -243,7 +258,7 @@ class _FlashAttention(torch.autograd.Function):
                                     cs, part, qs)
         if cs is not None:
             G.offer_colsum_partials(dqkv, cs)
-        return dqkv, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 def _dkdv_head_split(B: int, T: int, H: int, Hkv: int, device) -> int:
@@ -276,7 +291,45 @@ def window_mask(T: int, window: int, device=None) -> torch.Tensor:
     return (t[None, :] <= t[:, None]) & (t[None, :] > t[:, None] - window)
 
 
-def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None, window=None):
+def attention_dropout_keep(p: float) -> tuple[int, float]:
+    """(thr, inv_keep) of attention dropout at probability p.  The drop probability is quantised
+    to 1/256: thr = round(256 p) must lie in 1..255, an element is dropped with probability
+    thr / 256 (p = 0.1 -> 26 / 256) and the survivors are scaled by inv_keep = 256 / (256 - thr),
+    the realised keep probability, so the expectation is exact."""
+    thr = int(round(256.0 * float(p)))
+    if not 1 <= thr <= 255:
+        raise ValueError(f"attention dropout: round(256 * p) must lie in 1..255, got p={p} (thr={thr})")
+    return thr, 256.0 / (256 - thr)
+
+
+def attention_dropout_counters(B: int, H: int, T: int) -> int:
+    """Philox counters one attention dropout forward reserves: one per 4 x 4 block of every
+    (b, h) score matrix, the blocks above the diagonal included."""
+    if T % 4:
+        raise ValueError(f"attention dropout needs T % 4 == 0, got T={T}")
+    return B * H * (T // 4) ** 2
+
+
+def attention_dropout_mask(seed: int, offset: int, B: int, H: int, T: int, p: float) -> torch.Tensor:
+    """The keep mask of the flash kernels (attn_flash.hip drop_keep16) as a bool [B, H, T, T] CPU
+    tensor, built in numpy on `philox4x32`: block = ((b H + h) nb + q // 4) nb + key // 4 with
+    nb = T / 4, words = Philox(seed, 0, offset + block); word q % 4, byte key % 4 (little end
+    first) decides element (q, key), kept iff byte >= thr."""
+    import numpy as np
+
+    thr, _ = attention_dropout_keep(p)
+    n, nb = attention_dropout_counters(B, H, T), T // 4
+    ctr = (np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & ((1 << 64) - 1)))  # (wraps mod 2^64)
+    words = philox4x32(seed, 0, ctr)                                         # [n, 4]: word = q % 4
+    shifts = np.array([0, 8, 16, 24], dtype=np.uint32)
+    byte = (words[:, :, None] >> shifts[None, None, :]) & np.uint32(0xFF)     # [n, q % 4, key % 4]
+    keep = (byte >= np.uint32(thr)).reshape(B, H, nb, nb, 4, 4).transpose(0, 1, 2, 4, 3, 5).reshape(B, H, T, T)
+    return torch.from_numpy(np.ascontiguousarray(keep))
+
+
+def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None, window=None, keep=None, inv_keep=1.0):
+    """keep (bool [B, H, T, T], attention_dropout_mask) with inv_keep: attention dropout, through an
+    explicit softmax - P is normalised over every allowed key, then the kept entries are scaled."""
     C = H * Dh
     q = qkv[..., :C].reshape(B, T, H, Dh).transpose(1, 2)
     k = qkv[..., C:C + Hkv * Dh].reshape(B, T, Hkv, Dh).transpose(1, 2)
@@ -284,6 +337,15 @@ def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None, window=None):
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=1)
         v = v.repeat_interleave(H // Hkv, dim=1)
+    if keep is not None:
+        allowed = window_mask(T, window if window is not None else T, qkv.device)[None, None]
+        if docs is not None:
+            allowed = allowed & docs.mask()[:, None]
+        s = (q.float() @ k.float().transpose(-1, -2)) * (1.0 / math.sqrt(Dh))
+        pm = torch.softmax(s.masked_fill(~allowed, -math.inf), dim=-1)
+        pm = pm * (keep.to(qkv.device).to(pm.dtype) * inv_keep)
+        o = (pm @ v.float()).to(qkv.dtype)
+        return o.transpose(1, 2).reshape(B, T, C)
     if window is not None:  # boolean band mask, inside the document when both are given
         band = window_mask(T, window, qkv.device)[None, None]
         o = F.scaled_dot_product_attention(q, k, v, attn_mask=band if docs is None else band & docs.mask()[:, None])
@@ -295,14 +357,21 @@ def causal_attention_ref(qkv, B, T, H, Hkv, Dh, docs=None, window=None):
 
 
 def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = None,
-                     docs: DocLayout | None = None, window: int | None = None) -> torch.Tensor:
+                     docs: DocLayout | None = None, window: int | None = None, dropout_p: float = 0.0,
+                     training: bool = True, stream: PhiloxStream | None = None) -> torch.Tensor:
     """qkv: [B, T, (H + 2*Hkv) * Dh] -> [B, T, H*Dh].  docs (packed sequences): row q attends to
     the keys start[q] <= key <= q of its own document only; it needs the flash path - there is
     no unmasked fallback.  window (sliding-window attention, None = off): row q attends to its
     last `window` keys only, max(0, q - window + 1) <= key <= q, within its document when docs is
     given; window >= T masks nothing and runs the kernels that run without it.  Like docs it needs
     the flash path on the GPU.  Without docs and window any T runs: the composed path pads T to a
-    multiple of 64."""
+    multiple of 64.
+    dropout_p (attention dropout, active when training and dropout_p != 0): the probabilities are
+    dropped after the softmax with the quantised probability of attention_dropout_keep, under any
+    mask.  The keep mask is drawn inside the flash kernels from B * H * (T/4)^2 counters reserved
+    from `stream` (default: the default stream) and regenerated in the backward; the CPU path draws
+    the same mask from the same stream state (attention_dropout_mask).  Like docs and window it
+    needs the flash path on the GPU."""
     B, T, W = qkv.shape
     Hkv = n_kv_head or n_head
     Dh = W // (n_head + 2 * Hkv)
@@ -317,11 +386,27 @@ def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = Non
             raise ValueError(f"causal_attention: docs layout is {docs.shape}, qkv is [{B}, {T}, ...]")
         if docs.device != qkv.device:
             raise ValueError(f"causal_attention: docs on {docs.device}, qkv on {qkv.device}")
+    thr = 0
+    if training and dropout_p != 0.0:
+        thr, inv_keep = attention_dropout_keep(dropout_p)
+        ncnt = attention_dropout_counters(B, n_head, T)
     if qkv.is_cuda:
         require_dtype(qkv, "causal_attention")
+    elif thr:
+        seed, offset = (stream or default_stream()).reserve_counters(ncnt)
+        keep = attention_dropout_mask(seed, offset, B, n_head, T, dropout_p)
+        return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh, docs, window, keep, inv_keep)
     else:
         return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh, docs, window)
     impl = os.environ.get("RTDC_ATTN", "flash")
+    if thr:
+        if impl != "flash" or not flash_supported(T, Dh):
+            raise RuntimeError(
+                f"causal_attention: attention dropout needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
+                f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
+        st = stream or default_stream()
+        seed, offset = st.reserve_counters(ncnt)
+        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs, window, (thr, seed, offset, st.device_base()))
     if window is not None:
         if impl != "flash" or not flash_supported(T, Dh):
             raise RuntimeError(

@@ -67,6 +67,17 @@ class PhiloxStream:
             self.offset += n
         return self.seed, off
 
+    def reserve_counters(self, n: int) -> tuple[int, int]:
+        """Reserve `n` consecutive counters (Philox calls, not elements); returns (seed, offset).
+        Attention dropout takes one counter per 4 x 4 block of the score matrix."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"reserve_counters: n must be >= 0, got {n}")
+        with self._lock:
+            off = self.offset
+            self.offset += n
+        return self.seed, off
+
     def state_dict(self) -> dict:
         off = self.offset if self._base is None else int(self._base.item()) + self.offset
         return {"seed": self.seed, "offset": off}

@@ -71,6 +71,7 @@ class WorkloadConfig:
     max_grad_norm: Optional[float] = None  # clip the global gradient norm inside the fused step (None / 0: off)
     doc_len: Optional[int] = None  # LMs: packed sequences of documents of this mean length (None / 0: off)
     sliding_window: Optional[int] = None  # LMs: every attention sees its last N keys only (None / 0: off)
+    attn_dropout: Optional[float] = None  # LMs: dropout on the attention probabilities (None / 0: off)
     # LMs: dtype the fused AdamW stores exp_avg / exp_avg_sq in: "fp32" | "bf16" (bf16: stochastically
     # rounded with bits keyed by `seed`; a checkpoint resumes into the same setting)
     opt_state_dtype: str = "fp32"
@@ -325,6 +326,7 @@ def build(cfg: WorkloadConfig, device) -> Workload:
     # (with documents the batch is (x, y, docs); flops_per_token still counts the full causal triangle,
     # under a sliding window too)
     model.sliding_window = int(cfg.sliding_window) if cfg.sliding_window else None
+    model.attn_dropout = float(cfg.attn_dropout) if cfg.attn_dropout else 0.0
     if aux:
         model.z_loss, model.label_smoothing = zl, ls  # forward() leaves the plain cross-entropy in last_ce
 
@@ -480,6 +482,11 @@ def train_loop_per_worker(config: dict):
     train.torch.enable_reproducibility(cfg.seed)
 
     wl = build(cfg, dev)
+    if cfg.attn_dropout:
+        # every rank's default Philox stream starts at the same seed and would draw the same masks:
+        # seeded per (seed, rank) before the first step; an exact resume then restores the position
+        # from the checkpoint's RNG state.  With attn_dropout off nothing is seeded.
+        ops.manual_seed(int(cfg.seed) * 1000003 + rank)
     # fused optimizers wait for the deferred last bucket themselves (DDP defer_tail_to_optimizer)
     net = train.torch.prepare_model(wl.model, parallel_strategy_kwargs={"defer_tail_to_optimizer": True})
     core, opt = _unwrap(net), wl.optimizer
@@ -608,7 +615,7 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                    dataset_size: int = 1 << 20, name: str | None = None, verbose: int = 1,
                    report_every_n_steps: int | None = None, max_grad_norm: float | None = None,
                    doc_len: int | None = None, sliding_window: int | None = None,
-                   opt_state_dtype: str = "fp32", grad_accum_steps: int = 1,
+                   attn_dropout: float | None = None, opt_state_dtype: str = "fp32", grad_accum_steps: int = 1,
                    lr_schedule: str = "constant", warmup_steps: int = 0, min_lr_ratio: float = 0.0,
                    lr_total_steps: int | None = None, opt_capturable: bool = False, z_loss: float | None = None,
                    label_smoothing: float | None = None):
@@ -619,7 +626,13 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     documents of that mean length, attention and RoPE positions restricted to each document
     (None / 0: off; the report rows are unchanged).  sliding_window (LMs): every attention layer
     sees the last N keys only, within the document under doc_len (None / 0: off; nothing new is
-    checkpointed - a resume passes the same value).  opt_state_dtype (LMs): "fp32" | "bf16" - the
+    checkpointed - a resume passes the same value).  attn_dropout (LMs; None / 0: off): dropout on
+    the attention probabilities of every block, drawn inside the flash kernels
+    (ops.causal_attention dropout_p=; the probability is quantised to 1/256).  Each rank's default
+    Philox stream is then seeded from (seed, rank) before the first step; its position is part of
+    the RNG state every checkpoint already carries, so an exact resume with the same value is
+    bit-identical and nothing new is checkpointed.  Off: nothing is seeded, rows, checkpoints and
+    bits are unchanged.  opt_state_dtype (LMs): "fp32" | "bf16" - the
     dtype FusedAdamW stores its moments in (bf16: half the optimizer memory and checkpoint bytes,
     stochastic rounding keyed by `seed`; the report rows are unchanged).  grad_accum_steps = k:
     every optimizer step accumulates k micro-batches in place (optim.GradAccumulator) and applies
@@ -647,6 +660,8 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
     check_loss_coeffs(label_smoothing, z_loss)  # (argument errors here, not in the workers)
     if sliding_window and int(sliding_window) < 1:
         raise ValueError(f"sliding_window must be >= 1 (None / 0: off), got {sliding_window}")
+    if attn_dropout:
+        ops.attention_dropout_keep(attn_dropout)  # (ValueError here, not in the workers)
     if zero_stage < 0:
         zero_stage = default_zero_stage(model, num_workers)
     cfg = WorkloadConfig(model=model, steps=steps, batch_size_per_worker=batch_size_per_worker, seq_len=seq_len,
@@ -654,6 +669,7 @@ def train_workload(model: str = "gpt2-tiny", steps: int = 20, num_workers: int =
                          checkpoint=checkpoint, dataset_size=dataset_size, report_every_n_steps=report_every_n_steps,
                          max_grad_norm=max_grad_norm or None, doc_len=doc_len or None,
                          sliding_window=int(sliding_window) if sliding_window else None,
+                         attn_dropout=float(attn_dropout) if attn_dropout else None,
                          opt_state_dtype=opt_state_dtype, grad_accum_steps=int(grad_accum_steps),
                          lr_schedule=lr_schedule, warmup_steps=int(warmup_steps or 0),
                          min_lr_ratio=float(min_lr_ratio or 0.0), lr_total_steps=lr_total_steps or None,
@@ -696,6 +712,8 @@ def main(argv=None):
                          "RoPE positions per document (default: off)")
     ap.add_argument("--sliding-window", type=int, default=None,
                     help="LMs: sliding-window attention, every layer sees its last N keys only (default: off)")
+    ap.add_argument("--attn-dropout", type=float, default=None,
+                    help="LMs: dropout on the attention probabilities, inside the flash kernels (default: off)")
     ap.add_argument("--opt-state-dtype", default="fp32", choices=sorted(_OPT_STATE_DTYPES),
                     help="LMs: dtype of the fused AdamW's stored moments (bf16: stochastically rounded)")
     ap.add_argument("--grad-accum-steps", type=int, default=1,
@@ -722,7 +740,7 @@ def main(argv=None):
     res = train_workload(a.model, a.steps, a.num_workers, use_gpu, a.batch, a.seq_len, None, a.ckpt_every, a.keep,
                          a.storage, max_failures=a.max_failures, grad_comm_dtype=a.grad_comm_dtype,
                          zero_stage=a.zero_stage, max_grad_norm=a.max_grad_norm, doc_len=a.doc_len,
-                         sliding_window=a.sliding_window,
+                         sliding_window=a.sliding_window, attn_dropout=a.attn_dropout,
                          opt_state_dtype=a.opt_state_dtype, grad_accum_steps=a.grad_accum_steps,
                          lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, min_lr_ratio=a.min_lr_ratio,
                          lr_total_steps=a.lr_total_steps, opt_capturable=a.opt_capturable, z_loss=a.z_loss,

@@ -63,6 +63,26 @@ def parse(path):
     return stats
 
 
+def stream(path, name):
+    """The instruction stream of one kernel body: comments and directives dropped, the local labels
+    (.LBB<function>_<block>) renumbered by first appearance, so two builds compare line by line."""
+    out, inside, labels = [], False, {}
+    ren = lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels))
+    for ln in open(path):
+        if ln.startswith(name + ":"):
+            inside = True
+            continue
+        if not inside:
+            continue
+        s = ln.split(";")[0].strip()
+        if s.startswith(".Lfunc_end"):
+            break
+        if not s or (s.startswith(".") and not s.endswith(":")):
+            continue
+        out.append(re.sub(r"\.LBB\d+_\d+", ren, s))
+    return out
+
+
 def plain_name(d):
     """Every trailing `false` template argument dropped (kernel<A, false, false> and the parent's
     kernel<A, false> are both kernel<A>), and with it the empty argument struct that such a switch
@@ -72,14 +92,16 @@ def plain_name(d):
     # name2_kernel<D, NS[, true]> is name_kernel<D, NS, doc, 2> and name_kernel<D, NS[, true]> is
     # name_kernel<D, NS, doc, 1>; both trees are keyed by the four-argument name (a pair that is
     # still two kernels in both trees lines up under those names as well)
-    m = re.match(r"(.*\bfa::(?:fwd|bwd_dq|bwd_dkdv))(2?)_kernel<(\d+), (\d+)(?:, (true|false|\d+))?(?:, (\d+))?>(.*)$",
+    m = re.match(r"(.*\bfa::(?:fwd|bwd_dq|bwd_dkdv))(2?)_kernel<(\d+), (\d+)(?:, (true|false|\d+))?(?:, (\d+))?(?:, (true|false))?>(.*)$",
                  d)
     if m:
         # the mask switch was a bool (false / true = documents) before it became the int MASK
         # (0 none, 1 documents, 2 sliding window): 0 / 1 are listed under the bool's names
         mask = {"0": "false", "1": "true", "2": "window"}.get(m.group(5) or "0", m.group(5))
-        return "%s_kernel<%s, %s, %s, %d>%s" % (m.group(1), m.group(3), m.group(4), mask,
-                                                2 if m.group(2) else int(m.group(6) or 1), m.group(7))
+        # a trailing bool is the attention-dropout switch DROP: false keeps the four-argument name
+        return "%s_kernel<%s, %s, %s, %d%s>%s" % (m.group(1), m.group(3), m.group(4), mask,
+                                                  2 if m.group(2) else int(m.group(6) or 1),
+                                                  ", drop" if m.group(7) == "true" else "", m.group(8))
     while True:
         n = re.sub(r", false>", ">", d)
         if n == d:
@@ -99,8 +121,10 @@ def main(argv):
     tabs = [parse(p) for p in argv]
     # key by the demangled name; a defaulted trailing `false` template argument (the parent's
     # kernel<DH, NS> is the new kernel<DH, NS, false>) names the same kernel
+    mangled = [{}, {}]
     for i, t in enumerate(tabs):
         d = demangle(sorted(t))
+        mangled[i] = {plain_name(d[k]): k for k in t}
         tabs[i] = {plain_name(d[k]): v for k, v in t.items()}
     names = sorted(set().union(*tabs))
     dm = {n: n for n in names}
@@ -122,6 +146,15 @@ def main(argv):
         print("%-52s %s%s" % (short(dm[n]), "  ".join(cells), "   DIFFERS" if diff else ""))
     if len(tabs) == 2:
         print("kernels in both builds that differ: %d" % bad)
+        # beyond the counts: the instruction streams of the kernels present in both builds
+        print()
+        for n in names:
+            if n in tabs[0] and n in tabs[1]:
+                a, b = stream(argv[0], mangled[0][n]), stream(argv[1], mangled[1][n])
+                nd = sum(x != y for x, y in zip(a, b)) + abs(len(a) - len(b))
+                bad += nd != 0
+                print("%-46s %5d insts  %s" % (short(n), len([x for x in a if not x.endswith(":")]),
+                                              "identical instruction stream" if nd == 0 else "%d lines differ" % nd))
     return 1 if bad else 0
 
 

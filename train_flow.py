@@ -65,6 +65,9 @@ class RayTorchTrain(FlowSpec):
     sliding_window = Parameter("sliding_window", default=0,
                                help="LM workloads: sliding-window attention, every layer sees its last N keys only "
                                     "(0: off)")
+    attn_dropout = Parameter("attn_dropout", default=0.0,
+                             help="LM workloads: dropout on the attention probabilities, drawn inside the flash "
+                                  "kernels; the probability is quantised to 1/256 (0: off)")
     opt_state_dtype = Parameter("opt_state_dtype", default="fp32",
                                 help="LM workloads: fp32 | bf16 - dtype of the fused AdamW's stored moments (bf16: "
                                      "stochastically rounded, half the optimizer memory and checkpoint bytes)")
@@ -142,6 +145,7 @@ class RayTorchTrain(FlowSpec):
                 report_every_n_steps=int(self.report_every_n_steps) or None,
                 max_grad_norm=float(self.max_grad_norm) or None, doc_len=int(self.doc_len) or None,
                 sliding_window=int(self.sliding_window) or None,
+                attn_dropout=float(self.attn_dropout) or None,
                 opt_state_dtype=str(self.opt_state_dtype), grad_accum_steps=int(self.grad_accum_steps),
                 lr_schedule=str(self.lr_schedule), warmup_steps=int(self.warmup_steps),
                 min_lr_ratio=float(self.min_lr_ratio), lr_total_steps=int(self.lr_total_steps) or None,

@@ -140,6 +140,9 @@ int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, 
 int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st);
 int rtdc_synth_doc_flags(const int64_t* ids, int B, int T, long long doc_len, unsigned long long seed_add,
                          uint8_t* flags, hipStream_t st);
+int rtdc_decode_attn(const void* qkv_new, void* cache, const int* pos, const float* cosb, const float* sinb, void* out,
+                     float* part, int B, int Tmax, int H, int Hkv, int Dh, int window, int nsplit, float scale,
+                     hipStream_t st);
 }
 
 static hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
@@ -934,6 +937,51 @@ static void rope(Tensor x, Tensor y, Tensor cosb, Tensor sinb, int64_t T, int64_
                      (int)nrot_heads, (int)ntot_heads, (int)Dh, inverse, cur_stream()),
            "rope");
 }
+// Decode attention (attn_decode.hip): one new token per row of qkv_new [B, (H + 2 Hkv) Dh] against
+// cache [B, Tmax, 2 Hkv Dh]; stores the token's k|v row at cache[b, pos[b]] and writes out [B, H Dh].
+// part: fp32 workspace of at least B * H * nsplit * (Dh + 2) elements.  cosb / sinb: rope tables
+// with at least Tmax rows, or both absent.
+static void decode_attn(Tensor qkv_new, Tensor cache, Tensor pos, c10::optional<Tensor> cosb,
+                        c10::optional<Tensor> sinb, Tensor out, Tensor part, int64_t H, int64_t Hkv, int64_t window,
+                        int64_t nsplit, double scale) {
+  TORCH_CHECK(qkv_new.dim() == 2 && cache.dim() == 3 && pos.dim() == 1 && out.dim() == 2,
+              "decode_attn: qkv_new [B, W], cache [B, Tmax, 2 Hkv Dh], pos [B], out [B, H Dh] expected");
+  const int64_t B = qkv_new.size(0), Tmax = cache.size(1);
+  TORCH_CHECK(H >= 1 && Hkv >= 1 && H % Hkv == 0 && qkv_new.size(1) % (H + 2 * Hkv) == 0, "decode_attn: bad head counts");
+  const int64_t Dh = qkv_new.size(1) / (H + 2 * Hkv);
+  check_dev(qkv_new, "decode_attn: qkv_new");
+  check_dev(cache, "decode_attn: cache");
+  check_dev(out, "decode_attn: out");
+  TORCH_CHECK(part.is_cuda(), "decode_attn: part must be a GPU tensor");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
+              "decode_attn: pos must be contiguous int32 [B] on the device");
+  TORCH_CHECK(qkv_new.scalar_type() == at::kBFloat16 && cache.scalar_type() == at::kBFloat16 &&
+                  out.scalar_type() == at::kBFloat16 && part.scalar_type() == at::kFloat,
+              "decode_attn: bf16 qkv_new / cache / out and fp32 part expected");
+  TORCH_CHECK(qkv_new.is_contiguous() && cache.is_contiguous() && out.is_contiguous() && part.is_contiguous(),
+              "decode_attn: contiguous tensors expected");
+  TORCH_CHECK(cache.size(0) == B && cache.size(2) == 2 * Hkv * Dh && out.size(0) == B && out.size(1) == H * Dh,
+              "decode_attn: cache / out do not match qkv_new");
+  TORCH_CHECK(cache.device() == qkv_new.device() && out.device() == qkv_new.device() &&
+                  part.device() == qkv_new.device() && pos.device() == qkv_new.device(),
+              "decode_attn: tensors on different devices");
+  TORCH_CHECK(nsplit >= 1 && part.numel() >= B * H * nsplit * (Dh + 2), "decode_attn: part workspace too small");
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "decode_attn: window must be >= 0 (0 = off)");
+  TORCH_CHECK(cosb.has_value() == sinb.has_value(), "decode_attn: cos and sin tables go together");
+  const float *cp = nullptr, *sp = nullptr;
+  if (cosb.has_value()) {
+    for (const Tensor* t : {&*cosb, &*sinb})
+      TORCH_CHECK(t->is_cuda() && t->device() == qkv_new.device() && t->scalar_type() == at::kFloat &&
+                      t->is_contiguous() && t->dim() == 2 && t->size(0) >= Tmax && t->size(1) == Dh / 2,
+                  "decode_attn: rope tables must be contiguous fp32 [>= Tmax, Dh / 2] on the device");
+    cp = cosb->data_ptr<float>();
+    sp = sinb->data_ptr<float>();
+  }
+  check_rc(rtdc_decode_attn(qkv_new.data_ptr(), cache.data_ptr(), pos.data_ptr<int>(), cp, sp, out.data_ptr(),
+                            part.data_ptr<float>(), (int)B, (int)Tmax, (int)H, (int)Hkv, (int)Dh, (int)window,
+                            (int)nsplit, (float)scale, cur_stream()),
+           "decode_attn");
+}
 static void swiglu_fwd(Tensor gu, Tensor h) {
   const int64_t F = h.size(-1), M = h.numel() / F;
   check_rc(rtdc_swiglu_fwd(gu.data_ptr(), h.data_ptr(), M, (int)F, cur_stream()), "swiglu_fwd");
@@ -1487,6 +1535,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("synth_doc_flags", &synth_doc_flags);
   m.def("rope", &rope);
   m.def("rope_doc", &rope_doc);
+  m.def("decode_attn", &decode_attn, py::arg("qkv_new"), py::arg("cache"), py::arg("pos"), py::arg("cos"),
+        py::arg("sin"), py::arg("out"), py::arg("part"), py::arg("H"), py::arg("Hkv"), py::arg("window"),
+        py::arg("nsplit"), py::arg("scale"));
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("im2col", &im2col);

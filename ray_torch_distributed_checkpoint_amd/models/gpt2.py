@@ -159,6 +159,27 @@ class GPT2(nn.Module):
         logits = ops.linear(x, self.wte)
         return logits[..., : self.cfg.vocab_size]
 
+    def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
+        """The forward over the prompt idx [B, P] (dropout off) that fills the ops.KVCache and
+        returns the logits [B, vocab_size] of the last position only (models/generation.py)."""
+        from .generation import gpt2_prefill
+
+        return gpt2_prefill(self, idx, cache)
+
+    def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
+        """One token per row, tok [B], at the cache's positions -> logits [B, vocab_size]."""
+        from .generation import gpt2_decode_step
+
+        return gpt2_decode_step(self, tok, cache)
+
+    def generate(self, idx, max_new_tokens, temperature=0.0, top_k=None, seed=0, eos_id=None):
+        """idx [B, P] -> [B, P + max_new_tokens] with a KV cache: greedy at temperature 0, else
+        temperature / top-k sampling from a generator seeded with `seed`.  Honours
+        sliding_window; packed documents (docs) are not supported."""
+        from .generation import generate
+
+        return generate(self, idx, max_new_tokens, temperature, top_k, seed, eos_id)
+
     def flops_per_token(self, T: int, causal: bool = True) -> float:
         """Training FLOPs per token (6N + attention), N without the embedding table."""
         c = self.cfg

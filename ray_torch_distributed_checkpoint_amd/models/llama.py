@@ -162,6 +162,27 @@ class Llama(nn.Module):
             return ops.lm_head_cross_entropy(x, self.output, targets, self.cfg.vocab_size)
         return ops.linear(x, self.output)[..., : self.cfg.vocab_size]
 
+    def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
+        """The forward over the prompt idx [B, P] (dropout off) that fills the ops.KVCache and
+        returns the logits [B, vocab_size] of the last position only (models/generation.py)."""
+        from .generation import llama_prefill
+
+        return llama_prefill(self, idx, cache)
+
+    def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
+        """One token per row, tok [B], at the cache's positions -> logits [B, vocab_size]."""
+        from .generation import llama_decode_step
+
+        return llama_decode_step(self, tok, cache)
+
+    def generate(self, idx, max_new_tokens, temperature=0.0, top_k=None, seed=0, eos_id=None):
+        """idx [B, P] -> [B, P + max_new_tokens] with a KV cache: greedy at temperature 0, else
+        temperature / top-k sampling from a generator seeded with `seed`.  Honours
+        sliding_window; packed documents (docs) are not supported."""
+        from .generation import generate
+
+        return generate(self, idx, max_new_tokens, temperature, top_k, seed, eos_id)
+
     def split_qkv_w13(self) -> dict:
         """HF-style unfused view of the weights (q/k/v_proj, gate/up_proj)."""
         c = self.cfg

@@ -7,6 +7,7 @@ and gloo multi-process tests).
 from ._ext import available as native_available, ext  # noqa: F401
 from .attention import (DocLayout, attention_dropout_keep, attention_dropout_mask,  # noqa: F401
                         causal_attention)
+from .decode import KVCache, decode_attention  # noqa: F401
 from .dropout import dropout  # noqa: F401
 from .embedding import embedding  # noqa: F401
 from .linear import fused_mlp, linear  # noqa: F401

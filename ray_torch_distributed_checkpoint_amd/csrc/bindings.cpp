@@ -143,6 +143,9 @@ int rtdc_synth_doc_flags(const int64_t* ids, int B, int T, long long doc_len, un
 int rtdc_decode_attn(const void* qkv_new, void* cache, const int* pos, const float* cosb, const float* sinb, void* out,
                      float* part, int B, int Tmax, int H, int Hkv, int Dh, int window, int nsplit, float scale,
                      hipStream_t st);
+int rtdc_gemm_few_rows(const void* x, const void* w, const void* bias, int bias_type, const void* res, void* y, int M,
+                       int N, int K, int act, hipStream_t st);
+void rtdc_few_rows_plan(long long N, long long K, int* waves, int* per);
 }
 
 static hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
@@ -982,6 +985,51 @@ static void decode_attn(Tensor qkv_new, Tensor cache, Tensor pos, c10::optional<
                             (int)nsplit, (float)scale, cur_stream()),
            "decode_attn");
 }
+// Few-row linear (gemm_few_rows.hip): out[M, N] = act(x[M, K] . w[N, K]^T + bias + residual), 1 <= M <= 16,
+// K % 64 == 0, N % 8 == 0, every operand contiguous and 16-byte aligned; act 0 (none) or 2 (tanh GELU).
+// Anything else is refused here, before a launch: there is no other kernel behind this entry.
+static void gemm_few_rows(Tensor x, Tensor w, c10::optional<Tensor> bias, c10::optional<Tensor> residual, Tensor out,
+                          int64_t act) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "gemm_few_rows: x [M, K], w [N, K], out [M, N] expected");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 &&
+                  out.scalar_type() == at::kBFloat16,
+              "gemm_few_rows: bf16 x, w and out expected");
+  check_dev(x, "gemm_few_rows: x");
+  check_dev(w, "gemm_few_rows: w");
+  check_dev(out, "gemm_few_rows: out");
+  TORCH_CHECK(M >= 1 && M <= 16, "gemm_few_rows: 1 <= M <= 16 rows expected, got ", M);
+  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "gemm_few_rows: shapes do not match");
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && N >= 8 && N % 8 == 0 && N <= INT32_MAX && K <= INT32_MAX,
+              "gemm_few_rows: K % 64 == 0 and N % 8 == 0 expected, got N=", N, " K=", K);
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous(), "gemm_few_rows: contiguous x, w and out expected");
+  TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "gemm_few_rows: tensors on different devices");
+  TORCH_CHECK(act == 0 || act == 2, "gemm_few_rows: act must be 0 (none) or 2 (gelu_tanh)");
+  int bias_type = 0;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat,
+                "gemm_few_rows: bias must be bf16 or fp32");
+    check_dev(*bias, "gemm_few_rows: bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(),
+                "gemm_few_rows: bias must be a contiguous [N] tensor on x's device");
+    bias_type = bias->scalar_type() == at::kBFloat16 ? 1 : 2;
+  }
+  if (residual.has_value()) {
+    check_dev(*residual, "gemm_few_rows: residual");
+    TORCH_CHECK(residual->scalar_type() == at::kBFloat16 && residual->is_contiguous() && residual->dim() == 2 &&
+                    residual->size(0) == M && residual->size(1) == N && residual->device() == x.device(),
+                "gemm_few_rows: residual must be a contiguous bf16 [M, N] tensor on x's device");
+  }
+  check_rc(rtdc_gemm_few_rows(x.data_ptr(), w.data_ptr(), ptr_or_null(bias), bias_type, ptr_or_null(residual),
+                              out.data_ptr(), (int)M, (int)N, (int)K, (int)act, cur_stream()),
+           "gemm_few_rows");
+}
+// (waves per 16-column block, chunks of 64 k per wave) that gemm_few_rows launches for (N, K)
+static std::vector<int64_t> few_rows_plan(int64_t N, int64_t K) {
+  int waves = 0, per = 0;
+  rtdc_few_rows_plan(N, K, &waves, &per);
+  return {waves, per};
+}
 static void swiglu_fwd(Tensor gu, Tensor h) {
   const int64_t F = h.size(-1), M = h.numel() / F;
   check_rc(rtdc_swiglu_fwd(gu.data_ptr(), h.data_ptr(), M, (int)F, cur_stream()), "swiglu_fwd");
@@ -1538,6 +1586,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn", &decode_attn, py::arg("qkv_new"), py::arg("cache"), py::arg("pos"), py::arg("cos"),
         py::arg("sin"), py::arg("out"), py::arg("part"), py::arg("H"), py::arg("Hkv"), py::arg("window"),
         py::arg("nsplit"), py::arg("scale"));
+  m.def("gemm_few_rows", &gemm_few_rows, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("residual"),
+        py::arg("out"), py::arg("act"));
+  m.def("few_rows_plan", &few_rows_plan);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("im2col", &im2col);

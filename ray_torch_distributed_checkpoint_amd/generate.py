@@ -2,11 +2,14 @@
 
     python -m ray_torch_distributed_checkpoint_amd.generate --model gpt2-tiny --checkpoint DIR \\
         [--prompt-ids 1,2,3 | --prompt-len 16] --max-new-tokens 32 [--temperature --top-k --seed --batch]
+        [--few-row] [--captured] [--fast]
 
 Builds the model, loads the "model" part of the DCP checkpoint directory (what
 `workloads.restore(mode="weights")` loads) and runs `model.generate()` (KV cache, split-KV decode
 kernel on the GPU).  There is no tokenizer in the tree: the prompt is a list of token ids, or
 `--prompt-len` tokens of each of the first `--batch` rows of the workloads' SyntheticTokens.
+`--few-row` runs the decode linears on the weight-streaming few-row kernel (batch <= 16),
+`--captured` replays the decode step from a hipGraph (GPU only), `--fast` sets both.
 Prints one JSON line: the token ids and the tokens per second.
 """
 from __future__ import annotations
@@ -52,7 +55,7 @@ def prompt_tokens(args, vocab: int, device) -> torch.Tensor:
     return data.batch(torch.arange(args.batch, device=device))[0]
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="generate tokens from a GPT-2 / Llama checkpoint with a KV cache")
     ap.add_argument("--model", default="gpt2-tiny")
     ap.add_argument("--checkpoint", default=None, help="DCP checkpoint directory (default: the random init)")
@@ -66,8 +69,17 @@ def main(argv=None):
     ap.add_argument("--eos-id", type=int, default=None)
     ap.add_argument("--sliding-window", type=int, default=None)
     ap.add_argument("--device", default=None, help="default: cuda when available")
+    ap.add_argument("--few-row", action="store_true", help="decode linears on the few-row kernel (batch <= 16)")
+    ap.add_argument("--captured", action="store_true", help="replay the decode step from a hipGraph (GPU only)")
+    ap.add_argument("--fast", action="store_true", help="--few-row and --captured")
     args = ap.parse_args(argv)
+    if args.fast:
+        args.few_row = args.captured = True
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     device = torch.device(args.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     torch.manual_seed(args.seed)
     model = build_model(args.model, device)
@@ -80,11 +92,11 @@ def main(argv=None):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = model.generate(idx, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k, seed=args.seed,
-                         eos_id=args.eos_id)
+                         eos_id=args.eos_id, few_row=args.few_row, captured=args.captured)
     tokens = out.tolist()  # (the device is read here, once)
     dt = time.perf_counter() - t0
     row = {"model": args.model, "device": device.type, "batch": idx.shape[0], "prompt_len": idx.shape[1],
-           "new_tokens": args.max_new_tokens, "tokens": tokens,
+           "new_tokens": args.max_new_tokens, "few_row": args.few_row, "captured": args.captured, "tokens": tokens,
            "tokens_per_s": round(idx.shape[0] * args.max_new_tokens / dt, 2) if dt > 0 else None}
     print(json.dumps(row))
     return row

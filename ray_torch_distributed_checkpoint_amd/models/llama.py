@@ -162,26 +162,32 @@ class Llama(nn.Module):
             return ops.lm_head_cross_entropy(x, self.output, targets, self.cfg.vocab_size)
         return ops.linear(x, self.output)[..., : self.cfg.vocab_size]
 
-    def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
+    def prefill(self, idx: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
         """The forward over the prompt idx [B, P] (dropout off) that fills the ops.KVCache and
-        returns the logits [B, vocab_size] of the last position only (models/generation.py)."""
+        returns the logits [B, vocab_size] of the last position only (models/generation.py).
+        few_row: the last-position LM head on ops.linear_few_rows (B <= 16)."""
         from .generation import llama_prefill
 
-        return llama_prefill(self, idx, cache)
+        return llama_prefill(self, idx, cache, few_row=few_row)
 
-    def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
-        """One token per row, tok [B], at the cache's positions -> logits [B, vocab_size]."""
+    def decode_step(self, tok: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+        """One token per row, tok [B], at the cache's positions -> logits [B, vocab_size].
+        few_row: every linear of the step on ops.linear_few_rows, on the B <= 16 real rows."""
         from .generation import llama_decode_step
 
-        return llama_decode_step(self, tok, cache)
+        return llama_decode_step(self, tok, cache, few_row=few_row)
 
-    def generate(self, idx, max_new_tokens, temperature=0.0, top_k=None, seed=0, eos_id=None):
+    def generate(self, idx, max_new_tokens, temperature=0.0, top_k=None, seed=0, eos_id=None, few_row=False,
+                 captured=False):
         """idx [B, P] -> [B, P + max_new_tokens] with a KV cache: greedy at temperature 0, else
         temperature / top-k sampling from a generator seeded with `seed`.  Honours
-        sliding_window; packed documents (docs) are not supported."""
+        sliding_window; packed documents (docs) are not supported.  few_row / captured (both off by
+        default): the few-row linear kernel and the hipGraph-replayed decode step of
+        models/generation.py."""
         from .generation import generate
 
-        return generate(self, idx, max_new_tokens, temperature, top_k, seed, eos_id)
+        return generate(self, idx, max_new_tokens, temperature, top_k, seed, eos_id, few_row=few_row,
+                        captured=captured)
 
     def split_qkv_w13(self) -> dict:
         """HF-style unfused view of the weights (q/k/v_proj, gate/up_proj)."""

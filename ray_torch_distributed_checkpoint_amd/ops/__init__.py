@@ -10,6 +10,7 @@ from .attention import (DocLayout, attention_dropout_keep, attention_dropout_mas
 from .decode import KVCache, decode_attention  # noqa: F401
 from .dropout import dropout  # noqa: F401
 from .embedding import embedding  # noqa: F401
+from .gemm import linear_few_rows  # noqa: F401
 from .linear import fused_mlp, linear  # noqa: F401
 from .norm import layer_norm, rms_norm  # noqa: F401
 from .random import PhiloxStream, default_stream, manual_seed  # noqa: F401

@@ -81,6 +81,40 @@ def linear_fwd(x2d: torch.Tensor, w: torch.Tensor, bias=None, act=ACT_NONE, resi
     return y
 
 
+FEW_ROWS_MAX = 16
+
+
+def linear_few_rows(x2d: torch.Tensor, w: torch.Tensor, bias=None, act=ACT_NONE, residual=None, out=None):
+    """y[M,N] = act(x[M,K] @ w[N,K]^T + bias + residual) for 1 <= M <= 16 rows: one launch of the
+    weight-streaming kernel (csrc/kernels/gemm_few_rows.hip), which reads w from global memory
+    straight into the MFMA operands.  act: ACT_NONE or ACT_GELU (no pre-activation side output).
+    On the GPU x, w and residual are bf16 (w: the K-major shadow, as linear_fwd receives it), bias
+    bf16 or fp32, K % 64 == 0, N % 8 == 0, every operand contiguous and 16-byte aligned: anything
+    else raises in the binding before a launch.  Nothing routes here on its own: linear_fwd and
+    the tile launcher do not know this kernel.  On the CPU the same math in torch."""
+    if act not in (ACT_NONE, ACT_GELU):
+        raise ValueError(f"linear_few_rows: act must be ACT_NONE or ACT_GELU, got {act}")
+    if x2d.dim() != 2 or w.dim() != 2:
+        raise ValueError("linear_few_rows: x [M, K] and w [N, K] expected")
+    M, N = x2d.shape[0], w.shape[0]
+    if not 1 <= M <= FEW_ROWS_MAX:
+        raise ValueError(f"linear_few_rows: 1 <= M <= {FEW_ROWS_MAX} rows expected, got {M}")
+    if not x2d.is_cuda:
+        y = torch.nn.functional.linear(x2d, w.to(x2d.dtype), None if bias is None else bias.to(x2d.dtype))
+        if residual is not None:
+            y = y + residual
+        if act == ACT_GELU:
+            y = torch.nn.functional.gelu(y, approximate="tanh")
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x2d.device)
+    gpu_ext().gemm_few_rows(x2d, w, bias, residual, out, act)
+    return out
+
+
 def linear_dgrad(dy: torch.Tensor, w: torch.Tensor, act_bwd=ACT_NONE, aux_in=None, alpha=1.0, alpha_dev=None,
                  colsum_out=None, w_kmajor=None):
     """dx[M,K] = alpha (* alpha_dev[0]) * dy[M,N] @ w[N,K]  (optionally * act'(aux_in)).

@@ -418,6 +418,9 @@ struct FileJob {
   std::vector<Archive> archives;
   int fd = -1;
   int dfd = -1;  // O_DIRECT descriptor of the same file (-1: filesystem refuses O_DIRECT)
+  // cleared by the first writer whose direct write is refused; the descriptor itself stays
+  // open until the file is finalized, since other writers may be inside a pwrite on it
+  std::atomic<bool> direct_ok{true};
   uint64_t total = 0;
   std::atomic<int> pending{0};
   // per big-record ordered piece CRCs, key = (archive << 24) | record
@@ -616,6 +619,7 @@ class Engine {
       for (uint64_t o = 0; o < lens[i]; o += S)
         pieces.push_back({offs[i] + o, std::min(S, lens[i] - o), (char*)dsts[i] + o});
     std::atomic<size_t> next{0};
+    std::atomic<bool> direct_ok{dfd >= 0};  // cleared when a direct read is refused (see write_piece)
     std::string err;
     std::mutex emu, cmu;
     auto work = [&] {
@@ -632,9 +636,10 @@ class Engine {
           const P& pc = pieces[k];
           const uint64_t rl = (pc.len + kPage - 1) / kPage * kPage;  // round up: O_DIRECT length
           bool done = false;
-          if (dfd >= 0 && pc.off % kPage == 0 && rl <= S && pc.off + pc.len <= fsize) {
+          if (direct_ok.load() && pc.off % kPage == 0 && rl <= S && pc.off + pc.len <= fsize) {
             ssize_t r = ::pread(dfd, ring_.ptr(s), rl, (off_t)pc.off);
             if (r >= (ssize_t)pc.len) done = true;  // may stop short of rl at end of file
+            else if (r < 0 && (errno == EINVAL || errno == EFAULT)) direct_ok = false;
           }
           if (!done) pread_all(fd, ring_.ptr(s), pieces[k].len, pieces[k].off);
           hipError_t e;
@@ -879,9 +884,15 @@ class Engine {
   // Page-aligned runs of a piece go through the O_DIRECT descriptor (pinned slot -> device,
   // no page-cache copy); an unaligned remainder (a record's last bytes) through the buffered
   // one.  The two never touch the same 4 KiB page, and fsync on the file covers both.
+  //
+  // Direct I/O can be refused at the first write rather than at open: EINVAL from the
+  // filesystem, or EFAULT where the kernel cannot take references on the ring's pages (a
+  // hipHostMalloc block the driver maps as device memory instead of pinning user pages, as
+  // in a virtual machine).  The file then stays buffered; a source that is truly unreadable
+  // fails the buffered write the same way and is reported from there.
   static void write_piece(FileJob& f, const void* src, uint64_t len, uint64_t off) {
     const char* p = (const char*)src;
-    if (f.dfd >= 0 && off % kPage == 0 && ((uintptr_t)p % kPage) == 0) {
+    if (f.dfd >= 0 && f.direct_ok.load() && off % kPage == 0 && ((uintptr_t)p % kPage) == 0) {
       const uint64_t a = len / kPage * kPage;
       if (a > 0) {
         ssize_t w = ::pwrite(f.dfd, p, a, (off_t)off);
@@ -889,9 +900,8 @@ class Engine {
           p += a;
           off += a;
           len -= a;
-        } else if (w < 0 && errno == EINVAL) {  // filesystem refuses: stay buffered from here
-          ::close(f.dfd);
-          f.dfd = -1;
+        } else if (w < 0 && (errno == EINVAL || errno == EFAULT)) {
+          f.direct_ok = false;
         } else if (w < 0) {
           throw std::runtime_error(std::string("pwrite(O_DIRECT) failed: ") + strerror(errno));
         } else {  // short direct write: finish buffered

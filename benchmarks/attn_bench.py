@@ -20,7 +20,7 @@ the document-mask kernels fed the band as clipped [B, T] arrays (what a window c
 kernels of its own).  Next to the times it prints the share of key tiles the band visits, counted
 from the kernels' loop bounds.  It adds a long shape (T = 8192) to the two of --doc-len.
 
---dropout P times the attention-dropout kernels (flash_fwd_drop / flash_bwd_drop, plain causal
+--dropout P times the attention-dropout kernels (flash_fwd / flash_bwd with drop_thr=, plain causal
 mask) next to the plain kernels the same way: same buffers, alternating rounds, every timed
 window's length recorded, median / minimum per arm, the plain arm's own spread and the ratio.
 """
@@ -91,11 +91,12 @@ def doc_mask_ab(args):
             d = DocLayout.from_lengths([row] * B, T, "cuda")
             arms = {
                 "plain_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale),
-                "doc_fwd": lambda: ext.flash_fwd_doc(q_, o_, lse, d.start, d.end, B, T, H, Hkv, Dh, scale),
+                "doc_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale, doc_start=d.start,
+                                                 doc_end=d.end),
                 "plain_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part,
                                                    qs),
-                "doc_bwd": lambda: ext.flash_bwd_doc(q_, o_, dy, lse, delta, dqkv, d.start, d.end, B, T, H, Hkv, Dh,
-                                                     scale, None, part, qs),
+                "doc_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                                                 doc_start=d.start, doc_end=d.end),
             }
             # repetitions per arm so that every timed window is at least --window-ms long (a few ms
             # measure the clock ramp and the scheduler as much as the kernel)
@@ -172,14 +173,14 @@ def window_ab(args):
             cs, ce = (t_ - W + 1).clamp_min(0).contiguous(), (t_ + W).clamp_max(T).contiguous()
             arms = {
                 "plain_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale),
-                "win_fwd": lambda: ext.flash_fwd_win(q_, o_, lse, W, None, None, B, T, H, Hkv, Dh, scale),
-                "clip_fwd": lambda: ext.flash_fwd_doc(q_, o_, lse, cs, ce, B, T, H, Hkv, Dh, scale),
+                "win_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale, window=W),
+                "clip_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale, doc_start=cs, doc_end=ce),
                 "plain_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part,
                                                    qs),
-                "win_bwd": lambda: ext.flash_bwd_win(q_, o_, dy, lse, delta, dqkv, W, None, None, B, T, H, Hkv, Dh,
-                                                     scale, None, part, qs),
-                "clip_bwd": lambda: ext.flash_bwd_doc(q_, o_, dy, lse, delta, dqkv, cs, ce, B, T, H, Hkv, Dh, scale,
-                                                      None, part, qs),
+                "win_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                                                 window=W),
+                "clip_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                                                  doc_start=cs, doc_end=ce),
             }
             # (as --doc-len: windows of at least --window-ms, calibrated on warm calls; an arm's
             # forward runs right before its backward, which so reads the o / lse of its own mask)
@@ -228,12 +229,12 @@ def dropout_ab(args):
             seed, off = 0x5EED, 12345
             arms = {
                 "plain_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale),
-                "drop_fwd": lambda: ext.flash_fwd_drop(q_, o_, lse, 0, None, None, thr, seed, off, None, B, T, H, Hkv,
-                                                       Dh, scale),
+                "drop_fwd": lambda: ext.flash_fwd(q_, o_, lse, B, T, H, Hkv, Dh, scale, drop_thr=thr, drop_seed=seed,
+                                                  drop_offset=off),
                 "plain_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part,
                                                    qs),
-                "drop_bwd": lambda: ext.flash_bwd_drop(q_, o_, dy, lse, delta, dqkv, 0, None, None, thr, seed, off,
-                                                       None, B, T, H, Hkv, Dh, scale, None, part, qs),
+                "drop_bwd": lambda: ext.flash_bwd(q_, o_, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                                                  drop_thr=thr, drop_seed=seed, drop_offset=off),
             }
             # (as --doc-len: windows of at least --window-ms, calibrated on warm calls; an arm's
             # forward runs right before its backward, which so reads the o / lse of its own mask)

@@ -71,8 +71,9 @@ int rtdc_dropout(const void* x, void* y, long long n, float p, unsigned long lon
 int rtdc_relu_dropout(const void* h, void* y, const void* dy, void* dx, long long n, float p,
                       unsigned long long seed, unsigned long long offset, int backward, int is_bf16,
                       hipStream_t st);
-int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int Hkv, int Dh, float scale,
-                   hipStream_t st);
+int rtdc_flash_fwd(const void* qkv, void* out, float* lse, int window, const int* doc_start, const int* doc_end,
+                   int thr, unsigned long long seed, unsigned long long offset, const long long* off_dev, int B, int T,
+                   int H, int Hkv, int Dh, float scale, hipStream_t st);
 int rtdc_rope(const void* x, void* y, const float* cosb, const float* sinb, int ntok, int T, int nrot_heads,
               int ntot_heads, int Dh, int inverse, hipStream_t st);
 int rtdc_swiglu_fwd(const void* gu, void* h, long long M, int F, hipStream_t st);
@@ -116,25 +117,9 @@ int rtdc_maxpool(const void* x, void* y, void* arg, const void* dy, void* dx, in
                  int K, int s, int p, int backward, hipStream_t st);
 int rtdc_avgpool(const void* x, void* y, int B, int HW, int C, int backward, hipStream_t st);
 int rtdc_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                   int B, int T, int H, int Hkv, int Dh, float scale, float* cs_ws, float* part, int qs,
-                   hipStream_t st);
-int rtdc_flash_fwd_doc(const void* qkv, void* out, float* lse, const int* doc_start, const int* doc_end, int B, int T,
-                       int H, int Hkv, int Dh, float scale, hipStream_t st);
-int rtdc_flash_bwd_doc(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                       const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv, int Dh, float scale,
-                       float* cs_ws, float* part, int qs, hipStream_t st);
-int rtdc_flash_fwd_win(const void* qkv, void* out, float* lse, int window, const int* doc_start, const int* doc_end,
-                       int B, int T, int H, int Hkv, int Dh, float scale, hipStream_t st);
-int rtdc_flash_bwd_win(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                       int window, const int* doc_start, const int* doc_end, int B, int T, int H, int Hkv, int Dh,
-                       float scale, float* cs_ws, float* part, int qs, hipStream_t st);
-int rtdc_flash_fwd_drop(const void* qkv, void* out, float* lse, int window, const int* doc_start, const int* doc_end,
-                        int thr, unsigned long long seed, unsigned long long offset, const long long* off_dev, int B,
-                        int T, int H, int Hkv, int Dh, float scale, hipStream_t st);
-int rtdc_flash_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                        void* dqkv, int window, const int* doc_start, const int* doc_end, int thr,
-                        unsigned long long seed, unsigned long long offset, const long long* off_dev, int B, int T,
-                        int H, int Hkv, int Dh, float scale, float* cs_ws, float* part, int qs, hipStream_t st);
+                   int window, const int* doc_start, const int* doc_end, int thr, unsigned long long seed,
+                   unsigned long long offset, const long long* off_dev, int B, int T, int H, int Hkv, int Dh,
+                   float scale, float* cs_ws, float* part, int qs, hipStream_t st);
 int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, const int* doc_start, int ntok, int T,
                   int nrot_heads, int ntot_heads, int Dh, int inverse, hipStream_t st);
 int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st);
@@ -733,35 +718,6 @@ static void relu_dropout(Tensor h, c10::optional<Tensor> y, c10::optional<Tensor
 }
 
 // ---------------------------------------------------------------------------------- flash attention
-static void flash_fwd(Tensor qkv, Tensor out, Tensor lse, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh,
-                      double scale) {
-  check_dev(qkv, "qkv");
-  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd: contiguous tensors expected");
-  check_rc(rtdc_flash_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)B, (int)T, (int)H, (int)Hkv,
-                          (int)Dh, (float)scale, cur_stream()),
-           "flash_fwd");
-}
-// cs_ws (optional fp32 [B*T/16][W], W = (H + 2 Hkv) Dh): per 16-row group column sums of dqkv
-static void flash_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, int64_t B, int64_t T,
-                      int64_t H, int64_t Hkv, int64_t Dh, double scale, c10::optional<Tensor> cs_ws,
-                      c10::optional<Tensor> part, int64_t qs) {
-  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd: contiguous tensors expected");
-  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd: qs must divide the GQA group size");
-  if (qs > 1)
-    TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
-                    part->numel() >= qs * B * T * Hkv * 2 * Dh,
-                "flash_bwd: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
-  if (cs_ws.has_value())
-    TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
-                    cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
-                "flash_bwd: cs_ws fp32 [B*T/16][W]");
-  check_rc(rtdc_flash_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
-                          delta.data_ptr<float>(), dqkv.data_ptr(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh,
-                          (float)scale, cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
-                          qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
-           "flash_bwd");
-}
-
 // document layout of packed sequences: start / end int32 [B, T] on the qkv's device
 static void check_docs(const Tensor& qkv, const Tensor& start, const Tensor& end, int64_t B, int64_t T,
                        const char* what) {
@@ -771,131 +727,79 @@ static void check_docs(const Tensor& qkv, const Tensor& start, const Tensor& end
                   end.sizes() == start.sizes(),
               what, ": doc start / end must be contiguous int32 [B, T] on the qkv's device");
 }
-static void flash_fwd_doc(Tensor qkv, Tensor out, Tensor lse, Tensor doc_start, Tensor doc_end, int64_t B, int64_t T,
-                          int64_t H, int64_t Hkv, int64_t Dh, double scale) {
+// The mask and dropout of a flash_fwd / flash_bwd call; None = off, and what is given is checked:
+//   doc_start / doc_end (both or neither): packed sequences, check_docs;
+//   window >= 1: row q attends to its last `window` keys (inside its document under a layout);
+//   drop_thr in 1..255: an element is dropped with probability thr / 256; the mask's counter base is
+//   drop_offset (+ *drop_off_dev, an int64 GPU scalar, for graph replays) of the stream drop_seed.
+struct FlashOpts {
+  c10::optional<Tensor> doc_start, doc_end;
+  c10::optional<int64_t> window, drop_thr;
+  uint64_t drop_seed, drop_offset;
+  c10::optional<Tensor> drop_off_dev;
+
+  int win(int64_t T) const { return window.has_value() ? (int)std::min(*window, T) : 0; }  // 0: none
+  const int* start() const { return doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr; }
+  const int* end() const { return doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr; }
+  int thr() const { return (int)drop_thr.value_or(0); }  // 0: no dropout
+  const long long* off_dev() const {
+    return drop_off_dev.has_value() ? (const long long*)drop_off_dev->data_ptr<int64_t>() : nullptr;
+  }
+};
+// what both passes check: qkv and the tensors in `contig`, then the options
+static void check_flash(const Tensor& qkv, std::initializer_list<Tensor> contig, const FlashOpts& o, int64_t B,
+                        int64_t T, const char* what) {
   check_dev(qkv, "qkv");
-  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd_doc: contiguous tensors expected");
-  check_docs(qkv, doc_start, doc_end, B, T, "flash_fwd_doc");
-  check_rc(rtdc_flash_fwd_doc(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), doc_start.data_ptr<int>(),
-                              doc_end.data_ptr<int>(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
-                              cur_stream()),
-           "flash_fwd_doc");
+  TORCH_CHECK(qkv.is_contiguous(), what, ": contiguous tensors expected");
+  for (const Tensor& t : contig) TORCH_CHECK(t.is_contiguous(), what, ": contiguous tensors expected");
+  TORCH_CHECK(!o.window.has_value() || *o.window >= 1, what, ": window must be >= 1, got ", o.window.value_or(0));
+  TORCH_CHECK(o.doc_start.has_value() == o.doc_end.has_value(), what,
+              ": doc start / end are given together or not at all");
+  if (o.doc_start.has_value()) check_docs(qkv, *o.doc_start, *o.doc_end, B, T, what);
+  TORCH_CHECK(!o.drop_thr.has_value() || (*o.drop_thr >= 1 && *o.drop_thr <= 255), what,
+              ": thr must be in 1..255, got ", o.drop_thr.value_or(0));
+  TORCH_CHECK(!o.drop_off_dev.has_value() || (o.drop_off_dev->scalar_type() == at::kLong && o.drop_off_dev->is_cuda()),
+              what, ": off_dev must be an int64 GPU tensor");
 }
-static void flash_bwd_doc(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, Tensor doc_start,
-                          Tensor doc_end, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh, double scale,
-                          c10::optional<Tensor> cs_ws, c10::optional<Tensor> part, int64_t qs) {
-  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd_doc: contiguous tensors expected");
-  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd_doc: qs must divide the GQA group size");
-  check_docs(qkv, doc_start, doc_end, B, T, "flash_bwd_doc");
+// the backward's workspaces: part (the GQA head split, qs > 1) and cs_ws (optional fp32 [B*T/16][W],
+// W = (H + 2 Hkv) Dh: per 16-row group column sums of dqkv)
+static void check_flash_ws(const c10::optional<Tensor>& cs_ws, const c10::optional<Tensor>& part, int64_t qs, int64_t B,
+                           int64_t T, int64_t H, int64_t Hkv, int64_t Dh) {
+  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd: qs must divide the GQA group size");
   if (qs > 1)
     TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
                     part->numel() >= qs * B * T * Hkv * 2 * Dh,
-                "flash_bwd_doc: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
+                "flash_bwd: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
   if (cs_ws.has_value())
     TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
                     cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
-                "flash_bwd_doc: cs_ws fp32 [B*T/16][W]");
-  check_rc(rtdc_flash_bwd_doc(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
-                              delta.data_ptr<float>(), dqkv.data_ptr(), doc_start.data_ptr<int>(),
-                              doc_end.data_ptr<int>(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
-                              cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
-                              qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
-           "flash_bwd_doc");
+                "flash_bwd: cs_ws fp32 [B*T/16][W]");
 }
-// sliding window (row q attends to its last `window` keys), with or without a document layout:
-// doc_start / doc_end are both given or both None
-static void check_window(const Tensor& qkv, int64_t window, const c10::optional<Tensor>& start,
-                         const c10::optional<Tensor>& end, int64_t B, int64_t T, const char* what) {
-  TORCH_CHECK(window >= 1, what, ": window must be >= 1, got ", window);
-  TORCH_CHECK(start.has_value() == end.has_value(), what, ": doc start / end are given together or not at all");
-  if (start.has_value()) check_docs(qkv, *start, *end, B, T, what);
+static void flash_fwd(Tensor qkv, Tensor out, Tensor lse, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh,
+                      double scale, c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end,
+                      c10::optional<int64_t> window, c10::optional<int64_t> drop_thr, uint64_t drop_seed,
+                      uint64_t drop_offset, c10::optional<Tensor> drop_off_dev) {
+  const FlashOpts o{doc_start, doc_end, window, drop_thr, drop_seed, drop_offset, drop_off_dev};
+  check_flash(qkv, {out}, o, B, T, "flash_fwd");
+  check_rc(rtdc_flash_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), o.win(T), o.start(), o.end(), o.thr(),
+                          drop_seed, drop_offset, o.off_dev(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
+                          cur_stream()),
+           "flash_fwd");
 }
-static void flash_fwd_win(Tensor qkv, Tensor out, Tensor lse, int64_t window, c10::optional<Tensor> doc_start,
-                          c10::optional<Tensor> doc_end, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh,
-                          double scale) {
-  check_dev(qkv, "qkv");
-  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd_win: contiguous tensors expected");
-  check_window(qkv, window, doc_start, doc_end, B, T, "flash_fwd_win");
-  check_rc(rtdc_flash_fwd_win(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)std::min(window, T),
-                              doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
-                              doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H,
-                              (int)Hkv, (int)Dh, (float)scale, cur_stream()),
-           "flash_fwd_win");
-}
-static void flash_bwd_win(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, int64_t window,
-                          c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end, int64_t B, int64_t T,
-                          int64_t H, int64_t Hkv, int64_t Dh, double scale, c10::optional<Tensor> cs_ws,
-                          c10::optional<Tensor> part, int64_t qs) {
-  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd_win: contiguous tensors expected");
-  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd_win: qs must divide the GQA group size");
-  check_window(qkv, window, doc_start, doc_end, B, T, "flash_bwd_win");
-  if (qs > 1)
-    TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
-                    part->numel() >= qs * B * T * Hkv * 2 * Dh,
-                "flash_bwd_win: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
-  if (cs_ws.has_value())
-    TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
-                    cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
-                "flash_bwd_win: cs_ws fp32 [B*T/16][W]");
-  check_rc(rtdc_flash_bwd_win(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
-                              delta.data_ptr<float>(), dqkv.data_ptr(), (int)std::min(window, T),
-                              doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
-                              doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H,
-                              (int)Hkv, (int)Dh, (float)scale, cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
-                              qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
-           "flash_bwd_win");
-}
-// attention dropout: window 0 = none, doc_start / doc_end both given or both None; thr in 1..255 (an
-// element is dropped with probability thr / 256); the mask's counter base is offset (+ *off_dev)
-static void check_drop(const Tensor& qkv, int64_t window, const c10::optional<Tensor>& start,
-                       const c10::optional<Tensor>& end, int64_t thr, const c10::optional<Tensor>& off_dev, int64_t B,
-                       int64_t T, const char* what) {
-  TORCH_CHECK(window >= 0, what, ": window must be >= 0 (0 = none), got ", window);
-  TORCH_CHECK(start.has_value() == end.has_value(), what, ": doc start / end are given together or not at all");
-  if (start.has_value()) check_docs(qkv, *start, *end, B, T, what);
-  TORCH_CHECK(thr >= 1 && thr <= 255, what, ": thr must be in 1..255, got ", thr);
-  TORCH_CHECK(!off_dev.has_value() || (off_dev->scalar_type() == at::kLong && off_dev->is_cuda()), what,
-              ": off_dev must be an int64 GPU tensor");
-}
-static void flash_fwd_drop(Tensor qkv, Tensor out, Tensor lse, int64_t window, c10::optional<Tensor> doc_start,
-                           c10::optional<Tensor> doc_end, int64_t thr, uint64_t seed, uint64_t offset,
-                           c10::optional<Tensor> off_dev, int64_t B, int64_t T, int64_t H, int64_t Hkv, int64_t Dh,
-                           double scale) {
-  check_dev(qkv, "qkv");
-  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(), "flash_fwd_drop: contiguous tensors expected");
-  check_drop(qkv, window, doc_start, doc_end, thr, off_dev, B, T, "flash_fwd_drop");
-  check_rc(rtdc_flash_fwd_drop(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)std::min(window, T),
-                               doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
-                               doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)thr, seed, offset,
-                               off_dev.has_value() ? (const long long*)off_dev->data_ptr<int64_t>() : nullptr, (int)B,
-                               (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale, cur_stream()),
-           "flash_fwd_drop");
-}
-static void flash_bwd_drop(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, int64_t window,
-                           c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end, int64_t thr, uint64_t seed,
-                           uint64_t offset, c10::optional<Tensor> off_dev, int64_t B, int64_t T, int64_t H,
-                           int64_t Hkv, int64_t Dh, double scale, c10::optional<Tensor> cs_ws,
-                           c10::optional<Tensor> part, int64_t qs) {
-  TORCH_CHECK(dout.is_contiguous() && dqkv.is_contiguous(), "flash_bwd_drop: contiguous tensors expected");
-  TORCH_CHECK(qs >= 1 && (H / Hkv) % qs == 0, "flash_bwd_drop: qs must divide the GQA group size");
-  check_drop(qkv, window, doc_start, doc_end, thr, off_dev, B, T, "flash_bwd_drop");
-  if (qs > 1)
-    TORCH_CHECK(part.has_value() && part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() &&
-                    part->numel() >= qs * B * T * Hkv * 2 * Dh,
-                "flash_bwd_drop: part fp32 [qs][B*T][Hkv][2*Dh] workspace");
-  if (cs_ws.has_value())
-    TORCH_CHECK(cs_ws->is_cuda() && cs_ws->scalar_type() == at::kFloat && cs_ws->is_contiguous() &&
-                    cs_ws->numel() >= B * T / 16 * (H + 2 * Hkv) * Dh,
-                "flash_bwd_drop: cs_ws fp32 [B*T/16][W]");
-  check_rc(rtdc_flash_bwd_drop(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
-                               delta.data_ptr<float>(), dqkv.data_ptr(), (int)std::min(window, T),
-                               doc_start.has_value() ? doc_start->data_ptr<int>() : nullptr,
-                               doc_end.has_value() ? doc_end->data_ptr<int>() : nullptr, (int)thr, seed, offset,
-                               off_dev.has_value() ? (const long long*)off_dev->data_ptr<int64_t>() : nullptr, (int)B,
-                               (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
-                               cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
-                               qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
-           "flash_bwd_drop");
+static void flash_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, Tensor dqkv, int64_t B, int64_t T,
+                      int64_t H, int64_t Hkv, int64_t Dh, double scale, c10::optional<Tensor> cs_ws,
+                      c10::optional<Tensor> part, int64_t qs, c10::optional<Tensor> doc_start,
+                      c10::optional<Tensor> doc_end, c10::optional<int64_t> window, c10::optional<int64_t> drop_thr,
+                      uint64_t drop_seed, uint64_t drop_offset, c10::optional<Tensor> drop_off_dev) {
+  const FlashOpts o{doc_start, doc_end, window, drop_thr, drop_seed, drop_offset, drop_off_dev};
+  check_flash(qkv, {dout, dqkv}, o, B, T, "flash_bwd");
+  check_flash_ws(cs_ws, part, qs, B, T, H, Hkv, Dh);
+  check_rc(rtdc_flash_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
+                          delta.data_ptr<float>(), dqkv.data_ptr(), o.win(T), o.start(), o.end(), o.thr(), drop_seed,
+                          drop_offset, o.off_dev(), (int)B, (int)T, (int)H, (int)Hkv, (int)Dh, (float)scale,
+                          cs_ws.has_value() ? cs_ws->data_ptr<float>() : nullptr,
+                          qs > 1 ? part->data_ptr<float>() : nullptr, (int)qs, cur_stream()),
+           "flash_bwd");
 }
 // flags uint8 [B, T] (non-zero: a document starts here; position 0 always does) -> start / end
 static void doc_layout(Tensor flags, Tensor start, Tensor end) {
@@ -1555,30 +1459,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("B"), py::arg("T"), py::arg("accumulate_wpe"), py::arg("accumulate_wte") = false);
   m.def("dropout", &dropout);
   m.def("relu_dropout", &relu_dropout);
-  m.def("flash_fwd", &flash_fwd);
+  // flash_fwd / flash_bwd: the mask and dropout keywords default to off (FlashOpts)
+#define RTDC_FLASH_OPTS                                                                                       \
+  py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none(), py::arg("window") = py::none(),         \
+  py::arg("drop_thr") = py::none(), py::arg("drop_seed") = 0, py::arg("drop_offset") = 0,                     \
+  py::arg("drop_off_dev") = py::none()
+  m.def("flash_fwd", &flash_fwd, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("B"), py::arg("T"),
+        py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), RTDC_FLASH_OPTS);
   m.def("flash_bwd", &flash_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("dqkv"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"),
-        py::arg("cs_ws") = py::none(), py::arg("part") = py::none(), py::arg("qs") = 1);
-  m.def("flash_fwd_doc", &flash_fwd_doc);
-  m.def("flash_bwd_doc", &flash_bwd_doc, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
-        py::arg("delta"), py::arg("dqkv"), py::arg("doc_start"), py::arg("doc_end"), py::arg("B"), py::arg("T"),
-        py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
-        py::arg("part") = py::none(), py::arg("qs") = 1);
-  m.def("flash_fwd_win", &flash_fwd_win, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("window"),
-        py::arg("doc_start"), py::arg("doc_end"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Hkv"),
-        py::arg("Dh"), py::arg("scale"));
-  m.def("flash_bwd_win", &flash_bwd_win, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
-        py::arg("delta"), py::arg("dqkv"), py::arg("window"), py::arg("doc_start"), py::arg("doc_end"), py::arg("B"),
-        py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
-        py::arg("part") = py::none(), py::arg("qs") = 1);
-  m.def("flash_fwd_drop", &flash_fwd_drop, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("window"),
-        py::arg("doc_start"), py::arg("doc_end"), py::arg("thr"), py::arg("seed"), py::arg("offset"),
-        py::arg("off_dev"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"));
-  m.def("flash_bwd_drop", &flash_bwd_drop, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
-        py::arg("delta"), py::arg("dqkv"), py::arg("window"), py::arg("doc_start"), py::arg("doc_end"),
-        py::arg("thr"), py::arg("seed"), py::arg("offset"), py::arg("off_dev"), py::arg("B"), py::arg("T"),
-        py::arg("H"), py::arg("Hkv"), py::arg("Dh"), py::arg("scale"), py::arg("cs_ws") = py::none(),
-        py::arg("part") = py::none(), py::arg("qs") = 1);
+        py::arg("cs_ws") = py::none(), py::arg("part") = py::none(), py::arg("qs") = 1, RTDC_FLASH_OPTS);
+#undef RTDC_FLASH_OPTS
   m.def("doc_layout", &doc_layout);
   m.def("synth_doc_flags", &synth_doc_flags);
   m.def("rope", &rope);

@@ -196,30 +196,27 @@ class DocLayout:
         return (k[None, None, :] >= self.start[:, :, None].long()) & (k[None, None, :] <= k[None, :, None])
 
 
+def _flash_opts(docs, window, drop) -> dict:
+    """The mask and dropout keywords of the native flash_fwd / flash_bwd; what is None is off there."""
+    thr, seed, offset, base = drop if drop is not None else (None, 0, 0, None)
+    return dict(doc_start=docs.start if docs is not None else None, doc_end=docs.end if docs is not None else None,
+                window=window, drop_thr=thr, drop_seed=seed, drop_offset=offset, drop_off_dev=base)
+
+
 class _FlashAttention(torch.autograd.Function):
     """Fused causal flash attention (csrc/kernels/attn_flash.hip): no T x T matrix in HBM."""
 
     @staticmethod
     def forward(ctx, qkv, B, T, H, Hkv, Dh, docs=None, window=None, drop=None):
-        """window (int, 1 <= window < T, or None): the sliding-window kernels, with or without docs.
-        drop (None, or (thr, seed, offset, device_base)): the dropout kernels, under any mask; the
-        backward regenerates the mask from the same stream position."""
+        """docs (DocLayout or None): the document-masked kernels.  window (int, 1 <= window < T, or
+        None): the sliding-window kernels, with or without docs.  drop (None, or (thr, seed, offset,
+        device_base)): the dropout kernels, under any mask; the backward regenerates the mask from the
+        same stream position."""
         qkv = qkv.contiguous()
         out = torch.empty((B, T, H * Dh), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B * H, T), dtype=torch.float32, device=qkv.device)
         scale = 1.0 / math.sqrt(Dh)
-        if drop is not None:
-            thr, seed, offset, base = drop
-            gpu_ext().flash_fwd_drop(qkv, out, lse, window or 0, docs.start if docs is not None else None,
-                                     docs.end if docs is not None else None, thr, seed, offset, base,
-                                     B, T, H, Hkv, Dh, scale)
-        elif window is not None:
-            gpu_ext().flash_fwd_win(qkv, out, lse, window, docs.start if docs is not None else None,
-                                    docs.end if docs is not None else None, B, T, H, Hkv, Dh, scale)
-        elif docs is None:
-            gpu_ext().flash_fwd(qkv, out, lse, B, T, H, Hkv, Dh, scale)
-        else:
-            gpu_ext().flash_fwd_doc(qkv, out, lse, docs.start, docs.end, B, T, H, Hkv, Dh, scale)
+        gpu_ext().flash_fwd(qkv, out, lse, B, T, H, Hkv, Dh, scale, **_flash_opts(docs, window, drop))
         ctx.save_for_backward(qkv, out, lse)
         ctx.dims = (B, T, H, Hkv, Dh, scale)
         ctx.docs = docs  # (int32 layout tensors: no gradient, shared by every layer of the step)
@@ -240,22 +237,8 @@ class _FlashAttention(torch.autograd.Function):
         qs = _dkdv_head_split(B, T, H, Hkv, qkv.device)
         part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device=qkv.device) if qs > 1 else None
         dout = dout.contiguous()
-        docs = ctx.docs
-        if ctx.drop is not None:
-            thr, seed, offset, base = ctx.drop
-            gpu_ext().flash_bwd_drop(qkv, out, dout, lse, delta, dqkv, ctx.window or 0,
-                                     docs.start if docs is not None else None,
-                                     docs.end if docs is not None else None, thr, seed, offset, base,
-                                     B, T, H, Hkv, Dh, scale, cs, part, qs)
-        elif ctx.window is not None:
-            gpu_ext().flash_bwd_win(qkv, out, dout, lse, delta, dqkv, ctx.window,
-                                    docs.start if docs is not None else None,
-                                    docs.end if docs is not None else None, B, T, H, Hkv, Dh, scale, cs, part, qs)
-        elif docs is None:
-            gpu_ext().flash_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs)
-        else:
-            gpu_ext().flash_bwd_doc(qkv, out, dout, lse, delta, dqkv, docs.start, docs.end, B, T, H, Hkv, Dh, scale,
-                                    cs, part, qs)
+        gpu_ext().flash_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs,
+                            **_flash_opts(ctx.docs, ctx.window, ctx.drop))
         if cs is not None:
             G.offer_colsum_partials(dqkv, cs)
         return dqkv, None, None, None, None, None, None, None, None
@@ -399,28 +382,19 @@ def causal_attention(qkv: torch.Tensor, n_head: int, n_kv_head: int | None = Non
     else:
         return causal_attention_ref(qkv, B, T, n_head, Hkv, Dh, docs, window)
     impl = os.environ.get("RTDC_ATTN", "flash")
-    if thr:
-        if impl != "flash" or not flash_supported(T, Dh):
-            raise RuntimeError(
-                f"causal_attention: attention dropout needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
-                f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
-        st = stream or default_stream()
-        seed, offset = st.reserve_counters(ncnt)
-        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs, window, (thr, seed, offset, st.device_base()))
-    if window is not None:
-        if impl != "flash" or not flash_supported(T, Dh):
-            raise RuntimeError(
-                f"causal_attention: a sliding window needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
-                f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
-        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs, window)
-    if docs is not None:
-        if impl != "flash" or not flash_supported(T, Dh):
-            raise RuntimeError(
-                f"causal_attention: document masking needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
-                f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
-        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs)
     if impl == "flash" and flash_supported(T, Dh):
-        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh)
+        drop = None
+        if thr:
+            st = stream or default_stream()
+            seed, offset = st.reserve_counters(ncnt)
+            drop = (thr, seed, offset, st.device_base())
+        return _FlashAttention.apply(qkv, B, T, n_head, Hkv, Dh, docs, window, drop)
+    feature = ("attention dropout" if thr else "a sliding window" if window is not None
+               else "document masking" if docs is not None else None)
+    if feature is not None:  # no composed fallback under a mask or dropout
+        raise RuntimeError(
+            f"causal_attention: {feature} needs the flash kernels (T % 64 == 0, Dh in (64, 128), "
+            f"RTDC_ATTN=flash); got T={T}, Dh={Dh}, RTDC_ATTN={impl}")
     if T % 64:
         # the composed GEMMs take T as a reduction length and as the row pitch of P (gemm_bf16 needs
         # K % 64 == 0): zero rows are appended.  Causality keeps them out of every real row, and their

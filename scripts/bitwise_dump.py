@@ -11,8 +11,10 @@ with RTDC_NORM_BWD_VW4=0 RTDC_COLSUM_WIDE=0.  `norm` also runs ops/norm.py, so a
 norm bindings differ it is run from that build's own checkout, with this file dropped in.
 
 `attn` runs every instantiation of the flash kernels at small shapes (all three rows-per-wave knobs
-at 1 and at 2, head splits, plain and document-masked, every output), then three large default
-cases (profiles/attn_merge_bitwise.md).
+at 1 and at 2, head splits, every output; plain, document-masked, sliding window and dropout, the
+last two with and without a layout), then three large default cases (profiles/attn_merge_bitwise.md).
+Against a commit whose attention bindings differ (profiles/attn_one_entry_bitwise.md) it is run from
+that commit's own checkout, with this file dropped in and the two calls of _attn_variants rewritten.
 
 The `optim` family compares two COMMITS, not two builds: it covers the Python side of the fused
 optimizers' step as well, so drop this file into a checkout of the other commit, build the
@@ -34,11 +36,19 @@ def _attn_variants(out):
     entry points called as ops/attention.py's backward calls them (column-sum workspace requested,
     head split from RTDC_FA_QS as _dkdv_head_split takes it), with every output kept - y, lse, dqkv,
     delta and the colsum workspace.  T = 192 falls back to one 16-row group per wave at any knob,
-    T = 384 is an odd number of 128-row blocks; (2, 2, 2) at Dh = 128 is the dK/dV opt-in.  Plain, and
-    one ragged document layout: boundaries inside a tile (37, T - 5, 100) and, from T = 192 on, a
-    document that spans several tiles."""
+    T = 384 is an odd number of 128-row blocks; (2, 2, 2) at Dh = 128 is the dK/dV opt-in.  The ragged
+    document layout: boundaries inside a tile (37, T - 5, 100) and, from T = 192 on, a document that
+    spans several tiles.  Modes (the name's suffix): plain; doc (the layout); win (W = 100; T = 64
+    clamps it) and win_doc (inside the layout); drop (thr = 26, seed 1234, offset 77) and drop_doc_win
+    (under the layout and W = 48)."""
     from ray_torch_distributed_checkpoint_amd.ops import DocLayout
     from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+
+    def modes(docs):
+        lay = dict(doc_start=docs.start, doc_end=docs.end)
+        drop = dict(drop_thr=26, drop_seed=1234, drop_offset=77)
+        return {"plain": {}, "doc": lay, "win": dict(window=100), "win_doc": dict(lay, window=100),
+                "drop": drop, "drop_doc_win": dict(lay, window=48, **drop)}
 
     ext, B = gpu_ext(), 2
     saved = {k: os.environ.get(k) for k in ("RTDC_FA_FWD", "RTDC_FA_DQ", "RTDC_FA_DKDV")}
@@ -55,21 +65,16 @@ def _attn_variants(out):
                 for qs in (1, 2, 4):
                     if (H // Hkv) % qs:
                         continue
-                    for d in (None, docs):
+                    for mode, opts in modes(docs).items():
                         y = torch.zeros((B, T, H * Dh), dtype=torch.bfloat16, device="cuda")
                         lse = torch.zeros((B * H, T), dtype=torch.float32, device="cuda")
                         delta, dqkv = torch.zeros_like(lse), torch.zeros_like(qkv)
                         cs = torch.zeros((B * T // 16, W), dtype=torch.float32, device="cuda")
                         part = torch.zeros(qs * B * T * Hkv * 2 * Dh, dtype=torch.float32, device="cuda") if qs > 1 else None
-                        if d is None:
-                            ext.flash_fwd(qkv, y, lse, B, T, H, Hkv, Dh, scale)
-                            ext.flash_bwd(qkv, y, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs)
-                        else:
-                            ext.flash_fwd_doc(qkv, y, lse, d.start, d.end, B, T, H, Hkv, Dh, scale)
-                            ext.flash_bwd_doc(qkv, y, dy, lse, delta, dqkv, d.start, d.end, B, T, H, Hkv, Dh, scale,
-                                              cs, part, qs)
+                        ext.flash_fwd(qkv, y, lse, B, T, H, Hkv, Dh, scale, **opts)
+                        ext.flash_bwd(qkv, y, dy, lse, delta, dqkv, B, T, H, Hkv, Dh, scale, cs, part, qs, **opts)
                         torch.cuda.synchronize()
-                        name = f"T{T}.H{H}kv{Hkv}d{Dh}.knobs{knob}.qs{qs}.{'plain' if d is None else 'doc'}"
+                        name = f"T{T}.H{H}kv{Hkv}d{Dh}.knobs{knob}.qs{qs}.{mode}"
                         out[name] = {"y": y.cpu(), "lse": lse.cpu(), "dqkv": dqkv.cpu(), "delta": delta.cpu(),
                                      "colsum": cs.cpu()}
     for k, v in saved.items():  # the large cases below run at the caller's knobs

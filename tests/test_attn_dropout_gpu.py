@@ -159,7 +159,7 @@ def _guarded(n0, rest, dtype):
 
 @pytest.mark.parametrize("mode", ["plain", "A+W48"])
 def test_launchers_guarded(monkeypatch, mode):
-    """flash_fwd_drop / flash_bwd_drop called directly, both row variants, qs 1 and 2: lse and delta
+    """flash_fwd / flash_bwd called directly with drop_thr=, both row variants, qs 1 and 2: lse and delta
     judged as well; every output is a slice of a NaN-filled buffer - inside everything is written,
     outside nothing is"""
     from ray_torch_distributed_checkpoint_amd.ops import attention_dropout_keep
@@ -178,9 +178,10 @@ def test_launchers_guarded(monkeypatch, mode):
                     "delta": _guarded(B * H, (T,), F32), "dqkv": _guarded(B, (T, Wd), U.BF16)}
             out, lse, delta, dqkv = (bufs[n][1] for n in ("out", "lse", "delta", "dqkv"))
             part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=F32, device=DEV) if qs > 1 else None
-            _ext().flash_fwd_drop(x["qkv"], out, lse, W or 0, st, en, thr, SEED, off, None, B, T, H, Hkv, Dh, scale)
-            _ext().flash_bwd_drop(x["qkv"], out, x["dout"], lse, delta, dqkv, W or 0, st, en, thr, SEED, off, None,
-                                  B, T, H, Hkv, Dh, scale, None, part, qs)
+            opts = dict(doc_start=st, doc_end=en, window=W, drop_thr=thr, drop_seed=SEED, drop_offset=off)
+            _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, scale, **opts)
+            _ext().flash_bwd(x["qkv"], out, x["dout"], lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                             **opts)
             torch.cuda.synchronize()
             for name, (big, inner) in bufs.items():
                 assert torch.isfinite(inner.float()).all(), f"{name}: an element no block wrote (or a non-finite value)"
@@ -199,13 +200,13 @@ def test_launcher_argument_checks():
     lse = torch.empty(B * H, T, dtype=F32, device=DEV)
     for thr in (0, 256):
         with pytest.raises(RuntimeError, match="thr"):
-            _ext().flash_fwd_drop(x["qkv"], out, lse, 0, None, None, thr, 1, 0, None, B, T, H, Hkv, Dh, 0.125)
+            _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, 0.125, drop_thr=thr, drop_seed=1)
     with pytest.raises(RuntimeError, match="off_dev"):
-        _ext().flash_fwd_drop(x["qkv"], out, lse, 0, None, None, 26, 1, 0, torch.zeros(1, dtype=torch.int64),
-                              B, T, H, Hkv, Dh, 0.125)
+        _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, 0.125, drop_thr=26, drop_seed=1,
+                         drop_off_dev=torch.zeros(1, dtype=torch.int64))
     with pytest.raises(RuntimeError, match="off_dev"):
-        _ext().flash_fwd_drop(x["qkv"], out, lse, 0, None, None, 26, 1, 0, torch.zeros(1, dtype=torch.int32, device=DEV),
-                              B, T, H, Hkv, Dh, 0.125)
+        _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, 0.125, drop_thr=26, drop_seed=1,
+                         drop_off_dev=torch.zeros(1, dtype=torch.int32, device=DEV))
 
 
 # ---------------------------------------------------------------- 3. bitwise
@@ -252,9 +253,9 @@ def test_counter_base_split_between_host_and_device(monkeypatch):
         out = torch.empty(B, T, C, dtype=U.BF16, device=DEV)
         lse, delta = torch.empty(B * H, T, dtype=F32, device=DEV), torch.empty(B * H, T, dtype=F32, device=DEV)
         dqkv = torch.empty(B, T, Wd, dtype=U.BF16, device=DEV)
-        _ext().flash_fwd_drop(x["qkv"], out, lse, 0, None, None, thr, SEED, host, base, B, T, H, Hkv, Dh, scale)
-        _ext().flash_bwd_drop(x["qkv"], out, x["dout"], lse, delta, dqkv, 0, None, None, thr, SEED, host, base,
-                              B, T, H, Hkv, Dh, scale, None, None, 1)
+        opts = dict(drop_thr=thr, drop_seed=SEED, drop_offset=host, drop_off_dev=base)
+        _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, scale, **opts)
+        _ext().flash_bwd(x["qkv"], out, x["dout"], lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, None, 1, **opts)
         torch.cuda.synchronize()
         res.append((out, lse, delta, dqkv))
     for r in res[1:]:

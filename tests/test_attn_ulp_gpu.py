@@ -122,9 +122,9 @@ def _check_guards(bufs):
 @pytest.mark.parametrize("doc", [False, True], ids=["plain", "doc"])
 @pytest.mark.parametrize("c", U.ATTN_DIRECT, ids=U.attn_case_id)
 def test_launchers_guarded(monkeypatch, c, doc):
-    """flash_fwd(_doc) / flash_bwd(_doc) called directly, both row variants, qs 1 and 2: lse and
-    delta judged as well; every output is a slice of a NaN-filled buffer - inside everything is
-    written, outside nothing is"""
+    """flash_fwd / flash_bwd called directly (plain, and with doc_start= / doc_end=), both row
+    variants, qs 1 and 2: lse and delta judged as well; every output is a slice of a NaN-filled
+    buffer - inside everything is written, outside nothing is"""
     B, T, H, Hkv, Dh, _ = c
     W, C, scale = (H + 2 * Hkv) * Dh, H * Dh, 1.0 / math.sqrt(Dh)
     x, docs, ref, twin = _case(c, "A" if doc else None)
@@ -137,9 +137,9 @@ def test_launchers_guarded(monkeypatch, c, doc):
             out, lse, delta, dqkv = (bufs[n][1] for n in ("out", "lse", "delta", "dqkv"))
             part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=F32, device=DEV) if qs > 1 else None
             if doc:
-                _ext().flash_fwd_doc(x["qkv"], out, lse, docs.start, docs.end, B, T, H, Hkv, Dh, scale)
-                _ext().flash_bwd_doc(x["qkv"], out, x["dout"], lse, delta, dqkv, docs.start, docs.end, B, T, H, Hkv,
-                                     Dh, scale, None, part, qs)
+                _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, scale, doc_start=docs.start, doc_end=docs.end)
+                _ext().flash_bwd(x["qkv"], out, x["dout"], lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                                 doc_start=docs.start, doc_end=docs.end)
             else:
                 _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, scale)
                 _ext().flash_bwd(x["qkv"], out, x["dout"], lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs)

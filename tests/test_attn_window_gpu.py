@@ -123,7 +123,7 @@ def _guarded(n0, rest, dtype):
 
 @pytest.mark.parametrize("layout", LAYOUTS, ids=["plain", "A"])
 def test_launchers_guarded(monkeypatch, layout):
-    """flash_fwd_win / flash_bwd_win called directly, both row variants, qs 1 and 2: lse and delta
+    """flash_fwd / flash_bwd called directly with window=, both row variants, qs 1 and 2: lse and delta
     judged as well; every output is a slice of a NaN-filled buffer - inside everything is written,
     outside nothing is"""
     c, W = U.ATTN_CASES[7], 100
@@ -139,9 +139,9 @@ def test_launchers_guarded(monkeypatch, layout):
                     "delta": _guarded(B * H, (T,), F32), "dqkv": _guarded(B, (T, Wd), U.BF16)}
             out, lse, delta, dqkv = (bufs[n][1] for n in ("out", "lse", "delta", "dqkv"))
             part = torch.empty(qs * B * T * Hkv * 2 * Dh, dtype=F32, device=DEV) if qs > 1 else None
-            _ext().flash_fwd_win(x["qkv"], out, lse, W, st, en, B, T, H, Hkv, Dh, scale)
-            _ext().flash_bwd_win(x["qkv"], out, x["dout"], lse, delta, dqkv, W, st, en, B, T, H, Hkv, Dh, scale,
-                                 None, part, qs)
+            _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, scale, doc_start=st, doc_end=en, window=W)
+            _ext().flash_bwd(x["qkv"], out, x["dout"], lse, delta, dqkv, B, T, H, Hkv, Dh, scale, None, part, qs,
+                             doc_start=st, doc_end=en, window=W)
             torch.cuda.synchronize()
             for name, (big, inner) in bufs.items():
                 assert torch.isfinite(inner.float()).all(), f"{name}: an element no block wrote (or a non-finite value)"
@@ -160,9 +160,9 @@ def test_launcher_argument_checks():
     out = torch.empty(B, T, H * Dh, dtype=U.BF16, device=DEV)
     lse = torch.empty(B * H, T, dtype=F32, device=DEV)
     with pytest.raises(RuntimeError, match="window"):
-        _ext().flash_fwd_win(x["qkv"], out, lse, 0, None, None, B, T, H, Hkv, Dh, 0.125)
+        _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, 0.125, window=0)
     with pytest.raises(RuntimeError, match="together"):
-        _ext().flash_fwd_win(x["qkv"], out, lse, 17, docs.start, None, B, T, H, Hkv, Dh, 0.125)
+        _ext().flash_fwd(x["qkv"], out, lse, B, T, H, Hkv, Dh, 0.125, doc_start=docs.start, window=17)
 
 
 @pytest.mark.parametrize("layout", LAYOUTS, ids=["plain", "A"])

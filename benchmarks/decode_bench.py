@@ -19,7 +19,12 @@ at M = 1, 8, 16: microseconds (median, and the min .. max spread over the rounds
 time and its share of the copy rate (both arms allocate their output per call); a shape where the few-row median is not below the tile
 median by more than the larger of the two spreads is marked lost;
 (b) per decode step and generate() tokens/s for gpt2-small and llama3-1b at B = 1 and 8, four arms:
-eager / captured x tile / few-row (eager-tile is the path of the tables above).
+eager / captured x tile / few-row (eager-tile is the path of the tables above);
+(c) the FP8 tables of profiles/decode_fast_fp8.md: in (a)'s loop `linear_few_rows_fp8` on the per-row
+e4m3 image of the same weight alternates with the bf16 few-row kernel and with a second arm of that
+same bf16 kernel (its ratio to the first is the spread a ratio has to beat); weight bytes are
+N K + 4 N (codes and scales) against 2 N K; in (b)'s loop two more arms, eager / captured with
+weights="fp8".
 Prints one JSON line per measurement and a markdown table at the end (--out: also to a file).
 """
 from __future__ import annotations
@@ -208,19 +213,24 @@ def linear_shapes():
 
 
 def linear_rows(args, rate):
+    from ray_torch_distributed_checkpoint_amd import ops
     from ray_torch_distributed_checkpoint_amd.ops import gemm as G
 
     rows = []
     for model, layer, N, K in linear_shapes():
         w = (torch.randn(N, K, device=DEV) * K ** -0.5).bfloat16()
+        q, qs = ops.quantize_fp8_rows(w)
         for M in (1, 8, 16):
             Mp = -(-M // 8) * 8
             xp = torch.zeros(Mp, K, dtype=torch.bfloat16, device=DEV)
             xp[:M] = torch.randn(M, K, device=DEV).bfloat16()
             x = xp[:M]
             # both arms allocate their output per call, as the decode step does
-            r = ab({"few": lambda: G.linear_few_rows(x, w), "tile": lambda: G.linear_fwd(xp, w)},
+            r = ab({"few": lambda: G.linear_few_rows(x, w), "tile": lambda: G.linear_fwd(xp, w),
+                    "fp8": lambda: ops.linear_few_rows_fp8(x, q, qs), "few2": lambda: G.linear_few_rows(x, w)},
                    args.rounds, args.window_ms)
+            (pm, pmin, preps, pmax), f2 = r["fp8"], r["few2"][0]
+            fp8_bytes = N * K + 4 * N
             (fm, fmin, _, fmax), (tm, tmin, _, tmax) = r["few"], r["tile"]
             spread = max(fmax - fmin, tmax - tmin)
             row = {"bench": "few_rows_linear", "model": model, "layer": layer, "N": N, "K": K, "M": M,
@@ -228,16 +238,23 @@ def linear_rows(args, rate):
                    "few_us": [fm * 1e6, fmin * 1e6, fmax * 1e6], "tile_us": [tm * 1e6, tmin * 1e6, tmax * 1e6],
                    "weight_bytes": 2 * N * K, "few_GBps": 2 * N * K / fm * 1e-9, "tile_GBps": 2 * N * K / tm * 1e-9,
                    "few_share_of_copy_rate": 2 * N * K / fm / rate, "tile_share_of_copy_rate": 2 * N * K / tm / rate,
-                   "lost": not fm < tm - spread}
+                   "lost": not fm < tm - spread,
+                   "fp8_plan": list(gpu_ext().few_rows_fp8_plan(N, K)), "fp8_us": [pm * 1e6, pmin * 1e6, pmax * 1e6],
+                   "fp8_weight_bytes": fp8_bytes, "fp8_GBps": fp8_bytes / pm * 1e-9,
+                   "fp8_share_of_copy_rate": fp8_bytes / pm / rate, "few_over_fp8": fm / pm, "few_over_few2": fm / f2,
+                   "fp8_window_ms": [pm * preps * 1e3, fm * r["few"][2] * 1e3],
+                   "fp8_lost": not pm < fm - max(fmax - fmin, pmax - pmin)}
             print(json.dumps(row), flush=True)
             rows.append(row)
-        del w
+        del w, q, qs
         torch.cuda.empty_cache()
     return rows
 
 
-ARMS = (("eager tile", False, False), ("eager few-row", True, False), ("captured tile", False, True),
-        ("captured few-row", True, True))
+# arm, few_row, captured, weights
+ARMS = (("eager tile", False, False, "bf16"), ("eager few-row", True, False, "bf16"),
+        ("captured tile", False, True, "bf16"), ("captured few-row", True, True, "bf16"),
+        ("eager few-row fp8", True, False, "fp8"), ("captured few-row fp8", True, True, "fp8"))
 
 
 def fast_rows(args):
@@ -257,17 +274,17 @@ def fast_rows(args):
         cache.pos.fill_(P + N // 2)
         cache.length = P + N // 2
         steps, keep = {}, []
-        for arm, few, cap in ARMS:
+        for arm, few, cap, wts in ARMS:
             if cap:
-                sess = CapturedDecode(model, cache, few_row=few)
+                sess = CapturedDecode(model, cache, few_row=few, weights=wts)
                 keep.append(sess)
 
                 def step(sess=sess):
                     sess.step(tok)
                     cache.advance(-1)
             else:
-                def step(few=few):
-                    model.decode_step(tok, cache, few_row=few)
+                def step(few=few, wts=wts):
+                    model.decode_step(tok, cache, few_row=few, weights=wts)
                     cache.advance(-1)
             steps[arm] = step
         r = ab(steps, args.rounds, args.window_ms)
@@ -276,13 +293,13 @@ def fast_rows(args):
         for _ in range(2000):
             keep[0]._check_weights()
         guard_us = (time.perf_counter() - t0) / 2000 * 1e6    # host cost of the per-step weight guard
-        for arm, few, cap in ARMS:
-            model.generate(idx, 8, few_row=few, captured=cap)       # warm-up
+        for arm, few, cap, wts in ARMS:
+            model.generate(idx, 8, few_row=few, captured=cap, weights=wts)       # warm-up
             torch.cuda.synchronize()
             ts = []
             for _ in range(3):
                 t0 = time.perf_counter()
-                model.generate(idx, N, few_row=few, captured=cap)
+                model.generate(idx, N, few_row=few, captured=cap, weights=wts)
                 torch.cuda.synchronize()
                 ts.append(time.perf_counter() - t0)
             med, mn, _, mx = r[arm]
@@ -310,6 +327,20 @@ def fast_table(rate, lrows, frows):
                        f"{'LOST' if r['lost'] else ''} |")
         lost = [r for r in lrows if r["lost"]]
         out += ["", "lost shapes (few-row median not below the tile median by more than the larger spread): "
+                + (", ".join(f"{r['model']} {r['layer']} M={r['M']}" for r in lost) if lost else "none"), ""]
+        out += ["FP8 weights: `linear_few_rows_fp8` against the bf16 few-row kernel on the same x "
+                "(bytes: N K + 4 N against 2 N K)", "",
+                "| model | linear | N | K | M | T, waves, chunks/wave | fp8 us med (min .. max) | bf16 few-row us med (min .. max) | "
+                "fp8 weight GB/s | share of copy rate | bf16 / fp8 | bf16 / bf16 again | windows ms (fp8, bf16) | |",
+                "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+        for r in lrows:
+            f, t, pl, wm = r["fp8_us"], r["few_us"], r["fp8_plan"], r["fp8_window_ms"]
+            out.append(f"| {r['model']} | {r['layer']} | {r['N']} | {r['K']} | {r['M']} | {pl[0]}, {pl[1]}, {pl[2]} | "
+                       f"{f[0]:.1f} ({f[1]:.1f} .. {f[2]:.1f}) | {t[0]:.1f} ({t[1]:.1f} .. {t[2]:.1f}) | {r['fp8_GBps']:.0f} | "
+                       f"{100 * r['fp8_share_of_copy_rate']:.1f} % | {r['few_over_fp8']:.2f} | {r['few_over_few2']:.2f} | "
+                       f"{wm[0]:.0f}, {wm[1]:.0f} | {'LOST' if r['fp8_lost'] else ''} |")
+        lost = [r for r in lrows if r["fp8_lost"]]
+        out += ["", "FP8 lost shapes (fp8 median not below the bf16 few-row median by more than the larger spread): "
                 + (", ".join(f"{r['model']} {r['layer']} M={r['M']}" for r in lost) if lost else "none"), ""]
     if frows:
         out += ["| model | B | arm | decode step us med (min .. max) | generate() tokens/s med (min .. max) | step vs eager tile | "

@@ -131,6 +131,10 @@ int rtdc_decode_attn(const void* qkv_new, void* cache, const int* pos, const flo
 int rtdc_gemm_few_rows(const void* x, const void* w, const void* bias, int bias_type, const void* res, void* y, int M,
                        int N, int K, int act, hipStream_t st);
 void rtdc_few_rows_plan(long long N, long long K, int* waves, int* per);
+int rtdc_gemm_few_rows_fp8(const void* x, const void* q, const void* scale, const void* bias, int bias_type,
+                           const void* res, void* y, int M, int N, int K, int act, hipStream_t st);
+void rtdc_few_rows_fp8_plan(long long N, long long K, int* tiles_per_block, int* waves, int* per);
+int rtdc_quantize_fp8_rows(const void* w, int src_bf16, void* q, void* scale, long long N, long long K, hipStream_t st);
 }
 
 static hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
@@ -934,6 +938,79 @@ static std::vector<int64_t> few_rows_plan(int64_t N, int64_t K) {
   rtdc_few_rows_plan(N, K, &waves, &per);
   return {waves, per};
 }
+// FP8-weight few-row linear (gemm_few_rows_fp8.hip): out[M, N] = act((x[M, K] . q[N, K]^T) * scale[n] + bias +
+// residual), 1 <= M <= 16, K % 128 == 0, N % 8 == 0, q e4m3, scale fp32 [N], every operand contiguous and 16-byte
+// aligned; act 0 (none) or 2 (tanh GELU).  Anything else is refused here, before a launch.
+static void gemm_few_rows_fp8(Tensor x, Tensor q, Tensor scale, c10::optional<Tensor> bias,
+                              c10::optional<Tensor> residual, Tensor out, int64_t act) {
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && out.dim() == 2,
+              "gemm_few_rows_fp8: x [M, K], q [N, K], out [M, N] expected");
+  const int64_t M = x.size(0), K = x.size(1), N = q.size(0);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
+              "gemm_few_rows_fp8: bf16 x and out expected");
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn, "gemm_few_rows_fp8: q must be float8_e4m3fn");
+  check_dev(x, "gemm_few_rows_fp8: x");
+  check_dev(q, "gemm_few_rows_fp8: q");
+  check_dev(scale, "gemm_few_rows_fp8: scale");
+  check_dev(out, "gemm_few_rows_fp8: out");
+  TORCH_CHECK(M >= 1 && M <= 16, "gemm_few_rows_fp8: 1 <= M <= 16 rows expected, got ", M);
+  TORCH_CHECK(q.size(1) == K && out.size(0) == M && out.size(1) == N, "gemm_few_rows_fp8: shapes do not match");
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= 8 && N % 8 == 0 && N <= INT32_MAX && K <= INT32_MAX,
+              "gemm_few_rows_fp8: K % 128 == 0 and N % 8 == 0 expected, got N=", N, " K=", K);
+  TORCH_CHECK(x.is_contiguous() && q.is_contiguous() && out.is_contiguous(),
+              "gemm_few_rows_fp8: contiguous x, q and out expected");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.dim() == 1 && scale.size(0) == N && scale.is_contiguous(),
+              "gemm_few_rows_fp8: scale must be a contiguous fp32 [N] tensor");
+  TORCH_CHECK(q.device() == x.device() && scale.device() == x.device() && out.device() == x.device(),
+              "gemm_few_rows_fp8: tensors on different devices");
+  TORCH_CHECK(act == 0 || act == 2, "gemm_few_rows_fp8: act must be 0 (none) or 2 (gelu_tanh)");
+  int bias_type = 0;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat,
+                "gemm_few_rows_fp8: bias must be bf16 or fp32");
+    check_dev(*bias, "gemm_few_rows_fp8: bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(),
+                "gemm_few_rows_fp8: bias must be a contiguous [N] tensor on x's device");
+    bias_type = bias->scalar_type() == at::kBFloat16 ? 1 : 2;
+  }
+  if (residual.has_value()) {
+    check_dev(*residual, "gemm_few_rows_fp8: residual");
+    TORCH_CHECK(residual->scalar_type() == at::kBFloat16 && residual->is_contiguous() && residual->dim() == 2 &&
+                    residual->size(0) == M && residual->size(1) == N && residual->device() == x.device(),
+                "gemm_few_rows_fp8: residual must be a contiguous bf16 [M, N] tensor on x's device");
+  }
+  check_rc(rtdc_gemm_few_rows_fp8(x.data_ptr(), q.data_ptr(), scale.data_ptr(), ptr_or_null(bias), bias_type,
+                                  ptr_or_null(residual), out.data_ptr(), (int)M, (int)N, (int)K, (int)act,
+                                  cur_stream()),
+           "gemm_few_rows_fp8");
+}
+// (column tiles of 16 per block, waves per block, chunks of 128 k per wave) that gemm_few_rows_fp8 launches for (N, K)
+static std::vector<int64_t> few_rows_fp8_plan(int64_t N, int64_t K) {
+  int tiles = 0, waves = 0, per = 0;
+  rtdc_few_rows_fp8_plan(N, K, &tiles, &waves, &per);
+  return {tiles, waves, per};
+}
+// Per-row e4m3 quantisation (gemm_few_rows_fp8.hip): scale[n] = max_k |w[n, k]| / 448 (1 for a zero row),
+// q[n, k] = rne_e4m3(w[n, k] / scale[n]); w [N, K] contiguous fp32 or bf16, K % 16 == 0.
+static void quantize_fp8_rows(Tensor w, Tensor q, Tensor scale) {
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous() && (w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16),
+              "quantize_fp8_rows: w must be a contiguous fp32 or bf16 [N, K] tensor");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N >= 1 && K >= 16 && K % 16 == 0 && N <= INT32_MAX && K <= INT32_MAX,
+              "quantize_fp8_rows: K % 16 == 0 expected, got N=", N, " K=", K);
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 2 && q.size(0) == N && q.size(1) == K &&
+                  q.is_contiguous(),
+              "quantize_fp8_rows: q must be a contiguous float8_e4m3fn [N, K] tensor");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.dim() == 1 && scale.size(0) == N && scale.is_contiguous(),
+              "quantize_fp8_rows: scale must be a contiguous fp32 [N] tensor");
+  check_dev(w, "quantize_fp8_rows: w");
+  check_dev(q, "quantize_fp8_rows: q");
+  TORCH_CHECK(scale.is_cuda() && q.device() == w.device() && scale.device() == w.device(),
+              "quantize_fp8_rows: tensors on different devices");
+  check_rc(rtdc_quantize_fp8_rows(w.data_ptr(), w.scalar_type() == at::kBFloat16 ? 1 : 0, q.data_ptr(),
+                                  scale.data_ptr(), N, K, cur_stream()),
+           "quantize_fp8_rows");
+}
 static void swiglu_fwd(Tensor gu, Tensor h) {
   const int64_t F = h.size(-1), M = h.numel() / F;
   check_rc(rtdc_swiglu_fwd(gu.data_ptr(), h.data_ptr(), M, (int)F, cur_stream()), "swiglu_fwd");
@@ -1480,6 +1557,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_few_rows", &gemm_few_rows, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("residual"),
         py::arg("out"), py::arg("act"));
   m.def("few_rows_plan", &few_rows_plan);
+  m.def("gemm_few_rows_fp8", &gemm_few_rows_fp8, py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias"),
+        py::arg("residual"), py::arg("out"), py::arg("act"));
+  m.def("few_rows_fp8_plan", &few_rows_fp8_plan);
+  m.def("quantize_fp8_rows", &quantize_fp8_rows, py::arg("w"), py::arg("q"), py::arg("scale"));
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("im2col", &im2col);

@@ -72,9 +72,13 @@ def parse_args(argv=None):
     ap.add_argument("--few-row", action="store_true", help="decode linears on the few-row kernel (batch <= 16)")
     ap.add_argument("--captured", action="store_true", help="replay the decode step from a hipGraph (GPU only)")
     ap.add_argument("--fast", action="store_true", help="--few-row and --captured")
+    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: the few-row linears read per-row e4m3 weight images (implies --few-row)")
     args = ap.parse_args(argv)
     if args.fast:
         args.few_row = args.captured = True
+    if args.weights == "fp8":
+        args.few_row = True
     return args
 
 
@@ -92,11 +96,12 @@ def main(argv=None):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = model.generate(idx, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k, seed=args.seed,
-                         eos_id=args.eos_id, few_row=args.few_row, captured=args.captured)
+                         eos_id=args.eos_id, few_row=args.few_row, captured=args.captured, weights=args.weights)
     tokens = out.tolist()  # (the device is read here, once)
     dt = time.perf_counter() - t0
     row = {"model": args.model, "device": device.type, "batch": idx.shape[0], "prompt_len": idx.shape[1],
-           "new_tokens": args.max_new_tokens, "few_row": args.few_row, "captured": args.captured, "tokens": tokens,
+           "new_tokens": args.max_new_tokens, "few_row": args.few_row, "captured": args.captured, "weights": args.weights,
+           "tokens": tokens,
            "tokens_per_s": round(idx.shape[0] * args.max_new_tokens / dt, 2) if dt > 0 else None}
     print(json.dumps(row))
     return row

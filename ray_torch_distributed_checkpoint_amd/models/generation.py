@@ -12,6 +12,10 @@ Two switches, both off by default (a call without them runs the code above uncha
 `few_row=True` sends every linear of a decode step, and the last-position LM head of the prefill,
 to ops.linear_few_rows on the B real rows (B <= 16; no row padding); `CapturedDecode` /
 `generate(captured=True)` records one decode step as a hipGraph and replays it per token.
+`weights="fp8"` (with few_row=True; default "bf16") sends those same linears to
+ops.linear_few_rows_fp8 on ops.fp8_rows_of(weight), the per-row e4m3 image of each weight: half the
+bytes per step.  Weight-only: activations, the KV cache, norms, biases and embeddings are untouched,
+and the prompt's own forward in `prefill` stays the bf16 training forward.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..ops import gemm as G
 from ..ops._ext import gpu_ext
+from ..ops.fp8 import fp8_stamp
 from ..ops.llama_ops import rope_tables, swiglu_mlp
 
 
@@ -39,8 +44,21 @@ def _check_few_row(B: int) -> None:
         raise ValueError(f"few_row=True takes at most {G.FEW_ROWS_MAX} batch rows, got {B}")
 
 
-def _few(x, w, bias=None, act=G.ACT_NONE, residual=None):
-    """one linear of a few-row decode step: the weight's bf16 shadow through ops.linear_few_rows"""
+def _check_weights(weights: str, few_row: bool) -> bool:
+    """-> weights == "fp8", which needs few_row=True"""
+    if weights not in ("bf16", "fp8"):
+        raise ValueError(f'weights must be "bf16" or "fp8", got {weights!r}')
+    if weights == "fp8" and not few_row:
+        raise ValueError('weights="fp8" requires few_row=True (only the few-row kernel reads FP8 weights)')
+    return weights == "fp8"
+
+
+def _few(x, w, bias=None, act=G.ACT_NONE, residual=None, fp8=False):
+    """one linear of a few-row decode step: the weight's bf16 shadow through ops.linear_few_rows, or
+    its e4m3 image through ops.linear_few_rows_fp8"""
+    if fp8:
+        q, scale = ops.fp8_rows_of(w)
+        return ops.linear_few_rows_fp8(x, q, scale, bias=bias, act=act, residual=residual)
     return G.linear_few_rows(x, ops.shadow_of(w), bias=bias, act=act, residual=residual)
 
 
@@ -70,10 +88,11 @@ def _attend(qkv, B, cache, li, n_head, n_kv_head, rope, window, y):
 
 # ---------------------------------------------------------------------------------- GPT-2
 @torch.no_grad()
-def gpt2_prefill(model, idx: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+def gpt2_prefill(model, idx: torch.Tensor, cache, few_row: bool = False, weights: str = "bf16") -> torch.Tensor:
     c = model.cfg
     _check_prefill(idx, cache, c.n_positions, "n_positions")
     B, P = idx.shape
+    fp8 = _check_weights(weights, few_row)
     if few_row:
         _check_few_row(B)
     x = ops.embedding(_pad_prompt(idx), model.wte, model.wpe)
@@ -87,16 +106,17 @@ def gpt2_prefill(model, idx: torch.Tensor, cache, few_row: bool = False) -> torc
         h, x = blk.ln_2(x, passthrough=True)
         x = blk.mlp(h, residual=x)
     _finish_prefill(cache, P)
-    if few_row and idx.is_cuda:
-        return _few(model.ln_f(x[:, P - 1].contiguous()), model.wte)[:, : c.vocab_size]
+    if few_row and (idx.is_cuda or fp8):
+        return _few(model.ln_f(x[:, P - 1].contiguous()), model.wte, fp8=fp8)[:, : c.vocab_size]
     last = _rows8(x[:, P - 1].contiguous())
     return ops.linear(model.ln_f(last), model.wte)[:B, : c.vocab_size]
 
 
 @torch.no_grad()
-def gpt2_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+def gpt2_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False, weights: str = "bf16") -> torch.Tensor:
     c = model.cfg
     B = tok.shape[0]
+    fp8 = _check_weights(weights, few_row)
     if few_row:
         _check_few_row(B)
     if cache.length >= min(cache.Tmax, c.n_positions):
@@ -107,8 +127,8 @@ def gpt2_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False) -> 
         x = (ops.shadow_of(model.wte)[tok].float() + ops.shadow_of(model.wpe)[pos].float()).to(torch.bfloat16)
     else:
         x = model.wte[tok] + model.wpe[pos]
-    if few_row and tok.is_cuda:
-        return _gpt2_decode_few(model, x, cache)
+    if few_row and (tok.is_cuda or fp8):
+        return _gpt2_decode_few(model, x, cache, fp8)
     x = _rows8(x)
     y = x.new_zeros((x.shape[0], c.n_embd)) if x.shape[0] != B else None
     win = model.sliding_window or None
@@ -123,30 +143,32 @@ def gpt2_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False) -> 
     return ops.linear(model.ln_f(x), model.wte)[:B, : c.vocab_size]
 
 
-def _gpt2_decode_few(model, x, cache):
-    """the decode step on the B real rows: five few-row linears per block and the LM head"""
+def _gpt2_decode_few(model, x, cache, fp8=False):
+    """the decode step on the B real rows: five few-row linears per block and the LM head (fp8: the
+    tied wte is quantised for the LM head only; the embedding gather keeps the bf16 shadow)"""
     c = model.cfg
     win = model.sliding_window or None
     for li, blk in enumerate(model.h):
         h, x = blk.ln_1(x, passthrough=True)
-        qkv = _few(h, blk.attn.c_attn.weight, blk.attn.c_attn.bias)
+        qkv = _few(h, blk.attn.c_attn.weight, blk.attn.c_attn.bias, fp8=fp8)
         a = ops.decode_attention(qkv, cache, li, c.n_head, c.n_head, rope=None, window=win)
-        x = _few(a, blk.attn.c_proj.weight, blk.attn.c_proj.bias, residual=x)
+        x = _few(a, blk.attn.c_proj.weight, blk.attn.c_proj.bias, residual=x, fp8=fp8)
         h, x = blk.ln_2(x, passthrough=True)
-        g = _few(h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=G.ACT_GELU)
-        x = _few(g, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, residual=x)
+        g = _few(h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=G.ACT_GELU, fp8=fp8)
+        x = _few(g, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, residual=x, fp8=fp8)
     cache.advance()
-    return _few(model.ln_f(x), model.wte)[:, : c.vocab_size]
+    return _few(model.ln_f(x), model.wte, fp8=fp8)[:, : c.vocab_size]
 
 
 # ---------------------------------------------------------------------------------- Llama
 @torch.no_grad()
-def llama_prefill(model, idx: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+def llama_prefill(model, idx: torch.Tensor, cache, few_row: bool = False, weights: str = "bf16") -> torch.Tensor:
     from ..ops.llama_ops import apply_rope
 
     c = model.cfg
     _check_prefill(idx, cache, c.max_seq_len, "max_seq_len")
     B, P = idx.shape
+    fp8 = _check_weights(weights, few_row)
     if few_row:
         _check_few_row(B)
     x = ops.embedding(_pad_prompt(idx), model.tok_embeddings)
@@ -160,23 +182,24 @@ def llama_prefill(model, idx: torch.Tensor, cache, few_row: bool = False) -> tor
         h, x = blk.ffn_norm(x, passthrough=True)
         x = blk.feed_forward(h, residual=x)
     _finish_prefill(cache, P)
-    if few_row and idx.is_cuda:
-        return _few(model.norm(x[:, P - 1].contiguous()), model.output)[:, : c.vocab_size]
+    if few_row and (idx.is_cuda or fp8):
+        return _few(model.norm(x[:, P - 1].contiguous()), model.output, fp8=fp8)[:, : c.vocab_size]
     last = _rows8(x[:, P - 1].contiguous())
     return ops.linear(model.norm(last), model.output)[:B, : c.vocab_size]
 
 
 @torch.no_grad()
-def llama_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+def llama_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False, weights: str = "bf16") -> torch.Tensor:
     c = model.cfg
     B = tok.shape[0]
+    fp8 = _check_weights(weights, few_row)
     if few_row:
         _check_few_row(B)
     if cache.length >= min(cache.Tmax, c.max_seq_len):
         raise ValueError(f"decode_step: position {cache.length} is beyond the cache (Tmax={cache.Tmax}) or "
                          f"max_seq_len={c.max_seq_len}")
-    if few_row and tok.is_cuda:
-        return _llama_decode_few(model, tok, cache)
+    if few_row and (tok.is_cuda or fp8):
+        return _llama_decode_few(model, tok, cache, fp8)
     pad = -B % 8 if tok.is_cuda else 0
     x = ops.embedding(F.pad(tok, (0, pad))[:, None], model.tok_embeddings)[:, 0]
     y = x.new_zeros((x.shape[0], c.n_heads * c.head_dim)) if pad else None
@@ -193,7 +216,7 @@ def llama_decode_step(model, tok: torch.Tensor, cache, few_row: bool = False) ->
     return ops.linear(model.norm(x), model.output)[:B, : c.vocab_size]
 
 
-def _llama_decode_few(model, tok, cache):
+def _llama_decode_few(model, tok, cache, fp8=False):
     """the decode step on the B real rows: wqkv, wo, w13 (then the swiglu_fwd launch), w2, output"""
     c = model.cfg
     x = ops.embedding(tok[:, None], model.tok_embeddings)[:, 0]
@@ -201,16 +224,20 @@ def _llama_decode_few(model, tok, cache):
     win = model.sliding_window or None
     for li, blk in enumerate(model.layers):
         h, x = blk.attention_norm(x, passthrough=True)
-        qkv = _few(h, blk.attention.wqkv)
+        qkv = _few(h, blk.attention.wqkv, fp8=fp8)
         a = ops.decode_attention(qkv, cache, li, c.n_heads, c.n_kv_heads, rope=rope, window=win)
-        x = _few(a, blk.attention.wo, residual=x)
+        x = _few(a, blk.attention.wo, residual=x, fp8=fp8)
         h, x = blk.ffn_norm(x, passthrough=True)
-        gu = _few(h, blk.feed_forward.w13)
-        hh = torch.empty((gu.shape[0], gu.shape[1] // 2), dtype=torch.bfloat16, device=gu.device)
-        gpu_ext().swiglu_fwd(gu, hh)
-        x = _few(hh, blk.feed_forward.w2, residual=x)
+        gu = _few(h, blk.feed_forward.w13, fp8=fp8)
+        if gu.is_cuda:
+            hh = torch.empty((gu.shape[0], gu.shape[1] // 2), dtype=torch.bfloat16, device=gu.device)
+            gpu_ext().swiglu_fwd(gu, hh)
+        else:
+            g, u = gu.chunk(2, dim=-1)
+            hh = F.silu(g) * u
+        x = _few(hh, blk.feed_forward.w2, residual=x, fp8=fp8)
     cache.advance()
-    return _few(model.norm(x), model.output)[:, : c.vocab_size]
+    return _few(model.norm(x), model.output, fp8=fp8)[:, : c.vocab_size]
 
 
 # ---------------------------------------------------------------------------------- captured decode
@@ -234,7 +261,8 @@ class CapturedDecode:
     cache cannot be warmed up and is refused.
 
     What the graph bakes in, and how `step` guards it:
-    * `model.sliding_window` and `few_row` are recorded; `step` raises if either differs.
+    * `model.sliding_window`, `few_row` and `weights` are recorded; `step` raises if one differs
+      (`step(tok, weights=...)` is there to be checked against the captured value).
     * the addresses of every parameter and of every bf16 weight shadow.  ops.shadow_of refreshes a
       stale shadow in place (same storage), but only when it is called, and a replay calls nothing:
       `step` compares every parameter's version counter and, where one moved (load_state_dict, a
@@ -244,16 +272,20 @@ class CapturedDecode:
       new session has to be built.  The fused optimizers write master and shadow in the same kernel
       pass without a version bump: the guard does not see such an update and does not need to,
       since both storages are the ones the graph reads and nothing is left to refresh.
+      With weights="fp8" the same holds for the (q, scale) images of ops.fp8_rows_of: the guard
+      keeps their addresses, re-quantises in place before the replay where a version counter (or the
+      fused optimizers' generation) moved, and raises where an image's storage was replaced.
       The guard is one pass over the parameters on the host per step (three attribute reads each;
       its measured cost is in profiles/decode_fast.md) and runs while the previous replay executes.
     """
 
-    def __init__(self, model, cache, few_row: bool = False):
+    def __init__(self, model, cache, few_row: bool = False, weights: str = "bf16"):
         if not (torch.cuda.is_available() and cache.device.type == "cuda"):
             raise RuntimeError("CapturedDecode: hipGraph capture needs the model and the cache on a GPU")
         from ..ops.streams import side_stream
 
-        self.model, self.cache, self.few_row = model, cache, bool(few_row)
+        self.model, self.cache, self.few_row, self.weights = model, cache, bool(few_row), weights
+        _check_weights(weights, few_row)
         self.window = model.sliding_window or None
         self.limit = min(cache.Tmax, getattr(model.cfg, "n_positions", None) or model.cfg.max_seq_len)
         if few_row:
@@ -270,19 +302,23 @@ class CapturedDecode:
             with torch.no_grad():
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    model.decode_step(self.tok, cache, few_row=self.few_row)
+                    model.decode_step(self.tok, cache, few_row=self.few_row, weights=weights)
                 cur.wait_stream(side)
                 cache.pos.copy_(pos0)      # the capture below sees the position it was built at
                 cache.length = length0
                 torch.cuda.synchronize(dev)
                 self.graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph, stream=side):
-                    self.logits = model.decode_step(self.tok, cache, few_row=self.few_row)
+                    self.logits = model.decode_step(self.tok, cache, few_row=self.few_row, weights=weights)
         finally:
             cache.pos.copy_(pos0)
             cache.length = length0
         self._guard = [(p, p._version, p.data_ptr(), getattr(p, "_rtdc_shadow", None)) for p in model.parameters()]
         self._shadow_ptrs = [None if s is None else s.data_ptr() for _, _, _, s in self._guard]
+        # the FP8 images the graph reads: (parameter, image, its addresses, the stamp it was made for)
+        self._fp8_guard = [[p, p._rtdc_fp8, (p._rtdc_fp8[0].data_ptr(), p._rtdc_fp8[1].data_ptr()), fp8_stamp(p)]
+                           for p in model.parameters() if getattr(p, "_rtdc_fp8", None) is not None
+                           ] if weights == "fp8" else []
         self.replays = 0
 
     def _check_weights(self) -> None:
@@ -296,9 +332,21 @@ class CapturedDecode:
                 raise RuntimeError("CapturedDecode: a weight shadow's storage was replaced after capture; "
                                    "build a new session")
             self._guard[i] = (p, p._version, ptr, s)
+        for g in self._fp8_guard:
+            p, img, ptrs, stamp = g
+            if fp8_stamp(p) == stamp and getattr(p, "_rtdc_fp8", None) is img:
+                continue
+            new = ops.fp8_rows_of(p)   # (a moved stamp: re-quantised here, in place)
+            if new[0] is not img[0] or new[1] is not img[1] or (img[0].data_ptr(), img[1].data_ptr()) != ptrs:
+                raise RuntimeError("CapturedDecode: an FP8 weight image's storage was replaced after capture; "
+                                   "build a new session")
+            g[3] = fp8_stamp(p)
 
-    def step(self, tok: torch.Tensor) -> torch.Tensor:
+    def step(self, tok: torch.Tensor, weights: str | None = None) -> torch.Tensor:
         c = self.cache
+        if weights is not None and weights != self.weights:
+            raise RuntimeError(f"CapturedDecode: the step was captured with weights={self.weights!r}, not "
+                               f"{weights!r}; build a new session")
         if (self.model.sliding_window or None) != self.window:
             raise RuntimeError(f"CapturedDecode: model.sliding_window changed after capture "
                                f"({self.window} -> {self.model.sliding_window}); build a new session")
@@ -342,14 +390,18 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int | None, gen) -> 
 
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
-             seed: int = 0, eos_id: int | None = None, few_row: bool = False, captured: bool = False) -> torch.Tensor:
+             seed: int = 0, eos_id: int | None = None, few_row: bool = False, captured: bool = False,
+             weights: str = "bf16") -> torch.Tensor:
     """idx [B, P] -> [B, P + max_new_tokens].  One prefill, then one decode step per token; the
     loop has no host read of device data: a row that emitted eos_id keeps emitting it through a
     device-side mask and there is no early exit.
     few_row: the decode linears and the prefill's LM head on ops.linear_few_rows (B <= 16; on the
     CPU the reference math is the same either way).  captured (GPU only): the decode step is
     replayed from a CapturedDecode built on this call's cache; sampling and the eos mask stay
-    eager, on the same generator, so the tokens are those of the eager loop."""
+    eager, on the same generator, so the tokens are those of the eager loop.
+    weights: "bf16" | "fp8" (needs few_row=True): the few-row linears read the weights' per-row e4m3
+    images (ops.fp8_rows_of) through ops.linear_few_rows_fp8, on the CPU through its torch twin."""
+    _check_weights(weights, few_row)
     limit = getattr(model.cfg, "n_positions", None) or model.cfg.max_seq_len
     B, P = idx.shape
     N = int(max_new_tokens)
@@ -371,8 +423,8 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
     out = torch.empty((B, P + N), dtype=idx.dtype, device=idx.device)
     out[:, :P] = idx
     done = torch.zeros(B, dtype=torch.bool, device=idx.device)
-    logits = model.prefill(idx, cache, few_row=few_row)
-    sess = CapturedDecode(model, cache, few_row=few_row) if captured and N > 1 else None
+    logits = model.prefill(idx, cache, few_row=few_row, weights=weights)
+    sess = CapturedDecode(model, cache, few_row=few_row, weights=weights) if captured and N > 1 else None
     for i in range(N):
         tok = sample(logits, float(temperature), top_k, gen).to(idx.dtype)
         if eos_id is not None:
@@ -380,5 +432,6 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
             done = done | (tok == eos_id)
         out[:, P + i] = tok
         if i + 1 < N:
-            logits = sess.step(tok) if sess is not None else model.decode_step(tok, cache, few_row=few_row)
+            logits = (sess.step(tok) if sess is not None
+                      else model.decode_step(tok, cache, few_row=few_row, weights=weights))
     return out

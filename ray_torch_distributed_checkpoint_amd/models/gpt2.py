@@ -159,32 +159,34 @@ class GPT2(nn.Module):
         logits = ops.linear(x, self.wte)
         return logits[..., : self.cfg.vocab_size]
 
-    def prefill(self, idx: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+    def prefill(self, idx: torch.Tensor, cache, few_row: bool = False, weights: str = "bf16") -> torch.Tensor:
         """The forward over the prompt idx [B, P] (dropout off) that fills the ops.KVCache and
         returns the logits [B, vocab_size] of the last position only (models/generation.py).
-        few_row: the last-position LM head on ops.linear_few_rows (B <= 16)."""
+        few_row: the last-position LM head on ops.linear_few_rows (B <= 16); weights="fp8" (with
+        few_row): on ops.linear_few_rows_fp8 and the weight's e4m3 image."""
         from .generation import gpt2_prefill
 
-        return gpt2_prefill(self, idx, cache, few_row=few_row)
+        return gpt2_prefill(self, idx, cache, few_row=few_row, weights=weights)
 
-    def decode_step(self, tok: torch.Tensor, cache, few_row: bool = False) -> torch.Tensor:
+    def decode_step(self, tok: torch.Tensor, cache, few_row: bool = False, weights: str = "bf16") -> torch.Tensor:
         """One token per row, tok [B], at the cache's positions -> logits [B, vocab_size].
-        few_row: every linear of the step on ops.linear_few_rows, on the B <= 16 real rows."""
+        few_row: every linear of the step on ops.linear_few_rows, on the B <= 16 real rows;
+        weights="fp8" (with few_row): on ops.linear_few_rows_fp8 and the weights' e4m3 images."""
         from .generation import gpt2_decode_step
 
-        return gpt2_decode_step(self, tok, cache, few_row=few_row)
+        return gpt2_decode_step(self, tok, cache, few_row=few_row, weights=weights)
 
     def generate(self, idx, max_new_tokens, temperature=0.0, top_k=None, seed=0, eos_id=None, few_row=False,
-                 captured=False):
+                 captured=False, weights="bf16"):
         """idx [B, P] -> [B, P + max_new_tokens] with a KV cache: greedy at temperature 0, else
         temperature / top-k sampling from a generator seeded with `seed`.  Honours
         sliding_window; packed documents (docs) are not supported.  few_row / captured (both off by
         default): the few-row linear kernel and the hipGraph-replayed decode step of
-        models/generation.py."""
+        models/generation.py; weights="fp8" (needs few_row): FP8 weight images in those linears."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature, top_k, seed, eos_id, few_row=few_row,
-                        captured=captured)
+                        captured=captured, weights=weights)
 
     def flops_per_token(self, T: int, causal: bool = True) -> float:
         """Training FLOPs per token (6N + attention), N without the embedding table."""

@@ -25,6 +25,12 @@ e4m3 image of the same weight alternates with the bf16 few-row kernel and with a
 same bf16 kernel (its ratio to the first is the spread a ratio has to beat); weight bytes are
 N K + 4 N (codes and scales) against 2 N K; in (b)'s loop two more arms, eager / captured with
 weights="fp8".
+--kv-cache fp8 runs the tables of profiles/decode_fp8_kv.md alone (--kv-out FILE): per SHAPES row the
+FP8-cache decode kernel (csrc/kernels/attn_decode_fp8.hip) alternating with the bf16 kernel on the same
+values (the FP8 cache is the quantised bf16 one), bytes = the cached keys' K and V bytes plus, for FP8,
+their scales, over the copy rate; then per decode step and generate() tokens/s of gpt2-small and
+llama3-1b at B = 1 and 8 with the bf16 and the FP8 cache, eager, and together with captured few-row
+weights="fp8".  An FP8 median not below the bf16 median by more than the larger spread is marked LOST.
 Prints one JSON line per measurement and a markdown table at the end (--out: also to a file).
 """
 from __future__ import annotations
@@ -354,6 +360,125 @@ def fast_table(rate, lrows, frows):
     return "\n".join(out)
 
 
+def kv_kernel_rows(args, rate):
+    """the bf16 and the FP8-cache decode kernels alternating on the same cached values"""
+    from ray_torch_distributed_checkpoint_amd.ops import KVCache
+
+    ext, rows = gpu_ext(), []
+    for name, B, L, H, Hkv, Dh, rope in SHAPES:
+        if args.only and name != args.only:
+            continue
+        Tmax = L + 64
+        qkv_new = (torch.randn(B, (H + 2 * Hkv) * Dh, device=DEV) * 0.5).bfloat16()
+        cache = (torch.randn(B, Tmax, 2 * Hkv * Dh, device=DEV) * 0.5).bfloat16()
+        kvc = KVCache(1, B, Tmax, Hkv, Dh, DEV, kv_dtype="fp8")
+        filler = torch.zeros((B, Tmax, (H + 2 * Hkv) * Dh), dtype=torch.bfloat16, device=DEV)
+        filler[:, :, H * Dh:] = cache
+        kvc.fill(0, filler, H, Tmax)
+        del filler
+        cq, cs = kvc.layers[0], kvc.scales[0]
+        pos = torch.full((B,), L, dtype=torch.int32, device=DEV)
+        ns = decode_splits(B, Hkv, Tmax, torch.device(DEV))
+        part = torch.empty(B * H * ns * (Dh + 2), dtype=torch.float32, device=DEV)
+        out = torch.empty((B, H * Dh), dtype=torch.bfloat16, device=DEV)
+        cos, sin = rope_tables(Tmax, Dh, 500000.0, DEV) if rope else (None, None)
+        scale = Dh ** -0.5
+        r = ab({"bf16": lambda: ext.decode_attn(qkv_new, cache, pos, cos, sin, out, part, H, Hkv, 0, ns, scale),
+                "fp8": lambda: ext.decode_attn_fp8kv(qkv_new, cq, cs, pos, cos, sin, out, part, H, Hkv, 0, ns, scale)},
+               args.rounds, args.window_ms)
+        (bm, bmin, _, bmax), (fm, fmin, _, fmax) = r["bf16"], r["fp8"]
+        bb, fb = B * L * 2 * Hkv * Dh * 2, B * L * 2 * Hkv * (Dh + 4)
+        row = {"bench": "decode_attn_fp8kv", "shape": name, "B": B, "cached": L, "H": H, "Hkv": Hkv, "Dh": Dh, "nsplit": ns,
+               "bf16_us": [bm * 1e6, bmin * 1e6, bmax * 1e6], "fp8_us": [fm * 1e6, fmin * 1e6, fmax * 1e6],
+               "bf16_bytes": bb, "fp8_bytes": fb, "bf16_share": bb / bm / rate, "fp8_share": fb / fm / rate,
+               "bf16_over_fp8": bm / fm, "lost": not fm < bm - max(bmax - bmin, fmax - fmin)}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del cache, kvc, cq, cs
+        torch.cuda.empty_cache()
+    return rows
+
+
+# arm, kv_cache, few_row, captured, weights
+KV_ARMS = (("bf16 cache", "bf16", False, False, "bf16"), ("fp8 cache", "fp8", False, False, "bf16"),
+           ("bf16 cache, captured few-row fp8 weights", "bf16", True, True, "fp8"),
+           ("fp8 cache, captured few-row fp8 weights", "fp8", True, True, "fp8"))
+
+
+def kv_step_rows(args):
+    from ray_torch_distributed_checkpoint_amd.generate import build_model
+    from ray_torch_distributed_checkpoint_amd.models.generation import CapturedDecode, new_cache
+
+    rows = []
+    for name, B, P, N in (("gpt2-small", 1, 64, 192), ("gpt2-small", 8, 64, 192), ("llama3-1b", 1, 64, 192),
+                          ("llama3-1b", 8, 64, 192)):
+        torch.manual_seed(0)
+        model = build_model(name, DEV).eval()
+        idx = torch.randint(0, model.cfg.vocab_size, (B, P), device=DEV)
+        tok = idx[:, 0].contiguous()
+        steps, keep = {}, []
+        for arm, kvd, few, cap, wts in KV_ARMS:
+            cache = new_cache(model, B, P + N, DEV, kv_cache=kvd)
+            model.prefill(idx, cache, few_row=few, weights=wts)
+            cache.pos.fill_(P + N // 2)
+            cache.length = P + N // 2
+            sess = CapturedDecode(model, cache, few_row=few, weights=wts) if cap else None
+            keep.append((cache, sess))
+
+            def step(cache=cache, sess=sess, few=few, wts=wts):
+                if sess is not None:
+                    sess.step(tok)
+                else:
+                    model.decode_step(tok, cache, few_row=few, weights=wts)
+                cache.advance(-1)
+            steps[arm] = step
+        r = ab(steps, args.rounds, args.window_ms)
+        for arm, kvd, few, cap, wts in KV_ARMS:
+            kw = dict(few_row=few, captured=cap, weights=wts, kv_cache=kvd)
+            model.generate(idx, 8, **kw)       # warm-up
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                model.generate(idx, N, **kw)
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            med, mn, _, mx = r[arm]
+            row = {"bench": "decode_fp8kv_step", "model": name, "B": B, "prompt": P, "new_tokens": N, "arm": arm,
+                   "step_us": [med * 1e6, mn * 1e6, mx * 1e6], "tokens_per_s": B * N / median(ts),
+                   "tokens_per_s_range": [B * N / max(ts), B * N / min(ts)]}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+        del model, keep, steps
+        torch.cuda.empty_cache()
+    return rows
+
+
+def kv_table(rate, krows, srows):
+    out = [f"device-to-device copy rate (1 GiB, read + write bytes): {rate * 1e-12:.2f} TB/s", ""]
+    if krows:
+        out += ["| shape | B | cached keys | nsplit | bf16 kernel us med (min .. max) | fp8 kernel us med (min .. max) | "
+                "bf16 share of copy rate | fp8 share of copy rate | bf16 / fp8 | |", "|---|---|---|---|---|---|---|---|---|---|"]
+        for r in krows:
+            b, f = r["bf16_us"], r["fp8_us"]
+            out.append(f"| {r['shape']} H{r['H']} Hkv{r['Hkv']} Dh{r['Dh']} | {r['B']} | {r['cached']} | {r['nsplit']} | "
+                       f"{b[0]:.1f} ({b[1]:.1f} .. {b[2]:.1f}) | {f[0]:.1f} ({f[1]:.1f} .. {f[2]:.1f}) | "
+                       f"{100 * r['bf16_share']:.1f} % | {100 * r['fp8_share']:.1f} % | {r['bf16_over_fp8']:.2f} | "
+                       f"{'LOST' if r['lost'] else ''} |")
+        out.append("")
+    if srows:
+        out += ["| model | B | arm | decode step us med (min .. max) | generate() tokens/s med (min .. max) | "
+                "step vs the bf16 cache | |", "|---|---|---|---|---|---|---|"]
+        by = {(r["model"], r["B"], r["arm"]): r["step_us"] for r in srows}
+        for r in srows:
+            s, g = r["step_us"], r["tokens_per_s_range"]
+            base = by[(r["model"], r["B"], r["arm"].replace("fp8 cache", "bf16 cache"))]
+            lost = r["arm"].startswith("fp8") and not s[0] < base[0] - max(s[2] - s[1], base[2] - base[1])
+            out.append(f"| {r['model']} | {r['B']} | {r['arm']} | {s[0]:.0f} ({s[1]:.0f} .. {s[2]:.0f}) | "
+                       f"{r['tokens_per_s']:.0f} ({g[0]:.0f} .. {g[1]:.0f}) | {base[0] / s[0]:.2f} x | {'LOST' if lost else ''} |")
+    return "\n".join(out)
+
+
 def table(rate, krows, grows):
     out = [f"device-to-device copy rate (1 GiB, read + write bytes): {rate * 1e-12:.2f} TB/s", ""]
     if krows:
@@ -385,9 +510,21 @@ def main():
     ap.add_argument("--fast-only", action="store_true", help="only the few-row / captured tables")
     ap.add_argument("--fast-part", default="both", choices=("both", "linear", "step"))
     ap.add_argument("--fast-out", default=None)
+    ap.add_argument("--kv-cache", default=None, choices=("fp8",), help="only the FP8 KV-cache tables")
+    ap.add_argument("--kv-part", default="both", choices=("both", "kernel", "step"))
+    ap.add_argument("--kv-out", default=None)
     args = ap.parse_args()
     rate = copy_rate(args.rounds, args.window_ms)
     print(json.dumps({"bench": "copy_rate", "bytes_per_s": rate}), flush=True)
+    if args.kv_cache:
+        krows = kv_kernel_rows(args, rate) if args.kv_part in ("both", "kernel") else []
+        srows = kv_step_rows(args) if args.kv_part in ("both", "step") else []
+        text = kv_table(rate, krows, srows)
+        print(text)
+        if args.kv_out:
+            with open(args.kv_out, "w") as f:
+                f.write(text + "\n")
+        return
     if not args.fast_only:
         krows = kernel_rows(args, rate)
         grows = [] if args.no_generate else generate_rows(args)

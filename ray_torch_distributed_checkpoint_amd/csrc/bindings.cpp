@@ -135,6 +135,11 @@ int rtdc_gemm_few_rows_fp8(const void* x, const void* q, const void* scale, cons
                            const void* res, void* y, int M, int N, int K, int act, hipStream_t st);
 void rtdc_few_rows_fp8_plan(long long N, long long K, int* tiles_per_block, int* waves, int* per);
 int rtdc_quantize_fp8_rows(const void* w, int src_bf16, void* q, void* scale, long long N, long long K, hipStream_t st);
+int rtdc_decode_attn_fp8kv(const void* qkv_new, void* cache_q, float* cache_scale, const int* pos, const float* cosb,
+                           const float* sinb, void* out, float* part, int B, int Tmax, int H, int Hkv, int Dh,
+                           int window, int nsplit, float scale, hipStream_t st);
+int rtdc_kv_fill_fp8(const void* qkv, void* cache_q, float* cache_scale, int B, int T, int Tmax, int H, int Hkv, int Dh,
+                     int rows, hipStream_t st);
 }
 
 static hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
@@ -893,6 +898,81 @@ static void decode_attn(Tensor qkv_new, Tensor cache, Tensor pos, c10::optional<
                             (int)nsplit, (float)scale, cur_stream()),
            "decode_attn");
 }
+// The FP8 KV cache of attn_decode_fp8.hip: cache_q [B, Tmax, 2 Hkv Dh] float8_e4m3fn in the layout of the
+// bf16 cache, cache_scale [B, Tmax, 2 Hkv] fp32.  Dtypes and shapes are checked here, before any launch.
+static void check_fp8_cache(const Tensor& ref, const Tensor& cq, const Tensor& cs, int64_t B, int64_t Hkv, int64_t Dh,
+                            const char* what) {
+  TORCH_CHECK(cq.dim() == 3 && cs.dim() == 3 && cq.is_cuda() && cs.is_cuda() && cq.device() == ref.device() &&
+                  cs.device() == ref.device(),
+              what, ": cache_q [B, Tmax, 2 Hkv Dh] and cache_scale [B, Tmax, 2 Hkv] on the device of qkv expected");
+  TORCH_CHECK(cq.scalar_type() == at::kFloat8_e4m3fn && cs.scalar_type() == at::kFloat,
+              what, ": float8_e4m3fn cache_q and fp32 cache_scale expected");
+  TORCH_CHECK(cq.is_contiguous() && cs.is_contiguous(), what, ": contiguous cache_q / cache_scale expected");
+  TORCH_CHECK(cq.size(0) == B && cq.size(2) == 2 * Hkv * Dh && cs.size(0) == B && cs.size(1) == cq.size(1) &&
+                  cs.size(2) == 2 * Hkv,
+              what, ": cache_q / cache_scale do not match qkv");
+  TORCH_CHECK(((uintptr_t)cq.data_ptr()) % 16 == 0, what, ": cache_q must be 16-byte aligned");
+}
+static void decode_attn_fp8kv(Tensor qkv_new, Tensor cache_q, Tensor cache_scale, Tensor pos,
+                              c10::optional<Tensor> cosb, c10::optional<Tensor> sinb, Tensor out, Tensor part,
+                              int64_t H, int64_t Hkv, int64_t window, int64_t nsplit, double scale) {
+  TORCH_CHECK(qkv_new.dim() == 2 && pos.dim() == 1 && out.dim() == 2,
+              "decode_attn_fp8kv: qkv_new [B, W], pos [B], out [B, H Dh] expected");
+  const int64_t B = qkv_new.size(0);
+  TORCH_CHECK(H >= 1 && Hkv >= 1 && H % Hkv == 0 && qkv_new.size(1) % (H + 2 * Hkv) == 0,
+              "decode_attn_fp8kv: bad head counts");
+  const int64_t Dh = qkv_new.size(1) / (H + 2 * Hkv);
+  check_dev(qkv_new, "decode_attn_fp8kv: qkv_new");
+  check_dev(out, "decode_attn_fp8kv: out");
+  check_fp8_cache(qkv_new, cache_q, cache_scale, B, Hkv, Dh, "decode_attn_fp8kv");
+  const int64_t Tmax = cache_q.size(1);
+  TORCH_CHECK(part.is_cuda(), "decode_attn_fp8kv: part must be a GPU tensor");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
+              "decode_attn_fp8kv: pos must be contiguous int32 [B] on the device");
+  TORCH_CHECK(qkv_new.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16 &&
+                  part.scalar_type() == at::kFloat,
+              "decode_attn_fp8kv: bf16 qkv_new / out and fp32 part expected");
+  TORCH_CHECK(qkv_new.is_contiguous() && out.is_contiguous() && part.is_contiguous(),
+              "decode_attn_fp8kv: contiguous tensors expected");
+  TORCH_CHECK(out.size(0) == B && out.size(1) == H * Dh, "decode_attn_fp8kv: out does not match qkv_new");
+  TORCH_CHECK(out.device() == qkv_new.device() && part.device() == qkv_new.device() && pos.device() == qkv_new.device(),
+              "decode_attn_fp8kv: tensors on different devices");
+  TORCH_CHECK(nsplit >= 1 && part.numel() >= B * H * nsplit * (Dh + 2), "decode_attn_fp8kv: part workspace too small");
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "decode_attn_fp8kv: window must be >= 0 (0 = off)");
+  TORCH_CHECK(cosb.has_value() == sinb.has_value(), "decode_attn_fp8kv: cos and sin tables go together");
+  const float *cp = nullptr, *sp = nullptr;
+  if (cosb.has_value()) {
+    for (const Tensor* t : {&*cosb, &*sinb})
+      TORCH_CHECK(t->is_cuda() && t->device() == qkv_new.device() && t->scalar_type() == at::kFloat &&
+                      t->is_contiguous() && t->dim() == 2 && t->size(0) >= Tmax && t->size(1) == Dh / 2,
+                  "decode_attn_fp8kv: rope tables must be contiguous fp32 [>= Tmax, Dh / 2] on the device");
+    cp = cosb->data_ptr<float>();
+    sp = sinb->data_ptr<float>();
+  }
+  check_rc(rtdc_decode_attn_fp8kv(qkv_new.data_ptr(), cache_q.data_ptr(), cache_scale.data_ptr<float>(),
+                                  pos.data_ptr<int>(), cp, sp, out.data_ptr(), part.data_ptr<float>(), (int)B,
+                                  (int)Tmax, (int)H, (int)Hkv, (int)Dh, (int)window, (int)nsplit, (float)scale,
+                                  cur_stream()),
+           "decode_attn_fp8kv");
+}
+// The prefill's fill: rows t < rows of the k|v tail of qkv [B, T, (H + 2 Hkv) Dh], quantised per head run.
+static void kv_fill_fp8(Tensor qkv, Tensor cache_q, Tensor cache_scale, int64_t n_head, int64_t rows) {
+  TORCH_CHECK(qkv.dim() == 3 && qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous(),
+              "kv_fill_fp8: qkv must be a contiguous bf16 [B, T, (H + 2 Hkv) Dh] tensor");
+  check_dev(qkv, "kv_fill_fp8: qkv");
+  TORCH_CHECK(cache_scale.dim() == 3 && cache_scale.size(2) >= 2 && cache_scale.size(2) % 2 == 0,
+              "kv_fill_fp8: cache_scale [B, Tmax, 2 Hkv] expected");
+  const int64_t B = qkv.size(0), T = qkv.size(1), Hkv = cache_scale.size(2) / 2;
+  TORCH_CHECK(n_head >= 1 && qkv.size(2) % (n_head + 2 * Hkv) == 0, "kv_fill_fp8: bad head counts");
+  const int64_t Dh = qkv.size(2) / (n_head + 2 * Hkv);
+  check_fp8_cache(qkv, cache_q, cache_scale, B, Hkv, Dh, "kv_fill_fp8");
+  const int64_t Tmax = cache_q.size(1);
+  TORCH_CHECK(rows >= 0 && rows <= T && rows <= Tmax, "kv_fill_fp8: rows must be within the prompt and the cache");
+  TORCH_CHECK(((uintptr_t)qkv.data_ptr()) % 16 == 0, "kv_fill_fp8: qkv must be 16-byte aligned");
+  check_rc(rtdc_kv_fill_fp8(qkv.data_ptr(), cache_q.data_ptr(), cache_scale.data_ptr<float>(), (int)B, (int)T,
+                            (int)Tmax, (int)n_head, (int)Hkv, (int)Dh, (int)rows, cur_stream()),
+           "kv_fill_fp8");
+}
 // Few-row linear (gemm_few_rows.hip): out[M, N] = act(x[M, K] . w[N, K]^T + bias + residual), 1 <= M <= 16,
 // K % 64 == 0, N % 8 == 0, every operand contiguous and 16-byte aligned; act 0 (none) or 2 (tanh GELU).
 // Anything else is refused here, before a launch: there is no other kernel behind this entry.
@@ -1554,6 +1634,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn", &decode_attn, py::arg("qkv_new"), py::arg("cache"), py::arg("pos"), py::arg("cos"),
         py::arg("sin"), py::arg("out"), py::arg("part"), py::arg("H"), py::arg("Hkv"), py::arg("window"),
         py::arg("nsplit"), py::arg("scale"));
+  m.def("decode_attn_fp8kv", &decode_attn_fp8kv, py::arg("qkv_new"), py::arg("cache_q"), py::arg("cache_scale"),
+        py::arg("pos"), py::arg("cos"), py::arg("sin"), py::arg("out"), py::arg("part"), py::arg("H"), py::arg("Hkv"),
+        py::arg("window"), py::arg("nsplit"), py::arg("scale"));
+  m.def("kv_fill_fp8", &kv_fill_fp8, py::arg("qkv"), py::arg("cache_q"), py::arg("cache_scale"), py::arg("n_head"),
+        py::arg("rows"));
   m.def("gemm_few_rows", &gemm_few_rows, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("residual"),
         py::arg("out"), py::arg("act"));
   m.def("few_rows_plan", &few_rows_plan);

@@ -272,6 +272,15 @@ static void launch_decode(int G, dim3 grid, hipStream_t st, const DecodeArgs& a)
 #undef RTDC_DEC_CASE
 }
 
+// The merge launch alone (Dh 64 or 128, checked by the callers): shared with attn_decode_fp8.hip.
+extern "C" int rtdc_decode_merge(const float* part, void* out, int B, int H, int Dh, int nsplit, hipStream_t st) {
+  if (Dh == 64)
+    hipLaunchKernelGGL(decode_merge_kernel<64>, dim3(B * H), dim3(64), 0, st, part, (bf16_t*)out, nsplit);
+  else
+    hipLaunchKernelGGL(decode_merge_kernel<128>, dim3(B * H), dim3(128), 0, st, part, (bf16_t*)out, nsplit);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
 // part: B * H * nsplit * (Dh + 2) floats.  nsplit in 1 .. Tmax / 64; split s covers the keys
 // [s * chunk, (s + 1) * chunk) with chunk = ceil(Tmax / nsplit) rounded up to a multiple of 64.
 extern "C" int rtdc_decode_attn(const void* qkv_new, void* cache, const int* pos, const float* cosb, const float* sinb,
@@ -299,9 +308,5 @@ extern "C" int rtdc_decode_attn(const void* qkv_new, void* cache, const int* pos
   if (Dh == 64) launch_decode<64>(H / Hkv, grid, st, a);
   else launch_decode<128>(H / Hkv, grid, st, a);
   if (hipGetLastError() != hipSuccess) return 2;
-  if (Dh == 64)
-    hipLaunchKernelGGL(decode_merge_kernel<64>, dim3(B * H), dim3(64), 0, st, part, (bf16_t*)out, nsplit);
-  else
-    hipLaunchKernelGGL(decode_merge_kernel<128>, dim3(B * H), dim3(128), 0, st, part, (bf16_t*)out, nsplit);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return rtdc_decode_merge(part, out, B, H, Dh, nsplit, st);
 }

@@ -2,7 +2,7 @@
 
     python -m ray_torch_distributed_checkpoint_amd.generate --model gpt2-tiny --checkpoint DIR \\
         [--prompt-ids 1,2,3 | --prompt-len 16] --max-new-tokens 32 [--temperature --top-k --seed --batch]
-        [--few-row] [--captured] [--fast]
+        [--few-row] [--captured] [--fast] [--weights {bf16,fp8}] [--kv-cache {bf16,fp8}]
 
 Builds the model, loads the "model" part of the DCP checkpoint directory (what
 `workloads.restore(mode="weights")` loads) and runs `model.generate()` (KV cache, split-KV decode
@@ -10,6 +10,7 @@ kernel on the GPU).  There is no tokenizer in the tree: the prompt is a list of 
 `--prompt-len` tokens of each of the first `--batch` rows of the workloads' SyntheticTokens.
 `--few-row` runs the decode linears on the weight-streaming few-row kernel (batch <= 16),
 `--captured` replays the decode step from a hipGraph (GPU only), `--fast` sets both.
+`--kv-cache fp8` keeps the KV cache in e4m3 with per-head scales (half the cache bytes).
 Prints one JSON line: the token ids and the tokens per second.
 """
 from __future__ import annotations
@@ -74,6 +75,8 @@ def parse_args(argv=None):
     ap.add_argument("--fast", action="store_true", help="--few-row and --captured")
     ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: the few-row linears read per-row e4m3 weight images (implies --few-row)")
+    ap.add_argument("--kv-cache", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: an e4m3 KV cache with one fp32 scale per (token, kv-head, k|v)")
     args = ap.parse_args(argv)
     if args.fast:
         args.few_row = args.captured = True
@@ -96,11 +99,13 @@ def main(argv=None):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = model.generate(idx, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k, seed=args.seed,
-                         eos_id=args.eos_id, few_row=args.few_row, captured=args.captured, weights=args.weights)
+                         eos_id=args.eos_id, few_row=args.few_row, captured=args.captured, weights=args.weights,
+                         kv_cache=args.kv_cache)
     tokens = out.tolist()  # (the device is read here, once)
     dt = time.perf_counter() - t0
     row = {"model": args.model, "device": device.type, "batch": idx.shape[0], "prompt_len": idx.shape[1],
            "new_tokens": args.max_new_tokens, "few_row": args.few_row, "captured": args.captured, "weights": args.weights,
+           "kv_cache": args.kv_cache,
            "tokens": tokens,
            "tokens_per_s": round(idx.shape[0] * args.max_new_tokens / dt, 2) if dt > 0 else None}
     print(json.dumps(row))

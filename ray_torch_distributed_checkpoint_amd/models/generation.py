@@ -16,6 +16,10 @@ to ops.linear_few_rows on the B real rows (B <= 16; no row padding); `CapturedDe
 ops.linear_few_rows_fp8 on ops.fp8_rows_of(weight), the per-row e4m3 image of each weight: half the
 bytes per step.  Weight-only: activations, the KV cache, norms, biases and embeddings are untouched,
 and the prompt's own forward in `prefill` stays the bf16 training forward.
+`kv_cache="fp8"` (default "bf16"; `new_cache` and `generate`) keeps the KV cache in e4m3 with one fp32
+scale per (token, kv-head, k|v): half the cache bytes of a step and half the cache memory.  It is
+independent of the other three; `prefill`, `decode_step` and `CapturedDecode` follow the cache they
+are given.  The prompt's own attention still reads its bf16 k|v, not the cache.
 """
 from __future__ import annotations
 
@@ -364,8 +368,11 @@ class CapturedDecode:
 
 
 # ---------------------------------------------------------------------------------- sampling
-def new_cache(model, B: int, length: int, device):
-    """An ops.KVCache for `length` positions of this model (GPU: rounded up to a multiple of 64)."""
+def new_cache(model, B: int, length: int, device, kv_cache: str = "bf16"):
+    """An ops.KVCache for `length` positions of this model (GPU: rounded up to a multiple of 64).
+    kv_cache: "bf16" | "fp8", the cache's kv_dtype."""
+    if kv_cache not in ("bf16", "fp8"):
+        raise ValueError(f'kv_cache must be "bf16" or "fp8", got {kv_cache!r}')
     c = model.cfg
     if hasattr(c, "n_kv_heads"):
         n_layers, Hkv, Dh = c.n_layers, c.n_kv_heads, c.head_dim
@@ -373,7 +380,7 @@ def new_cache(model, B: int, length: int, device):
         n_layers, Hkv, Dh = c.n_layer, c.n_head, c.n_embd // c.n_head
     device = torch.device(device)
     Tmax = -(-length // 64) * 64 if device.type == "cuda" else length
-    return ops.KVCache(n_layers, B, Tmax, Hkv, Dh, device)
+    return ops.KVCache(n_layers, B, Tmax, Hkv, Dh, device, kv_dtype=kv_cache)
 
 
 def sample(logits: torch.Tensor, temperature: float, top_k: int | None, gen) -> torch.Tensor:
@@ -391,7 +398,7 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int | None, gen) -> 
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
              seed: int = 0, eos_id: int | None = None, few_row: bool = False, captured: bool = False,
-             weights: str = "bf16") -> torch.Tensor:
+             weights: str = "bf16", kv_cache: str = "bf16") -> torch.Tensor:
     """idx [B, P] -> [B, P + max_new_tokens].  One prefill, then one decode step per token; the
     loop has no host read of device data: a row that emitted eos_id keeps emitting it through a
     device-side mask and there is no early exit.
@@ -400,8 +407,11 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
     replayed from a CapturedDecode built on this call's cache; sampling and the eos mask stay
     eager, on the same generator, so the tokens are those of the eager loop.
     weights: "bf16" | "fp8" (needs few_row=True): the few-row linears read the weights' per-row e4m3
-    images (ops.fp8_rows_of) through ops.linear_few_rows_fp8, on the CPU through its torch twin."""
+    images (ops.fp8_rows_of) through ops.linear_few_rows_fp8, on the CPU through its torch twin.
+    kv_cache: "bf16" | "fp8": the KV cache's format (new_cache), independent of the other switches."""
     _check_weights(weights, few_row)
+    if kv_cache not in ("bf16", "fp8"):
+        raise ValueError(f'kv_cache must be "bf16" or "fp8", got {kv_cache!r}')
     limit = getattr(model.cfg, "n_positions", None) or model.cfg.max_seq_len
     B, P = idx.shape
     N = int(max_new_tokens)
@@ -419,7 +429,7 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
     if temperature != 0.0:
         gen = torch.Generator(device=idx.device)
         gen.manual_seed(int(seed))
-    cache = new_cache(model, B, P + N, idx.device)
+    cache = new_cache(model, B, P + N, idx.device, kv_cache=kv_cache)
     out = torch.empty((B, P + N), dtype=idx.dtype, device=idx.device)
     out[:, :P] = idx
     done = torch.zeros(B, dtype=torch.bool, device=idx.device)

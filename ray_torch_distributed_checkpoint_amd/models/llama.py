@@ -180,16 +180,17 @@ class Llama(nn.Module):
         return llama_decode_step(self, tok, cache, few_row=few_row, weights=weights)
 
     def generate(self, idx, max_new_tokens, temperature=0.0, top_k=None, seed=0, eos_id=None, few_row=False,
-                 captured=False, weights="bf16"):
+                 captured=False, weights="bf16", kv_cache="bf16"):
         """idx [B, P] -> [B, P + max_new_tokens] with a KV cache: greedy at temperature 0, else
         temperature / top-k sampling from a generator seeded with `seed`.  Honours
         sliding_window; packed documents (docs) are not supported.  few_row / captured (both off by
         default): the few-row linear kernel and the hipGraph-replayed decode step of
-        models/generation.py; weights="fp8" (needs few_row): FP8 weight images in those linears."""
+        models/generation.py; weights="fp8" (needs few_row): FP8 weight images in those linears;
+        kv_cache="fp8": an e4m3 KV cache with per-head scales (ops.KVCache(kv_dtype="fp8"))."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature, top_k, seed, eos_id, few_row=few_row,
-                        captured=captured, weights=weights)
+                        captured=captured, weights=weights, kv_cache=kv_cache)
 
     def split_qkv_w13(self) -> dict:
         """HF-style unfused view of the weights (q/k/v_proj, gate/up_proj)."""

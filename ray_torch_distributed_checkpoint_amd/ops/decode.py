@@ -9,6 +9,16 @@ split-KV kernel (csrc/kernels/attn_decode.hip) rotates the new q and k heads (Ro
 given), stores the new k|v row at `pos` and attends to the keys max(0, pos - window + 1) .. pos;
 on the CPU the same math in torch.  It does not advance `pos`: every layer of a step shares it
 and the model calls `KVCache.advance()` once the step is done.
+
+`KVCache(..., kv_dtype="fp8")` keeps the cache in OCP e4m3 with one fp32 scale per (token, kv-head,
+k|v): `layers[i]` is float8_e4m3fn [B, Tmax, 2 Hkv Dh] in the same layout and `scales[i]` fp32
+[B, Tmax, 2 Hkv] in the same head order.  Every run of Dh elements is quantised as
+ops.quantize_fp8_rows quantises a weight row (k after RoPE), so the cache viewed as [B Tmax 2 Hkv, Dh]
+is that function's image of the bf16 cache, bit for bit: 2 Dh + 8 bytes per key and kv-head instead
+of 4 Dh.  `fill` and `decode_attention` dispatch on `cache.kv_dtype`: on the GPU to
+csrc/kernels/attn_decode_fp8.hip (one quantising fill launch for all batch rows; the split-KV step,
+which quantises and stores the new row and attends to it through code * scale), on the CPU to the
+same math in torch.  The default, "bf16", is the cache described above, unchanged.
 """
 from __future__ import annotations
 
@@ -18,20 +28,33 @@ import os
 import torch
 
 from ._ext import gpu_ext, require_dtype
+from .fp8 import FP8, quantize_fp8_rows
 
 
 class KVCache:
     """One [B, Tmax, 2 * Hkv * Dh] cache tensor per layer, `pos` (int32 [B] on the device) and
-    `length`, the host's copy of the largest position (no device read is needed to know it)."""
+    `length`, the host's copy of the largest position (no device read is needed to know it).
+    kv_dtype="fp8": the layer tensors are float8_e4m3fn (`dtype` is not taken) and `scales` holds one
+    fp32 [B, Tmax, 2 * Hkv] tensor per layer; with "bf16" `scales` is None."""
 
-    def __init__(self, n_layers: int, B: int, Tmax: int, Hkv: int, Dh: int, device=None, dtype=None):
+    def __init__(self, n_layers: int, B: int, Tmax: int, Hkv: int, Dh: int, device=None, dtype=None,
+                 kv_dtype: str = "bf16"):
         device = torch.device(device if device is not None else "cpu")
-        if dtype is None:
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f'KVCache: kv_dtype must be "bf16" or "fp8", got {kv_dtype!r}')
+        if kv_dtype == "fp8":
+            if dtype not in (None, FP8):
+                raise ValueError(f'KVCache: kv_dtype="fp8" stores float8_e4m3fn, not {dtype}')
+            dtype = FP8
+        elif dtype is None:
             dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
         if min(n_layers, B, Tmax, Hkv, Dh) < 1:
             raise ValueError("KVCache: every dimension must be >= 1")
-        self.B, self.Tmax, self.Hkv, self.Dh = B, Tmax, Hkv, Dh
+        self.B, self.Tmax, self.Hkv, self.Dh, self.kv_dtype = B, Tmax, Hkv, Dh, kv_dtype
         self.layers = [torch.zeros((B, Tmax, 2 * Hkv * Dh), dtype=dtype, device=device) for _ in range(n_layers)]
+        self.scales = None
+        if kv_dtype == "fp8":
+            self.scales = [torch.ones((B, Tmax, 2 * Hkv), dtype=torch.float32, device=device) for _ in range(n_layers)]
         self.pos = torch.zeros(B, dtype=torch.int32, device=device)
         self.length = 0
         self._part = None
@@ -57,6 +80,17 @@ class KVCache:
             raise ValueError(f"KVCache.fill: qkv {tuple(qkv.shape)} / rows {rows} do not fit the cache "
                              f"[{self.B}, {self.Tmax}, {kvw}]")
         dst = self.layers[layer]
+        if self.kv_dtype == "fp8":
+            if qkv.is_cuda:   # one launch of kv_fill_fp8_kernel; the binding refuses what it cannot take
+                gpu_ext().kv_fill_fp8(qkv, dst, self.scales[layer], n_head, rows)
+            elif rows:
+                runs = qkv[:, :rows, n_head * self.Dh:].reshape(-1, self.Dh).contiguous()
+                if runs.dtype != torch.bfloat16:
+                    runs = runs.float()
+                q, s = quantize_fp8_rows(runs)
+                dst[:, :rows] = q.view(B, rows, kvw)
+                self.scales[layer][:, :rows] = s.view(B, rows, 2 * self.Hkv)
+            return
         if qkv.is_cuda and qkv.is_contiguous() and qkv.dtype == dst.dtype:
             es = qkv.element_size()
             ext = gpu_ext()
@@ -82,19 +116,42 @@ def decode_splits(B: int, Hkv: int, Tmax: int, device) -> int:
     return max(1, min(want, most))
 
 
-def _decode_ref(qkv_new, kv, pos, H, Hkv, Dh, rope, window, scale):
-    B = qkv_new.shape[0]
-    G = H // Hkv
-    Tmax = kv.shape[1]
-    x = qkv_new.reshape(B, H + 2 * Hkv, Dh)
-    p = pos.long()
+def _rotate_new(qkv_new, pos, H, Hkv, Dh, rope):
+    """the new row as [B, H + 2 Hkv, Dh] with its q and k heads rotated at pos (rope given)"""
+    x = qkv_new.reshape(qkv_new.shape[0], H + 2 * Hkv, Dh)
     if rope is not None:
         cos, sin = rope
+        p = pos.long()
         c, s = cos[p][:, None, :], sin[p][:, None, :]
         rot = x[:, : H + Hkv].float()
         x1, x2 = rot[..., : Dh // 2], rot[..., Dh // 2:]
         rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(x.dtype)
         x = torch.cat([rot, x[:, H + Hkv:]], dim=1)
+    return x
+
+
+def _decode_ref_fp8(qkv_new, cache, layer, H, Hkv, Dh, rope, window, scale):
+    """The FP8 cache on the CPU: the rotated new k and v heads are quantised by quantize_fp8_rows'
+    formula and stored, then _decode_ref runs on code * scale, the new key included."""
+    B = qkv_new.shape[0]
+    q, sc = cache.layers[layer], cache.scales[layer]
+    x = _rotate_new(qkv_new, cache.pos, H, Hkv, Dh, rope)
+    runs = x[:, H:].reshape(-1, Dh).contiguous()
+    nq, ns = quantize_fp8_rows(runs if runs.dtype == torch.bfloat16 else runs.float())
+    rows, p = torch.arange(B, device=q.device), cache.pos.long()
+    q[rows, p] = nq.view(B, 2 * Hkv * Dh)
+    sc[rows, p] = ns.view(B, 2 * Hkv)
+    kv = (q.float().view(B, cache.Tmax, 2 * Hkv, Dh) * sc[..., None]).view(B, cache.Tmax, 2 * Hkv * Dh)
+    xq = torch.cat([x[:, :H].float().reshape(B, -1), kv[rows, p]], dim=1)
+    return _decode_ref(xq, kv, cache.pos, H, Hkv, Dh, None, window, scale).to(qkv_new.dtype)
+
+
+def _decode_ref(qkv_new, kv, pos, H, Hkv, Dh, rope, window, scale):
+    B = qkv_new.shape[0]
+    G = H // Hkv
+    Tmax = kv.shape[1]
+    x = _rotate_new(qkv_new, pos, H, Hkv, Dh, rope)
+    p = pos.long()
     kv[torch.arange(B, device=kv.device), p] = x[:, H:].reshape(B, -1).to(kv.dtype)
     t = torch.arange(Tmax, device=kv.device)
     lo = (p - window + 1).clamp_min(0) if window else torch.zeros_like(p)
@@ -116,7 +173,8 @@ def decode_attention(qkv_new: torch.Tensor, cache: KVCache, layer: int, n_head: 
     """qkv_new [B, (H + 2 Hkv) Dh], the new token's packed row before RoPE -> [B, H Dh].
     rope: (cos, sin) of ops.llama_ops.rope_tables with at least Tmax rows (None: no rotation).
     window (None = off): the keys max(0, pos - window + 1) .. pos.  out: an optional [B, H Dh]
-    destination.  Stores the new k|v row (k rotated) at cache.layers[layer][b, pos[b]]."""
+    destination.  Stores the new k|v row (k rotated) at cache.layers[layer][b, pos[b]]; an FP8 cache
+    gets the row's e4m3 codes there and its scales at cache.scales[layer][b, pos[b]]."""
     Hkv = n_kv_head or n_head
     if qkv_new.dim() != 2 or qkv_new.shape[1] % (n_head + 2 * Hkv) or n_head % Hkv:
         raise ValueError(f"decode_attention: qkv_new must be [B, (H + 2 Hkv) Dh], got {tuple(qkv_new.shape)} "
@@ -127,7 +185,8 @@ def decode_attention(qkv_new: torch.Tensor, cache: KVCache, layer: int, n_head: 
     if (B, Hkv, Dh) != (cache.B, cache.Hkv, cache.Dh):
         raise ValueError(f"decode_attention: qkv_new (B={B}, Hkv={Hkv}, Dh={Dh}) does not match the cache "
                          f"(B={cache.B}, Hkv={cache.Hkv}, Dh={cache.Dh})")
-    if qkv_new.device != kv.device or qkv_new.dtype != kv.dtype:
+    fp8 = cache.kv_dtype == "fp8"
+    if qkv_new.device != kv.device or (not fp8 and qkv_new.dtype != kv.dtype):
         raise ValueError(f"decode_attention: qkv_new is {qkv_new.dtype} on {qkv_new.device}, the cache "
                          f"{kv.dtype} on {kv.device}")
     if cache.length >= cache.Tmax:
@@ -146,7 +205,10 @@ def decode_attention(qkv_new: torch.Tensor, cache: KVCache, layer: int, n_head: 
         raise ValueError("decode_attention: out must be a contiguous [B, H Dh] tensor like qkv_new")
     scale = 1.0 / math.sqrt(Dh)
     if not qkv_new.is_cuda:
-        y = _decode_ref(qkv_new, kv, cache.pos, n_head, Hkv, Dh, rope, window, scale)
+        if fp8:
+            y = _decode_ref_fp8(qkv_new, cache, layer, n_head, Hkv, Dh, rope, window, scale)
+        else:
+            y = _decode_ref(qkv_new, kv, cache.pos, n_head, Hkv, Dh, rope, window, scale)
         if out is not None:
             out.copy_(y)
             return out
@@ -167,5 +229,9 @@ def decode_attention(qkv_new: torch.Tensor, cache: KVCache, layer: int, n_head: 
     if out is None:
         out = torch.empty((B, n_head * Dh), dtype=torch.bfloat16, device=kv.device)
     cos, sin = rope if rope is not None else (None, None)
-    gpu_ext().decode_attn(qkv_new, kv, cache.pos, cos, sin, out, part, n_head, Hkv, window or 0, nsplit, scale)
+    if fp8:
+        gpu_ext().decode_attn_fp8kv(qkv_new, kv, cache.scales[layer], cache.pos, cos, sin, out, part, n_head, Hkv,
+                                    window or 0, nsplit, scale)
+    else:
+        gpu_ext().decode_attn(qkv_new, kv, cache.pos, cos, sin, out, part, n_head, Hkv, window or 0, nsplit, scale)
     return out

@@ -1,4 +1,4 @@
-"""Decode attention (split-KV kernel, csrc/kernels/attn_decode.hip) and generate() benchmark.
+"""Decode attention (split-KV kernel, csrc/kernels/attn_decode.hip, bf16 and FP8 cache) and generate() benchmark.
 
     python benchmarks/decode_bench.py [--rounds 7] [--window-ms 20] [--only llama8b] [--no-generate] [--out FILE]
     python benchmarks/decode_bench.py --fast [--fast-out FILE]      # the few-row / captured tables only
@@ -26,7 +26,7 @@ same bf16 kernel (its ratio to the first is the spread a ratio has to beat); wei
 N K + 4 N (codes and scales) against 2 N K; in (b)'s loop two more arms, eager / captured with
 weights="fp8".
 --kv-cache fp8 runs the tables of profiles/decode_fp8_kv.md alone (--kv-out FILE): per SHAPES row the
-FP8-cache decode kernel (csrc/kernels/attn_decode_fp8.hip) alternating with the bf16 kernel on the same
+FP8-cache decode kernel (the same file's e4m3 instantiations) alternating with the bf16 kernel on the same
 values (the FP8 cache is the quantised bf16 one), bytes = the cached keys' K and V bytes plus, for FP8,
 their scales, over the copy rate; then per decode step and generate() tokens/s of gpt2-small and
 llama3-1b at B = 1 and 8 with the bf16 and the FP8 cache, eager, and together with captured few-row
@@ -384,7 +384,7 @@ def kv_kernel_rows(args, rate):
         cos, sin = rope_tables(Tmax, Dh, 500000.0, DEV) if rope else (None, None)
         scale = Dh ** -0.5
         r = ab({"bf16": lambda: ext.decode_attn(qkv_new, cache, pos, cos, sin, out, part, H, Hkv, 0, ns, scale),
-                "fp8": lambda: ext.decode_attn_fp8kv(qkv_new, cq, cs, pos, cos, sin, out, part, H, Hkv, 0, ns, scale)},
+                "fp8": lambda: ext.decode_attn(qkv_new, cq, pos, cos, sin, out, part, H, Hkv, 0, ns, scale, cache_scale=cs)},
                args.rounds, args.window_ms)
         (bm, bmin, _, bmax), (fm, fmin, _, fmax) = r["bf16"], r["fp8"]
         bb, fb = B * L * 2 * Hkv * Dh * 2, B * L * 2 * Hkv * (Dh + 4)

@@ -125,9 +125,9 @@ int rtdc_rope_doc(const void* x, void* y, const float* cosb, const float* sinb, 
 int rtdc_doc_layout(const uint8_t* flags, int B, int T, int* start, int* end, hipStream_t st);
 int rtdc_synth_doc_flags(const int64_t* ids, int B, int T, long long doc_len, unsigned long long seed_add,
                          uint8_t* flags, hipStream_t st);
-int rtdc_decode_attn(const void* qkv_new, void* cache, const int* pos, const float* cosb, const float* sinb, void* out,
-                     float* part, int B, int Tmax, int H, int Hkv, int Dh, int window, int nsplit, float scale,
-                     hipStream_t st);
+int rtdc_decode_attn(const void* qkv_new, void* cache, float* cache_scale, const int* pos, const float* cosb,
+                     const float* sinb, void* out, float* part, int B, int Tmax, int H, int Hkv, int Dh, int window,
+                     int nsplit, float scale, hipStream_t st);
 int rtdc_gemm_few_rows(const void* x, const void* w, const void* bias, int bias_type, const void* res, void* y, int M,
                        int N, int K, int act, hipStream_t st);
 void rtdc_few_rows_plan(long long N, long long K, int* waves, int* per);
@@ -135,9 +135,6 @@ int rtdc_gemm_few_rows_fp8(const void* x, const void* q, const void* scale, cons
                            const void* res, void* y, int M, int N, int K, int act, hipStream_t st);
 void rtdc_few_rows_fp8_plan(long long N, long long K, int* tiles_per_block, int* waves, int* per);
 int rtdc_quantize_fp8_rows(const void* w, int src_bf16, void* q, void* scale, long long N, long long K, hipStream_t st);
-int rtdc_decode_attn_fp8kv(const void* qkv_new, void* cache_q, float* cache_scale, const int* pos, const float* cosb,
-                           const float* sinb, void* out, float* part, int B, int Tmax, int H, int Hkv, int Dh,
-                           int window, int nsplit, float scale, hipStream_t st);
 int rtdc_kv_fill_fp8(const void* qkv, void* cache_q, float* cache_scale, int B, int T, int Tmax, int H, int Hkv, int Dh,
                      int rows, hipStream_t st);
 }
@@ -853,52 +850,7 @@ static void rope(Tensor x, Tensor y, Tensor cosb, Tensor sinb, int64_t T, int64_
                      (int)nrot_heads, (int)ntot_heads, (int)Dh, inverse, cur_stream()),
            "rope");
 }
-// Decode attention (attn_decode.hip): one new token per row of qkv_new [B, (H + 2 Hkv) Dh] against
-// cache [B, Tmax, 2 Hkv Dh]; stores the token's k|v row at cache[b, pos[b]] and writes out [B, H Dh].
-// part: fp32 workspace of at least B * H * nsplit * (Dh + 2) elements.  cosb / sinb: rope tables
-// with at least Tmax rows, or both absent.
-static void decode_attn(Tensor qkv_new, Tensor cache, Tensor pos, c10::optional<Tensor> cosb,
-                        c10::optional<Tensor> sinb, Tensor out, Tensor part, int64_t H, int64_t Hkv, int64_t window,
-                        int64_t nsplit, double scale) {
-  TORCH_CHECK(qkv_new.dim() == 2 && cache.dim() == 3 && pos.dim() == 1 && out.dim() == 2,
-              "decode_attn: qkv_new [B, W], cache [B, Tmax, 2 Hkv Dh], pos [B], out [B, H Dh] expected");
-  const int64_t B = qkv_new.size(0), Tmax = cache.size(1);
-  TORCH_CHECK(H >= 1 && Hkv >= 1 && H % Hkv == 0 && qkv_new.size(1) % (H + 2 * Hkv) == 0, "decode_attn: bad head counts");
-  const int64_t Dh = qkv_new.size(1) / (H + 2 * Hkv);
-  check_dev(qkv_new, "decode_attn: qkv_new");
-  check_dev(cache, "decode_attn: cache");
-  check_dev(out, "decode_attn: out");
-  TORCH_CHECK(part.is_cuda(), "decode_attn: part must be a GPU tensor");
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
-              "decode_attn: pos must be contiguous int32 [B] on the device");
-  TORCH_CHECK(qkv_new.scalar_type() == at::kBFloat16 && cache.scalar_type() == at::kBFloat16 &&
-                  out.scalar_type() == at::kBFloat16 && part.scalar_type() == at::kFloat,
-              "decode_attn: bf16 qkv_new / cache / out and fp32 part expected");
-  TORCH_CHECK(qkv_new.is_contiguous() && cache.is_contiguous() && out.is_contiguous() && part.is_contiguous(),
-              "decode_attn: contiguous tensors expected");
-  TORCH_CHECK(cache.size(0) == B && cache.size(2) == 2 * Hkv * Dh && out.size(0) == B && out.size(1) == H * Dh,
-              "decode_attn: cache / out do not match qkv_new");
-  TORCH_CHECK(cache.device() == qkv_new.device() && out.device() == qkv_new.device() &&
-                  part.device() == qkv_new.device() && pos.device() == qkv_new.device(),
-              "decode_attn: tensors on different devices");
-  TORCH_CHECK(nsplit >= 1 && part.numel() >= B * H * nsplit * (Dh + 2), "decode_attn: part workspace too small");
-  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "decode_attn: window must be >= 0 (0 = off)");
-  TORCH_CHECK(cosb.has_value() == sinb.has_value(), "decode_attn: cos and sin tables go together");
-  const float *cp = nullptr, *sp = nullptr;
-  if (cosb.has_value()) {
-    for (const Tensor* t : {&*cosb, &*sinb})
-      TORCH_CHECK(t->is_cuda() && t->device() == qkv_new.device() && t->scalar_type() == at::kFloat &&
-                      t->is_contiguous() && t->dim() == 2 && t->size(0) >= Tmax && t->size(1) == Dh / 2,
-                  "decode_attn: rope tables must be contiguous fp32 [>= Tmax, Dh / 2] on the device");
-    cp = cosb->data_ptr<float>();
-    sp = sinb->data_ptr<float>();
-  }
-  check_rc(rtdc_decode_attn(qkv_new.data_ptr(), cache.data_ptr(), pos.data_ptr<int>(), cp, sp, out.data_ptr(),
-                            part.data_ptr<float>(), (int)B, (int)Tmax, (int)H, (int)Hkv, (int)Dh, (int)window,
-                            (int)nsplit, (float)scale, cur_stream()),
-           "decode_attn");
-}
-// The FP8 KV cache of attn_decode_fp8.hip: cache_q [B, Tmax, 2 Hkv Dh] float8_e4m3fn in the layout of the
+// The FP8 KV cache of attn_decode.hip: cache_q [B, Tmax, 2 Hkv Dh] float8_e4m3fn in the layout of the
 // bf16 cache, cache_scale [B, Tmax, 2 Hkv] fp32.  Dtypes and shapes are checked here, before any launch.
 static void check_fp8_cache(const Tensor& ref, const Tensor& cq, const Tensor& cs, int64_t B, int64_t Hkv, int64_t Dh,
                             const char* what) {
@@ -913,47 +865,64 @@ static void check_fp8_cache(const Tensor& ref, const Tensor& cq, const Tensor& c
               what, ": cache_q / cache_scale do not match qkv");
   TORCH_CHECK(((uintptr_t)cq.data_ptr()) % 16 == 0, what, ": cache_q must be 16-byte aligned");
 }
-static void decode_attn_fp8kv(Tensor qkv_new, Tensor cache_q, Tensor cache_scale, Tensor pos,
-                              c10::optional<Tensor> cosb, c10::optional<Tensor> sinb, Tensor out, Tensor part,
-                              int64_t H, int64_t Hkv, int64_t window, int64_t nsplit, double scale) {
-  TORCH_CHECK(qkv_new.dim() == 2 && pos.dim() == 1 && out.dim() == 2,
-              "decode_attn_fp8kv: qkv_new [B, W], pos [B], out [B, H Dh] expected");
-  const int64_t B = qkv_new.size(0);
-  TORCH_CHECK(H >= 1 && Hkv >= 1 && H % Hkv == 0 && qkv_new.size(1) % (H + 2 * Hkv) == 0,
-              "decode_attn_fp8kv: bad head counts");
+// The bf16 cache [B, Tmax, 2 Hkv Dh] (no cache_scale): a float8_e4m3fn cache is named, it needs its scales.
+static void check_bf16_cache(const Tensor& ref, const Tensor& cache, int64_t B, int64_t Hkv, int64_t Dh,
+                             const char* what) {
+  TORCH_CHECK(cache.scalar_type() != at::kFloat8_e4m3fn, what, ": a float8_e4m3fn cache needs its cache_scale");
+  TORCH_CHECK(cache.is_cuda() && cache.device() == ref.device(), what, ": cache must be a GPU tensor on the device of qkv_new");
+  TORCH_CHECK(((uintptr_t)cache.data_ptr()) % 16 == 0, what, ": cache must be 16-byte aligned");
+  TORCH_CHECK(cache.scalar_type() == at::kBFloat16, what, ": bf16 cache (or float8_e4m3fn with its cache_scale) expected");
+  TORCH_CHECK(cache.is_contiguous(), what, ": contiguous cache expected");
+  TORCH_CHECK(cache.size(0) == B && cache.size(2) == 2 * Hkv * Dh, what, ": cache and qkv_new do not match");
+}
+// Decode attention (attn_decode.hip): one new token per row of qkv_new [B, (H + 2 Hkv) Dh] against
+// cache [B, Tmax, 2 Hkv Dh]; stores the token's k|v row at cache[b, pos[b]] and writes out [B, H Dh].
+// The cache is bf16, or float8_e4m3fn (cache_q) together with cache_scale [B, Tmax, 2 Hkv] fp32, which
+// then gets the row's scales; one without the other is refused.  part: fp32 workspace of at least
+// B * H * nsplit * (Dh + 2) elements.  cosb / sinb: rope tables with at least Tmax rows, or both absent.
+static void decode_attn(Tensor qkv_new, Tensor cache, Tensor pos, c10::optional<Tensor> cosb,
+                        c10::optional<Tensor> sinb, Tensor out, Tensor part, int64_t H, int64_t Hkv, int64_t window,
+                        int64_t nsplit, double scale, c10::optional<Tensor> cache_scale) {
+  TORCH_CHECK(qkv_new.dim() == 2 && cache.dim() == 3 && pos.dim() == 1 && out.dim() == 2,
+              "decode_attn: qkv_new [B, W], cache [B, Tmax, 2 Hkv Dh], pos [B], out [B, H Dh] expected");
+  const int64_t B = qkv_new.size(0), Tmax = cache.size(1);
+  TORCH_CHECK(H >= 1 && Hkv >= 1 && H % Hkv == 0 && qkv_new.size(1) % (H + 2 * Hkv) == 0, "decode_attn: bad head counts");
   const int64_t Dh = qkv_new.size(1) / (H + 2 * Hkv);
-  check_dev(qkv_new, "decode_attn_fp8kv: qkv_new");
-  check_dev(out, "decode_attn_fp8kv: out");
-  check_fp8_cache(qkv_new, cache_q, cache_scale, B, Hkv, Dh, "decode_attn_fp8kv");
-  const int64_t Tmax = cache_q.size(1);
-  TORCH_CHECK(part.is_cuda(), "decode_attn_fp8kv: part must be a GPU tensor");
+  check_dev(qkv_new, "decode_attn: qkv_new");
+  check_dev(out, "decode_attn: out");
+  if (cache_scale.has_value()) {
+    check_fp8_cache(qkv_new, cache, *cache_scale, B, Hkv, Dh, "decode_attn");
+  } else {
+    check_bf16_cache(qkv_new, cache, B, Hkv, Dh, "decode_attn");
+  }
+  TORCH_CHECK(part.is_cuda(), "decode_attn: part must be a GPU tensor");
   TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
-              "decode_attn_fp8kv: pos must be contiguous int32 [B] on the device");
+              "decode_attn: pos must be contiguous int32 [B] on the device");
   TORCH_CHECK(qkv_new.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16 &&
                   part.scalar_type() == at::kFloat,
-              "decode_attn_fp8kv: bf16 qkv_new / out and fp32 part expected");
+              "decode_attn: bf16 qkv_new / cache / out and fp32 part expected");
   TORCH_CHECK(qkv_new.is_contiguous() && out.is_contiguous() && part.is_contiguous(),
-              "decode_attn_fp8kv: contiguous tensors expected");
-  TORCH_CHECK(out.size(0) == B && out.size(1) == H * Dh, "decode_attn_fp8kv: out does not match qkv_new");
+              "decode_attn: contiguous tensors expected");
+  TORCH_CHECK(out.size(0) == B && out.size(1) == H * Dh, "decode_attn: cache / out do not match qkv_new");
   TORCH_CHECK(out.device() == qkv_new.device() && part.device() == qkv_new.device() && pos.device() == qkv_new.device(),
-              "decode_attn_fp8kv: tensors on different devices");
-  TORCH_CHECK(nsplit >= 1 && part.numel() >= B * H * nsplit * (Dh + 2), "decode_attn_fp8kv: part workspace too small");
-  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "decode_attn_fp8kv: window must be >= 0 (0 = off)");
-  TORCH_CHECK(cosb.has_value() == sinb.has_value(), "decode_attn_fp8kv: cos and sin tables go together");
+              "decode_attn: tensors on different devices");
+  TORCH_CHECK(nsplit >= 1 && part.numel() >= B * H * nsplit * (Dh + 2), "decode_attn: part workspace too small");
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "decode_attn: window must be >= 0 (0 = off)");
+  TORCH_CHECK(cosb.has_value() == sinb.has_value(), "decode_attn: cos and sin tables go together");
   const float *cp = nullptr, *sp = nullptr;
   if (cosb.has_value()) {
     for (const Tensor* t : {&*cosb, &*sinb})
       TORCH_CHECK(t->is_cuda() && t->device() == qkv_new.device() && t->scalar_type() == at::kFloat &&
                       t->is_contiguous() && t->dim() == 2 && t->size(0) >= Tmax && t->size(1) == Dh / 2,
-                  "decode_attn_fp8kv: rope tables must be contiguous fp32 [>= Tmax, Dh / 2] on the device");
+                  "decode_attn: rope tables must be contiguous fp32 [>= Tmax, Dh / 2] on the device");
     cp = cosb->data_ptr<float>();
     sp = sinb->data_ptr<float>();
   }
-  check_rc(rtdc_decode_attn_fp8kv(qkv_new.data_ptr(), cache_q.data_ptr(), cache_scale.data_ptr<float>(),
-                                  pos.data_ptr<int>(), cp, sp, out.data_ptr(), part.data_ptr<float>(), (int)B,
-                                  (int)Tmax, (int)H, (int)Hkv, (int)Dh, (int)window, (int)nsplit, (float)scale,
-                                  cur_stream()),
-           "decode_attn_fp8kv");
+  check_rc(rtdc_decode_attn(qkv_new.data_ptr(), cache.data_ptr(),
+                            cache_scale.has_value() ? cache_scale->data_ptr<float>() : nullptr, pos.data_ptr<int>(), cp,
+                            sp, out.data_ptr(), part.data_ptr<float>(), (int)B, (int)Tmax, (int)H, (int)Hkv, (int)Dh,
+                            (int)window, (int)nsplit, (float)scale, cur_stream()),
+           "decode_attn");
 }
 // The prefill's fill: rows t < rows of the k|v tail of qkv [B, T, (H + 2 Hkv) Dh], quantised per head run.
 static void kv_fill_fp8(Tensor qkv, Tensor cache_q, Tensor cache_scale, int64_t n_head, int64_t rows) {
@@ -973,41 +942,51 @@ static void kv_fill_fp8(Tensor qkv, Tensor cache_q, Tensor cache_scale, int64_t 
                             (int)Tmax, (int)n_head, (int)Hkv, (int)Dh, (int)rows, cur_stream()),
            "kv_fill_fp8");
 }
-// Few-row linear (gemm_few_rows.hip): out[M, N] = act(x[M, K] . w[N, K]^T + bias + residual), 1 <= M <= 16,
-// K % 64 == 0, N % 8 == 0, every operand contiguous and 16-byte aligned; act 0 (none) or 2 (tanh GELU).
-// Anything else is refused here, before a launch: there is no other kernel behind this entry.
-static void gemm_few_rows(Tensor x, Tensor w, c10::optional<Tensor> bias, c10::optional<Tensor> residual, Tensor out,
-                          int64_t act) {
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "gemm_few_rows: x [M, K], w [N, K], out [M, N] expected");
+// What the two few-row linears refuse alike, before a launch: x [M, K] with 1 <= M <= 16, the weight
+// [N, K] with N % 8 == 0, out [M, N], bf16 x and out, every operand contiguous, 16-byte aligned and on
+// x's device, act 0 (none) or 2 (tanh GELU), bias bf16 or fp32 [N], residual bf16 [M, N].  Returns
+// the bias type of the native entries (0 none, 1 bf16, 2 fp32).
+static int check_few_rows(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias,
+                          const c10::optional<Tensor>& residual, const Tensor& out, int64_t act, const char* what,
+                          const char* wname) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2,
+              what, ": x [M, K], ", wname, " [N, K], out [M, N] expected");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 &&
-                  out.scalar_type() == at::kBFloat16,
-              "gemm_few_rows: bf16 x, w and out expected");
-  check_dev(x, "gemm_few_rows: x");
-  check_dev(w, "gemm_few_rows: w");
-  check_dev(out, "gemm_few_rows: out");
-  TORCH_CHECK(M >= 1 && M <= 16, "gemm_few_rows: 1 <= M <= 16 rows expected, got ", M);
-  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "gemm_few_rows: shapes do not match");
-  TORCH_CHECK(K >= 64 && K % 64 == 0 && N >= 8 && N % 8 == 0 && N <= INT32_MAX && K <= INT32_MAX,
-              "gemm_few_rows: K % 64 == 0 and N % 8 == 0 expected, got N=", N, " K=", K);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous(), "gemm_few_rows: contiguous x, w and out expected");
-  TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "gemm_few_rows: tensors on different devices");
-  TORCH_CHECK(act == 0 || act == 2, "gemm_few_rows: act must be 0 (none) or 2 (gelu_tanh)");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16, what, ": bf16 x and out expected");
+  for (const Tensor* t : {&x, &w, &out}) {
+    TORCH_CHECK(t->is_cuda(), what, ": x, ", wname, " and out must be GPU tensors");
+    TORCH_CHECK(((uintptr_t)t->data_ptr()) % 16 == 0, what, ": x, ", wname, " and out must be 16-byte aligned");
+  }
+  TORCH_CHECK(M >= 1 && M <= 16, what, ": 1 <= M <= 16 rows expected, got ", M);
+  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, what, ": shapes do not match");
+  TORCH_CHECK(N >= 8 && N % 8 == 0 && N <= INT32_MAX && K <= INT32_MAX, what, ": N % 8 == 0 expected, got N=", N, " K=", K);
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous(),
+              what, ": contiguous x, ", wname, " and out expected");
+  TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), what, ": tensors on different devices");
+  TORCH_CHECK(act == 0 || act == 2, what, ": act must be 0 (none) or 2 (gelu_tanh)");
   int bias_type = 0;
   if (bias.has_value()) {
-    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat,
-                "gemm_few_rows: bias must be bf16 or fp32");
-    check_dev(*bias, "gemm_few_rows: bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(),
-                "gemm_few_rows: bias must be a contiguous [N] tensor on x's device");
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat, what, ": bias must be bf16 or fp32");
+    TORCH_CHECK(bias->is_cuda() && ((uintptr_t)bias->data_ptr()) % 16 == 0 && bias->is_contiguous() &&
+                    bias->numel() == N && bias->device() == x.device(),
+                what, ": bias must be a contiguous, 16-byte aligned [N] tensor on x's device");
     bias_type = bias->scalar_type() == at::kBFloat16 ? 1 : 2;
   }
-  if (residual.has_value()) {
-    check_dev(*residual, "gemm_few_rows: residual");
-    TORCH_CHECK(residual->scalar_type() == at::kBFloat16 && residual->is_contiguous() && residual->dim() == 2 &&
+  if (residual.has_value())
+    TORCH_CHECK(residual->is_cuda() && ((uintptr_t)residual->data_ptr()) % 16 == 0 &&
+                    residual->scalar_type() == at::kBFloat16 && residual->is_contiguous() && residual->dim() == 2 &&
                     residual->size(0) == M && residual->size(1) == N && residual->device() == x.device(),
-                "gemm_few_rows: residual must be a contiguous bf16 [M, N] tensor on x's device");
-  }
+                what, ": residual must be a contiguous, 16-byte aligned bf16 [M, N] tensor on x's device");
+  return bias_type;
+}
+// Few-row linear (gemm_few_rows.hip): out[M, N] = act(x[M, K] . w[N, K]^T + bias + residual), bf16 w,
+// K % 64 == 0.  Anything else is refused here, before a launch: there is no other kernel behind this entry.
+static void gemm_few_rows(Tensor x, Tensor w, c10::optional<Tensor> bias, c10::optional<Tensor> residual, Tensor out,
+                          int64_t act) {
+  const int bias_type = check_few_rows(x, w, bias, residual, out, act, "gemm_few_rows", "w");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, "gemm_few_rows: bf16 w expected");
+  TORCH_CHECK(K >= 64 && K % 64 == 0, "gemm_few_rows: K % 64 == 0 expected, got K=", K);
   check_rc(rtdc_gemm_few_rows(x.data_ptr(), w.data_ptr(), ptr_or_null(bias), bias_type, ptr_or_null(residual),
                               out.data_ptr(), (int)M, (int)N, (int)K, (int)act, cur_stream()),
            "gemm_few_rows");
@@ -1019,46 +998,17 @@ static std::vector<int64_t> few_rows_plan(int64_t N, int64_t K) {
   return {waves, per};
 }
 // FP8-weight few-row linear (gemm_few_rows_fp8.hip): out[M, N] = act((x[M, K] . q[N, K]^T) * scale[n] + bias +
-// residual), 1 <= M <= 16, K % 128 == 0, N % 8 == 0, q e4m3, scale fp32 [N], every operand contiguous and 16-byte
-// aligned; act 0 (none) or 2 (tanh GELU).  Anything else is refused here, before a launch.
+// residual), q e4m3, scale fp32 [N], K % 128 == 0.  Anything else is refused here, before a launch.
 static void gemm_few_rows_fp8(Tensor x, Tensor q, Tensor scale, c10::optional<Tensor> bias,
                               c10::optional<Tensor> residual, Tensor out, int64_t act) {
-  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && out.dim() == 2,
-              "gemm_few_rows_fp8: x [M, K], q [N, K], out [M, N] expected");
+  const int bias_type = check_few_rows(x, q, bias, residual, out, act, "gemm_few_rows_fp8", "q");
   const int64_t M = x.size(0), K = x.size(1), N = q.size(0);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
-              "gemm_few_rows_fp8: bf16 x and out expected");
   TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn, "gemm_few_rows_fp8: q must be float8_e4m3fn");
-  check_dev(x, "gemm_few_rows_fp8: x");
-  check_dev(q, "gemm_few_rows_fp8: q");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "gemm_few_rows_fp8: K % 128 == 0 expected, got K=", K);
   check_dev(scale, "gemm_few_rows_fp8: scale");
-  check_dev(out, "gemm_few_rows_fp8: out");
-  TORCH_CHECK(M >= 1 && M <= 16, "gemm_few_rows_fp8: 1 <= M <= 16 rows expected, got ", M);
-  TORCH_CHECK(q.size(1) == K && out.size(0) == M && out.size(1) == N, "gemm_few_rows_fp8: shapes do not match");
-  TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= 8 && N % 8 == 0 && N <= INT32_MAX && K <= INT32_MAX,
-              "gemm_few_rows_fp8: K % 128 == 0 and N % 8 == 0 expected, got N=", N, " K=", K);
-  TORCH_CHECK(x.is_contiguous() && q.is_contiguous() && out.is_contiguous(),
-              "gemm_few_rows_fp8: contiguous x, q and out expected");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.dim() == 1 && scale.size(0) == N && scale.is_contiguous(),
-              "gemm_few_rows_fp8: scale must be a contiguous fp32 [N] tensor");
-  TORCH_CHECK(q.device() == x.device() && scale.device() == x.device() && out.device() == x.device(),
-              "gemm_few_rows_fp8: tensors on different devices");
-  TORCH_CHECK(act == 0 || act == 2, "gemm_few_rows_fp8: act must be 0 (none) or 2 (gelu_tanh)");
-  int bias_type = 0;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat,
-                "gemm_few_rows_fp8: bias must be bf16 or fp32");
-    check_dev(*bias, "gemm_few_rows_fp8: bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(),
-                "gemm_few_rows_fp8: bias must be a contiguous [N] tensor on x's device");
-    bias_type = bias->scalar_type() == at::kBFloat16 ? 1 : 2;
-  }
-  if (residual.has_value()) {
-    check_dev(*residual, "gemm_few_rows_fp8: residual");
-    TORCH_CHECK(residual->scalar_type() == at::kBFloat16 && residual->is_contiguous() && residual->dim() == 2 &&
-                    residual->size(0) == M && residual->size(1) == N && residual->device() == x.device(),
-                "gemm_few_rows_fp8: residual must be a contiguous bf16 [M, N] tensor on x's device");
-  }
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.dim() == 1 && scale.size(0) == N && scale.is_contiguous() &&
+                  scale.device() == x.device(),
+              "gemm_few_rows_fp8: scale must be a contiguous fp32 [N] tensor on x's device");
   check_rc(rtdc_gemm_few_rows_fp8(x.data_ptr(), q.data_ptr(), scale.data_ptr(), ptr_or_null(bias), bias_type,
                                   ptr_or_null(residual), out.data_ptr(), (int)M, (int)N, (int)K, (int)act,
                                   cur_stream()),
@@ -1633,10 +1583,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_doc", &rope_doc);
   m.def("decode_attn", &decode_attn, py::arg("qkv_new"), py::arg("cache"), py::arg("pos"), py::arg("cos"),
         py::arg("sin"), py::arg("out"), py::arg("part"), py::arg("H"), py::arg("Hkv"), py::arg("window"),
-        py::arg("nsplit"), py::arg("scale"));
-  m.def("decode_attn_fp8kv", &decode_attn_fp8kv, py::arg("qkv_new"), py::arg("cache_q"), py::arg("cache_scale"),
-        py::arg("pos"), py::arg("cos"), py::arg("sin"), py::arg("out"), py::arg("part"), py::arg("H"), py::arg("Hkv"),
-        py::arg("window"), py::arg("nsplit"), py::arg("scale"));
+        py::arg("nsplit"), py::arg("scale"), py::arg("cache_scale") = py::none());
   m.def("kv_fill_fp8", &kv_fill_fp8, py::arg("qkv"), py::arg("cache_q"), py::arg("cache_scale"), py::arg("n_head"),
         py::arg("rows"));
   m.def("gemm_few_rows", &gemm_few_rows, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("residual"),

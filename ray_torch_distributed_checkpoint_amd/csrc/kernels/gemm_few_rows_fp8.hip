@@ -6,7 +6,7 @@
 //
 // A decode step's linear is a read of its weights; a bf16 kernel cannot go below its bytes, so
 // this one reads half of them.  Every e4m3 value is a bf16 value: the weights are widened in
-// registers (v_cvt_scalef32_pk_bf16_fp8 at scale 1.0, two bytes per VALU op) and fed to the same
+// registers (fp8.h: v_cvt_scalef32_pk_bf16_fp8 at scale 1.0, two bytes per VALU op) and fed to the same
 // v_mfma_f32_16x16x32_bf16 as gemm_few_rows.hip, so against the dequantised weights the only error
 // is the fp32 accumulation.  The row scale multiplies the fp32 sum in the epilogue.
 //
@@ -41,8 +41,10 @@
 //
 // quant_fp8_rows_kernel: one wave per weight row (4 rows per block), 16 elements per lane and
 // step.  Pass 1 takes the row maximum (DPP / row-swap wave_max of common.h), pass 2 re-reads the
-// row (it is in the L2), divides, converts with v_cvt_pk_fp8_f32 and stores 16 bytes per lane.
+// row (it is in the L2), divides, converts with v_cvt_pk_fp8_f32 and stores 16 bytes per lane, by
+// fp8.h's formula, which the FP8 KV cache (attn_decode.hip) shares.
 #include "common.h"
+#include "fp8.h"
 
 namespace rtdc {
 
@@ -50,8 +52,6 @@ constexpr int kF8MaxWaves = 16;
 constexpr int kF8MaxWavesT = 8;    // T > 1: the fragments in flight need more than the 128 VGPRs of a 16-wave block
 constexpr int kF8InFlight = 16384; // (tile, wave) load streams x chunks each keeps in flight, at 2 KiB: 32 MiB
 __host__ __device__ constexpr int f8_group(int T) { return T == 4 ? 2 : 4; }
-
-typedef __attribute__((ext_vector_type(2))) __bf16 f8_bf16x2;
 
 struct FewRowsFp8Args {
   const bf16_t* x;
@@ -75,11 +75,11 @@ __device__ __forceinline__ void f8_load4_bf16(const bf16_t* p, float* v) {
 
 // 8 e4m3 bytes (k ascending with the byte address) -> one bf16x8 MFMA fragment, exactly
 __device__ __forceinline__ bf16x8 f8_widen8(uint32_t lo, uint32_t hi) {
-  union { f8_bf16x2 p[4]; bf16x8 v; } u;
-  u.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
-  u.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
-  u.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
-  u.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+  union { fp8_bf16x2 p[4]; bf16x8 v; } u;
+  u.p[0] = fp8_widen2<false>(lo);
+  u.p[1] = fp8_widen2<true>(lo);
+  u.p[2] = fp8_widen2<false>(hi);
+  u.p[3] = fp8_widen2<true>(hi);
   return u.v;
 }
 
@@ -230,19 +230,12 @@ __global__ __launch_bounds__(kQuantRows * 64) void quant_fp8_rows_kernel(const T
     for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
   }
   amax = wave_max(amax);
-  const float s = amax > 0.f ? __fdiv_rn(amax, 448.f) : 1.f;
+  const float s = fp8_scale(amax);
   if (lane == 0) scale[n] = s;
   uint8_t* qrow = q + (long long)n * K;
   for (int k = 16 * lane; k < K; k += 16 * 64) {
     f8_load16(row + k, v);
-    uint32_t o[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int p = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(v[4 * i], s), __fdiv_rn(v[4 * i + 1], s), 0, false);
-      p = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(v[4 * i + 2], s), __fdiv_rn(v[4 * i + 3], s), p, true);
-      o[i] = (uint32_t)p;
-    }
-    *(uint4*)(qrow + k) = make_uint4(o[0], o[1], o[2], o[3]);
+    *(uint4*)(qrow + k) = make_uint4(fp8_pack4(v, s), fp8_pack4(v + 4, s), fp8_pack4(v + 8, s), fp8_pack4(v + 12, s));
   }
 }
 

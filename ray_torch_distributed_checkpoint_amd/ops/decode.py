@@ -15,10 +15,10 @@ k|v): `layers[i]` is float8_e4m3fn [B, Tmax, 2 Hkv Dh] in the same layout and `s
 [B, Tmax, 2 Hkv] in the same head order.  Every run of Dh elements is quantised as
 ops.quantize_fp8_rows quantises a weight row (k after RoPE), so the cache viewed as [B Tmax 2 Hkv, Dh]
 is that function's image of the bf16 cache, bit for bit: 2 Dh + 8 bytes per key and kv-head instead
-of 4 Dh.  `fill` and `decode_attention` dispatch on `cache.kv_dtype`: on the GPU to
-csrc/kernels/attn_decode_fp8.hip (one quantising fill launch for all batch rows; the split-KV step,
-which quantises and stores the new row and attends to it through code * scale), on the CPU to the
-same math in torch.  The default, "bf16", is the cache described above, unchanged.
+of 4 Dh.  `fill` and `decode_attention` follow `cache.kv_dtype`: on the GPU the same file's quantising
+fill (one launch for all batch rows) and the same split-KV kernel, which is given the scales, quantises
+and stores the new row and attends to it through code * scale; on the CPU the same math in torch.  The
+default, "bf16", is the cache described above, unchanged.
 """
 from __future__ import annotations
 
@@ -229,9 +229,6 @@ def decode_attention(qkv_new: torch.Tensor, cache: KVCache, layer: int, n_head: 
     if out is None:
         out = torch.empty((B, n_head * Dh), dtype=torch.bfloat16, device=kv.device)
     cos, sin = rope if rope is not None else (None, None)
-    if fp8:
-        gpu_ext().decode_attn_fp8kv(qkv_new, kv, cache.scales[layer], cache.pos, cos, sin, out, part, n_head, Hkv,
-                                    window or 0, nsplit, scale)
-    else:
-        gpu_ext().decode_attn(qkv_new, kv, cache.pos, cos, sin, out, part, n_head, Hkv, window or 0, nsplit, scale)
+    gpu_ext().decode_attn(qkv_new, kv, cache.pos, cos, sin, out, part, n_head, Hkv, window or 0, nsplit, scale,
+                          cache_scale=cache.scales[layer] if fp8 else None)
     return out

@@ -2,7 +2,7 @@
 (RTDC_EXT_SO=<path>) can be compared bitwise - the check behind every "bitwise equal" A/B record
 in profiles/.
 
-    python scripts/bitwise_dump.py attn|norm|colsum|xent|resnet|gemm OUT.pt
+    python scripts/bitwise_dump.py attn|norm|colsum|xent|resnet|gemm|decode|few_rows OUT.pt
     python scripts/bitwise_dump.py compare A.pt B.pt
 
 `norm`, `colsum` and `xent` call the native entry points at small shapes that reach every
@@ -15,6 +15,12 @@ at 1 and at 2, head splits, every output; plain, document-masked, sliding window
 last two with and without a layout), then three large default cases (profiles/attn_merge_bitwise.md).
 Against a commit whose attention bindings differ (profiles/attn_one_entry_bitwise.md) it is run from
 that commit's own checkout, with this file dropped in and the two calls of _attn_variants rewritten.
+
+`decode` and `few_rows` (profiles/decode_one_kernel.md) call the native entries of the generation path:
+every instantiation of the decode kernel on both cache formats, and both few-row linears with the
+quantiser at the launch plans that the few-row tests' shapes reach.  They compare two commits as well, each from its own checkout with this
+file dropped in: the FP8-cache entry is `decode_attn_fp8kv` where the extension has it, else
+`decode_attn(..., cache_scale=)`.
 
 The `optim` family compares two COMMITS, not two builds: it covers the Python side of the fused
 optimizers' step as well, so drop this file into a checkout of the other commit, build the
@@ -413,6 +419,97 @@ def optim(device="cpu"):
     return out
 
 
+def decode():
+    """decode_attn on a bf16 and on an FP8 cache (filled by kv_fill_fp8 from the same values): Dh 64 and
+    128, G = H / Hkv = 1 .. 8 at Hkv = 2 - all 32 instantiations - Tmax 320, B = 3, two ragged position
+    sets, window off and 5, RoPE off and on, 1 and 5 splits, the "randn" inputs of tests/decode_ref.py.
+    Cache rows at or beyond pos are zero, so `out`, `part` and the cache after the call compare by
+    plain equality."""
+    from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+    from ray_torch_distributed_checkpoint_amd.ops.llama_ops import rope_tables
+    from tests import decode_ref as D
+
+    ext, out, B, Tmax, Hkv = gpu_ext(), {}, 3, 320, 2
+    old = hasattr(ext, "decode_attn_fp8kv")
+    for Dh in (64, 128):
+        tables = rope_tables(Tmax, Dh, 500000.0, "cuda")
+        for G in range(1, 9):
+            H = G * Hkv
+            qkv_new, cache = D.decode_inputs("randn", B, Tmax, H, Hkv, Dh, dev="cuda")
+            # kv_fill_fp8 reads the k|v tail of a packed qkv: zero q heads in front of the cache rows
+            packed = torch.cat([torch.zeros((B, Tmax, H * Dh), dtype=cache.dtype, device="cuda"), cache], dim=2)
+            for pos in ((0, 319, 64), (63, 65, 127)):
+                p = torch.tensor(pos, dtype=torch.int32, device="cuda")
+                used = (torch.arange(Tmax, device="cuda")[None] < p[:, None])[:, :, None]
+                for window in (0, 5):
+                    for rope in (False, True):
+                        cos, sin = tables if rope else (None, None)
+                        for ns in (1, 5):
+                            res = {}
+                            for fmt in ("bf16", "fp8"):
+                                o = torch.zeros((B, H * Dh), dtype=torch.bfloat16, device="cuda")
+                                part = torch.zeros(B * H * ns * (Dh + 2), device="cuda")
+                                if fmt == "bf16":
+                                    c = torch.where(used, cache, torch.zeros_like(cache))
+                                    ext.decode_attn(qkv_new, c, p, cos, sin, o, part, H, Hkv, window, ns, Dh ** -0.5)
+                                    kept = {"cache": c}
+                                else:
+                                    cq = torch.zeros((B, Tmax, 2 * Hkv * Dh), dtype=torch.float8_e4m3fn, device="cuda")
+                                    cs = torch.zeros((B, Tmax, 2 * Hkv), device="cuda")
+                                    ext.kv_fill_fp8(packed, cq, cs, H, Tmax)
+                                    cq = torch.where(used, cq.view(torch.uint8), torch.zeros_like(cq.view(torch.uint8)))
+                                    cq, cs = cq.view(torch.float8_e4m3fn), torch.where(used, cs, torch.zeros_like(cs))
+                                    if old:
+                                        ext.decode_attn_fp8kv(qkv_new, cq, cs, p, cos, sin, o, part, H, Hkv, window, ns,
+                                                              Dh ** -0.5)
+                                    else:
+                                        ext.decode_attn(qkv_new, cq, p, cos, sin, o, part, H, Hkv, window, ns, Dh ** -0.5,
+                                                        cache_scale=cs)
+                                    kept = {"cache": cq.view(torch.uint8), "scale": cs}
+                                torch.cuda.synchronize()
+                                kept.update(out=o, part=part)
+                                res[fmt] = {k: v.cpu() for k, v in kept.items()}
+                            out[f"d{Dh}.G{G}.pos{pos[0]}.w{window}.{'rope' if rope else 'plain'}.ns{ns}"] = res
+    return out
+
+
+def few_rows():
+    """gemm_few_rows on the (N, K) of tests/few_rows_cases.py, gemm_few_rows_fp8 and quantize_fp8_rows
+    (fp32 and bf16 source) on those of tests/test_few_rows_fp8_gpu.py: the launch plans those tests reach
+    (of the FP8 kernel's 13 (T, W) instantiations, the six that PLANS lists), recorded with the values;
+    M = 1, 7, 16; no epilogue, bf16 bias + residual, fp32 bias + GELU."""
+    from ray_torch_distributed_checkpoint_amd.ops._ext import gpu_ext
+    from tests.few_rows_cases import SHAPES
+    from tests.test_few_rows_fp8_gpu import PLANS
+
+    ext, out = gpu_ext(), {}
+    for kind, shapes in (("bf16", SHAPES), ("fp8", tuple(PLANS))):
+        for N, K in shapes:
+            g = torch.Generator().manual_seed(31 * N + K)
+            w = (torch.randn(N, K, generator=g) * K ** -0.5).cuda()
+            case = {"plan": list(ext.few_rows_plan(N, K) if kind == "bf16" else ext.few_rows_fp8_plan(N, K))}
+            if kind == "fp8":
+                q = torch.zeros((N, K), dtype=torch.float8_e4m3fn, device="cuda")
+                sc, qb, sb = torch.zeros(N, device="cuda"), torch.zeros_like(q), torch.zeros(N, device="cuda")
+                ext.quantize_fp8_rows(w, q, sc)
+                ext.quantize_fp8_rows(w.bfloat16(), qb, sb)
+                case.update(q=q.view(torch.uint8).cpu(), scale=sc.cpu(), q_bf16=qb.view(torch.uint8).cpu(), scale_bf16=sb.cpu())
+            for M in (1, 7, 16):
+                x = torch.randn(M, K, generator=g).bfloat16().cuda()
+                res = torch.randn(M, N, generator=g).bfloat16().cuda()
+                bias = torch.randn(N, generator=g).cuda()
+                for epi, b, r, act in (("plain", None, None, 0), ("bias_res", bias.bfloat16(), res, 0), ("bias_f32_gelu", bias, None, 2)):
+                    y = torch.zeros((M, N), dtype=torch.bfloat16, device="cuda")
+                    if kind == "bf16":
+                        ext.gemm_few_rows(x, w.bfloat16(), b, r, y, act)
+                    else:
+                        ext.gemm_few_rows_fp8(x, q, sc, b, r, y, act)
+                    torch.cuda.synchronize()
+                    case[f"M{M}.{epi}"] = y.cpu()
+            out[f"{kind}.{N}x{K}"] = case
+    return out
+
+
 def compare(a, b, path=""):
     """(values compared, paths that differ) of two dumps: tensors by torch.equal, the rest by ==."""
     if isinstance(a, dict) and isinstance(b, dict) and a.keys() == b.keys():
@@ -439,5 +536,5 @@ if __name__ == "__main__":
         print(f"{len(a)} cases, {n} values compared, {len(bad)} mismatches")
         sys.exit(1 if bad else 0)
     family = {"attn": attn, "norm": norm, "colsum": colsum, "xent": xent, "resnet": resnet, "gemm": gemm,
-              "optim": optim}[sys.argv[1]]
+              "optim": optim, "decode": decode, "few_rows": few_rows}[sys.argv[1]]
     torch.save(family(*sys.argv[3:]), sys.argv[2])

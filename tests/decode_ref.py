@@ -1,4 +1,5 @@
-"""Yardstick of the decode attention kernel (csrc/kernels/attn_decode.hip), in the manner of the
+"""Yardstick of the decode attention kernel (csrc/kernels/attn_decode.hip, both cache formats:
+tests/test_decode_gpu.py on the bf16 cache, tests/test_decode_fp8kv_gpu.py on the e4m3 one), in the manner of the
 attention section of tests/ulp.py, whose helpers it reuses unchanged.
 
 `decode_ref` in float64 is the reference: for row b the keys max(0, pos - window + 1) .. pos, key

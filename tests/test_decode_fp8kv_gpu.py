@@ -1,11 +1,11 @@
-"""The FP8 KV cache kernels (csrc/kernels/attn_decode_fp8.hip) on the GPU, on the shapes of
+"""The FP8 KV cache kernels (csrc/kernels/attn_decode.hip, the e4m3 cache format) on the GPU, on the shapes of
 tests/decode_ref.py: the quantising fill and the stored row bit for bit against the CPU formula
 (ops.quantize_fp8_rows of the [*, Dh] view), `out` per element against fp64, bitwise properties.
 
 The reference of `out` is decode_ref(F64) on the dequantised cache, the new row dequantised too
 (code * scale is exact in fp64), so it already holds the quantised values and the kernel adds no
 bf16 term.  Counted from the source as decode_ref's docstring counts, the kernel adds two fp32
-roundings to attn_decode.hip's: one multiply per score (the group sum times kscale * scale * log2 e,
+roundings to the bf16 cache's: one multiply per score (the group sum times kscale * scale * log2 e,
 itself one rounding per key in place of the host's scale * log2 e) and one per key and head
 (p * vscale).  That is Dh + 65 and Tmax + 65 terms where decode_ref allows Dh + 64 and Tmax + 64; the
 test keeps decode_ref's allowance as it is, the narrower of the two.  WORST lines of one run:
@@ -84,8 +84,8 @@ def _launch(qkv_new, cq0, cs0, pos, H, Hkv, Dh, window, rope, nsplit, fill=NANB)
     obuf = torch.full((B + 2, H * Dh), NAN, dtype=U.BF16, device=DEV)
     pbuf = torch.full((3, B * H * nsplit * (Dh + 2)), NAN, dtype=torch.float32, device=DEV)
     cos, sin = _tables(Dh) if rope else (None, None)
-    _ext().decode_attn_fp8kv(qkv_new, qbuf[1:B + 1].view(F8), sbuf[1:B + 1], p, cos, sin, obuf[1:B + 1], pbuf[1],
-                             H, Hkv, window or 0, nsplit, 1.0 / math.sqrt(Dh))
+    _ext().decode_attn(qkv_new, qbuf[1:B + 1].view(F8), p, cos, sin, obuf[1:B + 1], pbuf[1],
+                       H, Hkv, window or 0, nsplit, 1.0 / math.sqrt(Dh), cache_scale=sbuf[1:B + 1])
     torch.cuda.synchronize()
     assert _guards_intact(qbuf, sbuf, B), "guard slab of the cache was written"
     assert all(bool(torch.isnan(t).all()) for t in (obuf[0], obuf[B + 1], pbuf[0], pbuf[2])), "guard slab written"
@@ -180,6 +180,11 @@ def test_operator_follows_the_cache_and_refuses_bad_tensors():
     for bad_q, bad_s in ((cq0, cs0), (cq0.view(F8), cs0.double()), (cq0.view(F8)[:, :, :Dh].contiguous(), cs0),
                          (cq0.view(F8), cs0[:, :64].contiguous())):
         with pytest.raises(RuntimeError, match="cache_q"):
-            _ext().decode_attn_fp8kv(qkv_new, bad_q, bad_s, p, None, None, o, part, H, Hkv, 0, 1, 0.1)
+            _ext().decode_attn(qkv_new, bad_q, p, None, None, o, part, H, Hkv, 0, 1, 0.1, cache_scale=bad_s)
         with pytest.raises(RuntimeError, match="cache_q"):
             _ext().kv_fill_fp8(qkv, bad_q, bad_s, H, 1)
+    with pytest.raises(RuntimeError, match="needs its cache_scale"):       # an FP8 cache without its scales
+        _ext().decode_attn(qkv_new, cq0.view(F8), p, None, None, o, part, H, Hkv, 0, 1, 0.1)
+    with pytest.raises(RuntimeError, match="float8_e4m3fn cache_q"):       # a bf16 cache with scales
+        _ext().decode_attn(qkv_new, torch.zeros(cq0.shape, dtype=U.BF16, device=DEV), p, None, None, o, part,
+                           H, Hkv, 0, 1, 0.1, cache_scale=cs0)

@@ -1020,7 +1020,7 @@ static std::vector<int64_t> few_rows_fp8_plan(int64_t N, int64_t K) {
   rtdc_few_rows_fp8_plan(N, K, &tiles, &waves, &per);
   return {tiles, waves, per};
 }
-// Per-row e4m3 quantisation (gemm_few_rows_fp8.hip): scale[n] = max_k |w[n, k]| / 448 (1 for a zero row),
+// Per-row e4m3 quantisation (gemm_few_rows_fp8.hip): scale[n] = max_k |w[n, k]| / 448 (1 where that is not > 0),
 // q[n, k] = rne_e4m3(w[n, k] / scale[n]); w [N, K] contiguous fp32 or bf16, K % 16 == 0.
 static void quantize_fp8_rows(Tensor w, Tensor q, Tensor scale) {
   TORCH_CHECK(w.dim() == 2 && w.is_contiguous() && (w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16),

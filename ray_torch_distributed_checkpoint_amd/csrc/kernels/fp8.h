@@ -1,8 +1,11 @@
 // OCP e4m3 for gfx950, the one formula every FP8 kernel of this project quantises and widens by:
-//   scale = amax / 448 (a true fp32 division; 1.0 for an all-zero run), code = rne_e4m3(x / scale),
-// and every e4m3 value is a bf16 value, so the widening is exact.  quant_fp8_rows_kernel
-// (gemm_few_rows_fp8.hip), kv_fill_fp8_kernel and the decode kernel's owner (attn_decode.hip) must
-// agree bit for bit: they all come here.
+//   scale = amax / 448 (a true fp32 division), or 1.0 where that quotient is not > 0: an all-zero
+//   run, and a run so small (amax <= 448 * 2^-150, about 3e-43) that the quotient underflows to
+//   zero, whose codes are then all zero; code = rne_e4m3(x / scale),
+// and every e4m3 value is a bf16 value, so the widening is exact.  The scale is never zero, so no
+// finite run divides by it into NaN codes.  quant_fp8_rows_kernel (gemm_few_rows_fp8.hip),
+// kv_fill_fp8_kernel and the decode kernel's owner (attn_decode.hip) must agree bit for bit: they
+// all come here.
 #pragma once
 #include "common.h"
 
@@ -11,7 +14,10 @@ namespace rtdc {
 typedef __attribute__((ext_vector_type(2))) __bf16 fp8_bf16x2;
 
 // the scale of a run from its largest magnitude
-__device__ __forceinline__ float fp8_scale(float amax) { return amax > 0.f ? __fdiv_rn(amax, 448.f) : 1.f; }
+__device__ __forceinline__ float fp8_scale(float amax) {
+  const float s = __fdiv_rn(amax, 448.f);
+  return s > 0.f ? s : 1.f;
+}
 
 // v[0 .. 3] / s -> four e4m3 bytes, v[0] in the lowest (v_cvt_pk_fp8_f32 twice)
 __device__ __forceinline__ uint32_t fp8_pack4(const float* v, float s) {

@@ -1,8 +1,8 @@
 // FP8-weight few-row linear for gfx950:
 //   y[M, N] = act((x[M, K] . q[N, K]^T) * scale[n] + bias + residual), 1 <= M <= 16,
 // q OCP e4m3 (one byte per weight), scale fp32 per weight row, x / residual / y bf16, and the
-// quantiser that makes (q, scale) from a weight:  scale[n] = max_k |w[n, k]| / 448 (1 for a zero
-// row), q[n, k] = rne_e4m3(w[n, k] / scale[n]), both divisions true fp32 divisions.
+// quantiser that makes (q, scale) from a weight:  scale[n] = max_k |w[n, k]| / 448 (1 where that
+// is not > 0: fp8.h), q[n, k] = rne_e4m3(w[n, k] / scale[n]), both divisions true fp32 divisions.
 //
 // A decode step's linear is a read of its weights; a bf16 kernel cannot go below its bytes, so
 // this one reads half of them.  Every e4m3 value is a bf16 value: the weights are widened in

@@ -4,11 +4,14 @@ reads them (csrc/kernels/gemm_few_rows_fp8.hip) and the cache of a parameter's i
 Weight-only: activations, the KV cache, norms, biases and embeddings stay as they are.  The
 quantisation of a weight w [N, K], per row n:
 
-    scale[n] = max_k |w[n, k]| / 448        (fp32 division; 1.0 for an all-zero row)
+    scale[n] = max_k |w[n, k]| / 448        (fp32 division; 1.0 where the quotient is not > 0)
     q[n, k]  = rne_e4m3(float(w[n, k]) / scale[n])      (a true fp32 division)
 
-No quotient exceeds 448 by more than an fp32 rounding, so nothing saturates or becomes NaN.  The
-GPU kernels and the torch formulas below give the same bits.
+The scale is 1.0 for an all-zero row and for a row so small that the division underflows to zero
+(a maximum of about 3e-43 or less: its codes are all zero), so it is never zero: no finite row divides
+by zero.  For a finite row no quotient exceeds 448 by more than an fp32 rounding, so no code saturates or is
+NaN; a row whose scale is a subnormal fp32 (a maximum below about 5e-36) is quantised more coarsely.  A row
+that holds inf or NaN is not defined here.  The GPU kernels and the torch formulas below give the same bits.
 """
 from __future__ import annotations
 
@@ -25,7 +28,8 @@ FP8_MAX = 448.0
 def quantize_fp8_rows(w: torch.Tensor, out=None):
     """w [N, K] contiguous, fp32 or bf16 -> (q [N, K] float8_e4m3fn, scale [N] fp32) by the formula
     of this module; out=(q, scale) writes into existing storage.  On the GPU one launch of
-    quant_fp8_rows_kernel (K % 16 == 0); on the CPU the formula in torch."""
+    quant_fp8_rows_kernel (K % 16 == 0); on the CPU the formula in torch.  Finite weights only: what a
+    row that holds inf or NaN gives is not defined."""
     if w.dim() != 2 or w.dtype not in (torch.float32, torch.bfloat16) or not w.is_contiguous():
         raise ValueError("quantize_fp8_rows: a contiguous fp32 or bf16 [N, K] weight expected")
     N, K = w.shape
@@ -41,7 +45,8 @@ def quantize_fp8_rows(w: torch.Tensor, out=None):
             wf = w.detach().float()
             amax = wf.abs().amax(dim=1)
             # (a tensor divisor: a Python scalar would be turned into a multiplication by 1 / 448)
-            s = torch.where(amax > 0, amax / torch.full_like(amax, FP8_MAX), torch.ones_like(amax))
+            s = amax / torch.full_like(amax, FP8_MAX)
+            s = torch.where(s > 0, s, torch.ones_like(s))   # a zero row, or a quotient that underflowed
             scale.copy_(s)
             q.copy_((wf / s[:, None]).to(FP8))
     return q, scale
